@@ -17,9 +17,18 @@ over xGMI between staging buffers the ranks share (owners pull their slices devi
 no collective kernel has to find room beside a scan), after a self-test every rank passed; otherwise RCCL send / receive groups with
 the exchange gate.  MDBG_COMM_MODE=peer|rccl|auto selects; MDBG_BENCH_EXCHANGE=torch moves the bytes with torch.distributed instead.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up, warms up, times the N steps,
+writes the last step's outputs when --dump-outputs DIR is given, and prints the line.  Everything else below -- the CPU baseline,
+the parity checks, the self-checks, the kminmer roofline and the legs -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float64, integers split into exact
+32-bit halves where they are wider; at N > 1 every rank writes <name>_rank<r>.npy): the k-min-mer table's row count, solid count and
+order-independent sums over ALL its rows, a fixed sample of its rows chosen by key and sorted by key, and the minimizers of a fixed,
+seeded sample of reads before and after the palindrome purge.  The inputs are seeded, so two builds can be compared output for output.
+
 Prints ONE compact JSON line (rank 0; under 4 KB -- compact_line below; the full result goes to bench_detail.json next to this script
 and to stderr) with `roofline` (dominant kernel, HIP-event timed on the library's stream; `traffic` only from a PMC
-collection made on this very csrc/scan.hip), `roofline_kminmer` (the table kernels alone: 4 M + 16 I + 20 D bytes, and the atomic-rate
+collection made on this very csrc/scan.hip) and, with --full, `roofline_kminmer` (the table kernels alone: 4 M + 16 I + 20 D bytes, and the atomic-rate
 ceiling of the insert), `cpu_baseline` (the reference's own code, oracle/_ref/refdrv, timed on this box's cores on BASELINE.json
 configs[1] whole -- 1 M reads, 10 Gbp; `path_only` = up to the moment its tables are on disk) and, at N=1, `parity` (the HIP path's
 read_data_init bytes, corrected reads, k-min-mer table and abundance checksum against the reference's files for that whole config, plus
@@ -28,7 +37,7 @@ reference from the same FASTA file), `multik` (configs[2]: k = 4..11 over the re
 (configs[2] in the reference's own mode: its graph -> contig -> toMinspace loop on 200 000 reads, mdbg_tool graph's tables against the
 reference's at every k), `pcie` (reads arriving over the link, synchronous and pipelined) and `ont` (configs[3] at its stated size: 10 M
 x 20 kb reads with qualities in three resident pieces, parity on a 100 000-read sample).
-At N>1 the line carries a `parity` block too: one more sharded step, its per-rank tables reduced to counts and order-independent sums,
+At N>1 with --full the line carries a `parity` block too: one more sharded step, its per-rank tables reduced to counts and order-independent sums,
 all-reduced and compared with the single-GPU first pass over ALL the reads that rank 0 runs alone; `config.exchange` reports the
 communicator's rank count, wire bytes and exchange time per step.  A mismatch fails the run.
 """
@@ -69,9 +78,14 @@ def parse_args():
                                                                 "words it: 40 M reads at 1 / 2 / 4 / 8 GPUs); overrides --reads, the line says \"scaling\": \"strong\"")
     ap.add_argument("--read-len", type=int, default=10_000)
     ap.add_argument("--in-flight", type=int, default=2, help="batches processed concurrently per GPU (own context, stream and host thread each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and side measurements after the timed steps: kminmer roofline, self-checks, CPU baseline, parity, legs "
+                         "(N=1), the single-GPU parity pass (N>1); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; a fixed sample of the table, all of its sums)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000,
-                    help="reads of the CPU-baseline / parity read set, a HiFi set of its own at 50x (1 M = BASELINE.json configs[1]; 0 = skip)")
-    ap.add_argument("--legs", default="all", help="N=1 only: comma list of end_to_end,multik,multik_reference,pcie,ont,graph_per_k ('all', 'none')")
+                    help="--full: reads of the CPU-baseline / parity read set, a HiFi set of its own at 50x (1 M = BASELINE.json configs[1]; 0 = skip)")
+    ap.add_argument("--legs", default="all", help="--full, N=1 only: comma list of end_to_end,multik,multik_reference,pcie,ont,graph_per_k ('all', 'none')")
     ap.add_argument("--multik-sample", type=int, default=200_000, help="reads of the multik_reference leg (the reference's own loop k = 4..11)")
     ap.add_argument("--ont-reads", type=int, default=10_000_000, help="reads (20 kb, with qualities) of the ont leg: BASELINE.json configs[3]")
     ap.add_argument("--ont-sample", type=int, default=100_000, help="reads of the ont leg's parity sample against the reference")
@@ -210,6 +224,96 @@ def emit(out: dict, json_fd: int, detail_path: str | None = None) -> None:
         print(f"[bench] {detail_path} not written: {exc}", file=sys.stderr)
     print("[bench] full result: " + full, file=sys.stderr, flush=True)
     os.write(json_fd, (json.dumps(compact_line(out)) + "\n").encode())
+
+
+DUMP_SEED = 0x5EED_2026                 # --dump-outputs: which table rows and which reads are sampled
+DUMP_TABLE_ROWS = 1 << 18               # the table's sample holds about this many rows and never more than twice as many (9 float64 each)
+DUMP_READ_RANGES, DUMP_READS_PER_RANGE = 64, 64     # minimizers of 64 runs of 64 consecutive reads
+
+
+def _halves(a):
+    """u64 values as exact float64: a trailing axis of (low 32 bits, high 32 bits)."""
+    import numpy as np
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def _table_sample(table):
+    """The rows whose key falls in a fixed, seeded 2^-shift of the key space (the same keys whatever the row order the pass left),
+    sorted by key: (lo, hi, abundance, vectors or None, shift)."""
+    import numpy as np
+    n = table.info()["n_records"]
+    shift = 0
+    while (n >> shift) > DUMP_TABLE_ROWS:
+        shift += 1
+    recs, vecs = [], []
+    chunk = 1 << 22
+    for first in range(0, n, chunk):
+        rec, vec = table.to_host_range(first, min(chunk, n - first))
+        if shift:
+            mixed = (rec["lo"] ^ np.uint64(DUMP_SEED)) * np.uint64(0x9E3779B97F4A7C15)      # (wraps modulo 2^64)
+            sel = (mixed >> np.uint64(64 - shift)) == 0
+            rec, vec = rec[sel], (vec[sel] if vec is not None else None)
+        recs.append(rec)
+        if vec is not None:
+            vecs.append(vec)
+    from metamdbg_amd.formats import ABUNDANCE_DTYPE
+    rec = np.concatenate(recs) if recs else np.zeros(0, ABUNDANCE_DTYPE)
+    order = np.lexsort((rec["lo"], rec["hi"]))[: 2 * DUMP_TABLE_ROWS]
+    vec = np.concatenate(vecs)[order] if vecs else None
+    rec = rec[order]
+    return rec["lo"], rec["hi"], rec["abundance"], vec, shift
+
+
+def _read_sample(ctx, m, first_read: int):
+    """Minimizers of a fixed, seeded set of read runs of m: (global read indices, CSR offsets, minimizer values)."""
+    import numpy as np
+    n_reads = m.info()["n_reads"]
+    per = min(DUMP_READS_PER_RANGE, n_reads)
+    if per == 0:
+        return np.zeros(0, np.uint64), np.zeros(1, np.uint64), np.zeros(0, np.uint32)
+    runs = n_reads // per
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(runs, size=min(DUMP_READ_RANGES, runs), replace=False)) * per
+    reads, counts, values = [], [], []
+    for s in starts:
+        part = ctx.minimizers_slice(m, int(s), per)
+        h = part.to_host(full=False)
+        part.free()
+        reads.append(np.arange(s, s + per, dtype=np.uint64) + np.uint64(first_read))
+        counts.append(np.diff(h["offsets"].astype(np.int64)))
+        values.append(h["minimizers"])
+    offsets = np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.uint64)
+    return np.concatenate(reads), offsets, np.concatenate(values)
+
+
+def dump_outputs(out_dir: str, kept: dict, first_read: int, rank: int, world: int) -> int:
+    """--dump-outputs: what the last timed step computed -- its k-min-mer table (counts and order-independent sums over all rows, a sample of
+    rows) and the minimizers of sampled reads before and after the purge -- as float64 .npy files in out_dir.  Frees the step's objects;
+    returns the bytes written."""
+    import numpy as np
+    mins, corr, table = kept["mins"], kept["corr"], kept["table"]
+    ctx = mins.ctx
+    ti = table.info()
+    lo, hi, abundance, vec, shift = _table_sample(table)
+    arrays = {"counts": np.array([mins.info()["n_reads"], mins.info()["n_minimizers"], corr.info()["n_minimizers"], ti["n_records"], ti["n_solid"]],
+                                 dtype=np.float64),
+              "table_checksum": _halves(table.checksum()),
+              "table_sample_shift": np.array([shift], dtype=np.float64),
+              "table_keys": np.concatenate([_halves(lo), _halves(hi)], axis=1),
+              "table_abundance": abundance.astype(np.float64)}
+    if vec is not None:
+        arrays["table_vectors"] = vec.astype(np.float64)
+    reads, offsets, values = _read_sample(ctx, mins, first_read)
+    arrays.update(sampled_reads=reads.astype(np.float64), minimizer_offsets=offsets.astype(np.float64), minimizers=values.astype(np.float64))
+    _, offsets, values = _read_sample(ctx, corr, first_read)
+    arrays.update(purged_minimizer_offsets=offsets.astype(np.float64), purged_minimizers=values.astype(np.float64))
+    for o in (table, corr, mins):
+        o.free()
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 def _arm_deadline(rank: int, world: int, json_fd: int) -> None:
@@ -531,12 +635,16 @@ def main() -> None:
         ti = table.info()
         if collect:
             ti = dict(ti, sums=table.checksum(), stats=table.stats())
-        for o in (table, corr, mins):
-            o.free()
+        if index == dump_index:
+            kept.update(slot=slot, mins=mins, corr=corr, table=table)      # --dump-outputs: freed after the dump
+        else:
+            for o in (table, corr, mins):
+                o.free()
         return n_min, ti
 
     results: dict = {}
     errors: list = []
+    kept: dict = {}
 
     def run_steps(slot: int, indices: list):
         try:
@@ -565,6 +673,7 @@ def main() -> None:
     # start on slot 0
     n_warm = max(args.warmup, n_slots)
     n_warm += (-n_warm) % n_slots
+    dump_index = n_warm + args.steps - 1 if args.dump_outputs else -1     # the step whose objects step() keeps for the dump
     _phase("warm-up steps")
     run_phase(0, n_warm)
 
@@ -634,6 +743,12 @@ def main() -> None:
     for c, _ in slots:
         c.timing(False)
     acct1 = exchange_account() if exchange else None
+    if args.dump_outputs:
+        _phase("writing the outputs of the last timed step")
+        t_d = time.perf_counter()
+        nbytes = dump_outputs(args.dump_outputs, kept, rank * args.reads, rank, world)
+        print(f"[bench] rank {rank}: {nbytes / 1e6:.1f} MB of outputs of the last timed step in {args.dump_outputs} "
+              f"({time.perf_counter() - t_d:.2f} s)", file=sys.stderr, flush=True)
 
     # ---- N > 1: the job checks itself (after the timed region).  One more sharded step on every rank, its share of the table
     # reduced to record count, solid count and the order-independent sums of mdbg_table_checksum (sums[0] is the "Checksum
@@ -642,7 +757,7 @@ def main() -> None:
     # packed at N = 8, one MI355X holds them).  The union of the shares IS the single-GPU table, so a lost row, a count summed
     # twice or a key listed by two ranks shows here, in the run that is being scored.
     verify = None
-    if world > 1:
+    if world > 1 and args.full:
         v_min, v_ti = step(0, n_warm + args.steps, collect=True)
         halves = [v_ti["n_records"], v_ti["n_solid"], v_min] + [h for x in v_ti["sums"] for h in (x & 0xFFFFFFFF, x >> 32)]
         vt = torch.tensor(halves, dtype=torch.int64, device="cuda")
@@ -765,13 +880,13 @@ def main() -> None:
                     failed = not parity_n["table_equal"]
                 except Exception as exc:       # the check could not be made (memory on this box): the line says so; a made check that fails is fatal
                     parity_n = {"error": f"{type(exc).__name__}: {exc}", "sharded": verify, "reads": total_reads}
-        legs_on = set() if (world > 1 or args.legs == "none") else \
+        legs_on = set() if (world > 1 or not args.full or args.legs == "none") else \
             ({"end_to_end", "multik", "multik_reference", "pcie", "ont", "graph_per_k"} if args.legs == "all" else set(args.legs.split(",")))
         # ---- the table kernels on the record (4 M + 16 I + 20 D bytes per k): two steps of this context ALONE on
         # the device, timed by HIP events like the scan -- beside another batch's scan they share the CUs, that is not their speed
         kroof = None
         self_check = None
-        if world == 1:
+        if world == 1 and args.full:
             kroof = kminmer_roofline(ctx, reads, args.reads, args.read_len)
             # the timed workload's own table, at its full size: the whole batch against the union of the shares of its halves
             run_alone(ctx)
@@ -787,7 +902,7 @@ def main() -> None:
             if not self_check["all_equal"]:
                 failed = True
                 print(f"[bench] SELF-CHECK FAILURE (the timed workload's table against the shares of its halves): {self_check}", file=sys.stderr)
-        side = sample_legs(ctx, min(args.cpu_sample, args.reads), args.read_len, "end_to_end" in legs_on) if world == 1 else {}
+        side = sample_legs(ctx, min(args.cpu_sample, args.reads), args.read_len, "end_to_end" in legs_on) if world == 1 and args.full else {}
         base = side.get("cpu_baseline")
         legs = {}
         if "end_to_end" in side:
@@ -845,7 +960,7 @@ def main() -> None:
                                         "(configs[4]: 40 M over 8), so per-GPU work halves between the N=1 point and the others -- use --reads to hold it fixed"),
                        "kminmer_records": int(totals[0].item()), "solid": int(totals[1].item()),
                        "batches_in_flight": n_slots, "table_blocks_per_cu": table_blocks, "table_grid_blocks": table_grid, "table_cu_count": table_cus, "shared_device_options": shared_opts, "overlap_probe": probe, "device": info["arch"], "cus": info["n_cu"],
-                       "exchange": exch},
+                       "exchange": exch, "full": args.full},
             "roofline": {"bound": "valu", "kernel": "scan_fast_kernel<HPC=1,QUAL=0,APPROX=1> (_ZN4mdbg16scan_fast_kernelILb1ELb0ELb1EEEvNS_8ScanArgsE)", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
                          "bound_note": "`achieved` / `peak` / `frac` are the kernel's algorithmic bytes over its launch time against the HBM peak, as the "

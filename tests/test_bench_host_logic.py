@@ -157,3 +157,59 @@ def test_counter_traffic_is_reported_only_for_the_sources_it_was_collected_on(tm
     t, note = bench.index_traffic(10_000_000, 10_000)
     assert t == {"refined": 35.0e9, "index": 46.0e9} and "y_index_traffic.json" in note
     assert bench.index_traffic(1_000_000, 10_000)[0] is None
+
+
+class _FakeTable:
+    """What dump_outputs asks of a capi.Table, over host arrays."""
+    def __init__(self, rec, vec):
+        self.rec, self.vec = rec, vec
+
+    def info(self):
+        return {"k": self.vec.shape[1], "n_records": len(self.rec), "n_solid": int((self.rec["abundance"] > 1).sum()), "has_vectors": True}
+
+    def to_host_range(self, first, count):
+        return self.rec[first:first + count].copy(), self.vec[first:first + count].copy()
+
+
+def _fake_table(n, seed):
+    import numpy as np
+    from metamdbg_amd.formats import ABUNDANCE_DTYPE
+    rng = np.random.default_rng(seed)
+    rec = np.zeros(n, ABUNDANCE_DTYPE)
+    rec["lo"] = rng.integers(0, 2 ** 63, n, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    rec["hi"] = rng.integers(0, 2 ** 63, n, dtype=np.uint64)
+    rec["abundance"] = rng.integers(1, 60, n)
+    vec = rng.integers(0, 2 ** 32, (n, 4), dtype=np.uint32)
+    return rec, vec
+
+
+def test_the_dumped_table_sample_is_chosen_by_key_whatever_the_row_order(monkeypatch):
+    """--dump-outputs compares two builds output for output: the table's rows come in whatever order the pass left them, so the sample is a
+    fixed part of the key space, sorted by key -- the same rows and the same arrays from any order -- and stays within its size cap."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_TABLE_ROWS", 1000)
+    rec, vec = _fake_table(37_000, seed=5)
+    lo, hi, ab, v, shift = bench._table_sample(_FakeTable(rec, vec))
+    perm = np.random.default_rng(9).permutation(len(rec))
+    lo2, hi2, ab2, v2, shift2 = bench._table_sample(_FakeTable(rec[perm], vec[perm]))
+    assert shift == shift2 == 6 and 300 < len(lo) <= 2000
+    assert np.array_equal(lo, lo2) and np.array_equal(hi, hi2) and np.array_equal(ab, ab2) and np.array_equal(v, v2)
+    assert np.all(np.diff(hi.astype(np.float64)) >= 0)
+    rows = {(int(a), int(b)): (int(c), tuple(int(x) for x in d)) for a, b, c, d in zip(rec["lo"], rec["hi"], rec["abundance"], vec)}
+    assert all(rows[(int(a), int(b))] == (int(c), tuple(int(x) for x in d)) for a, b, c, d in zip(lo, hi, ab, v))
+    # a table under the cap goes whole
+    lo3, _, _, _, shift3 = bench._table_sample(_FakeTable(rec[:900], vec[:900]))
+    assert shift3 == 0 and sorted(lo3.tolist()) == sorted(rec["lo"][:900].tolist())
+
+
+def test_u64_values_are_dumped_as_exact_float64_halves():
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    x = np.array([0, 1, 2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1, 0x0123456789ABCDEF], dtype=np.uint64)
+    h = bench._halves(x)
+    assert h.dtype == np.float64 and h.shape == (6, 2)
+    back = h[:, 0].astype(np.uint64) | (h[:, 1].astype(np.uint64) << np.uint64(32))
+    assert np.array_equal(back, x)

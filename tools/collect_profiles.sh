@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/collect_profiles.sh <tag>
 # Writes under gpurun_out/<tag>/ what profiles/<tag>_* is made of:
-#   bench_stdout.json            python bench.py (default flags: N=1, 10 M reads, parity + cpu_baseline + legs)
+#   bench_stdout.json            python bench.py --full (N=1, 10 M reads, parity + cpu_baseline + legs)
 #   bench_in_flight_1.json       one context, no legs
 #   bench_kernel_stats.txt       rocprofv3 --kernel-trace of the timed workload alone (--legs none): the scan launches are the bench's
 #   bench_legs_kernel_stats.txt  the same with the legs (multik, pcie, ont, parity sample): every kernel they run
@@ -13,13 +13,13 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$PWD
-timeout 600 python bench.py > $OUT/bench_stdout.json 2> $OUT/bench_stderr.log
+timeout 600 python bench.py --full > $OUT/bench_stdout.json 2> $OUT/bench_stderr.log
 timeout 300 python bench.py --in-flight 1 --steps 20 --legs none --cpu-sample 0 > $OUT/bench_in_flight_1.json 2>> $OUT/bench_stderr.log
 # the timed workload alone (warm-up, overlap probe and timed steps: every scan launch is the 10 M-read batch), then the legs
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $ROOT/$OUT/kt -o kt -- python $ROOT/bench.py --steps 10 --warmup 3 --legs none --cpu-sample 0 > $ROOT/$OUT/kt_bench.json 2> $ROOT/$OUT/kt.err )
 python tools/rocpd_summary.py $OUT/kt/kt_results.db > $OUT/bench_kernel_stats.txt 2>&1
 rm -rf $OUT/kt
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $ROOT/$OUT/ktl -o kt -- python $ROOT/bench.py --steps 3 --warmup 3 --cpu-sample 20000 > $ROOT/$OUT/kt_legs_bench.json 2> $ROOT/$OUT/kt_legs.err )
+( cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace -d $ROOT/$OUT/ktl -o kt -- python $ROOT/bench.py --steps 3 --warmup 3 --full --cpu-sample 20000 > $ROOT/$OUT/kt_legs_bench.json 2> $ROOT/$OUT/kt_legs.err )
 python tools/rocpd_summary.py $OUT/ktl/kt_results.db > $OUT/bench_legs_kernel_stats.txt 2>&1
 rm -rf $OUT/ktl
 for c in FETCH_SIZE WRITE_SIZE; do
