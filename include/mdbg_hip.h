@@ -362,6 +362,28 @@ int  mdbg_minimizers_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records,
                                        uint8_t *circular, mdbg_minimizers **out);
 int  mdbg_prev_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records, uint64_t n_records, mdbg_table **out);
 
+/* ---- FASTA / FASTQ text taken apart on the device -----------------------------------------------------------------------------------
+ * Replaces the host side of ReadParserParallel for a plain file: the kseq loop (KSEQ_INIT(gzFile, gzread), Commons.hpp:82) that
+ * ReadParser::parse / ReadParserParallel::parse run over every character (Commons.hpp:5827-5922).  The file's bytes travel as they are
+ * (mdbg_bytes_*); records are found, stripped of line ends and packed by kernels.  The result is the mdbg_reads that
+ * mdbg_reads_from_ascii builds from the same records (words, offsets, lengths, side masks, masked list, qualities).
+ *
+ * [begin, end) of `text` holds a whole number of records -- a whole file, or a slab cut at record starts -- and text[begin] is '>'
+ * (FASTA) or '@' (FASTQ); anything else is MDBG_EINVAL.  An empty range gives zero reads.  Uploads still in flight on `text` are
+ * waited for on the device.  info (optional) receives {format (0 FASTA, 1 FASTQ), n_reads, n_bases, n_masked}.
+ *
+ * FASTA: a record starts at every line whose first byte is '>'; that line is skipped; the sequence is every byte of the following
+ *        lines except \n, \r, space and tab (multi-line, LF or CR-LF, blank lines, a last line without \n).  A header directly
+ *        followed by a header is a read of length 0.  A non-header line that starts with '@' or '+' is refused (MDBG_EINVAL): kseq
+ *        would switch format there.
+ * FASTQ: four lines per record, counted, not recognised by their first byte (a quality line may start with '@' or '+'): line 4i
+ *        starts with '@', line 4i+2 with '+', line 4i+3 has as many bytes as line 4i+1 (one trailing \r dropped from both).  Lines of
+ *        nothing but \r after the last record are ignored.  Multi-line FASTQ, a length mismatch and a truncated last record are
+ *        MDBG_EINVAL with a message that names the first offending line; nothing is built.  Bases are stripped of space, tab and \r
+ *        as in FASTA (the quality of a stripped byte goes with it); quality bytes are otherwise passed through unchanged.
+ * A read longer than 0xFFFFFFF0 bases is MDBG_ERANGE. */
+int  mdbg_reads_from_fastx_bytes(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, mdbg_reads **out, uint64_t info[4]);
+
 /* Page-locked host memory for read batches handed to mdbg_reads_from_ascii / _from_packed: uploads from it
  * run at PCIe rate instead of through the driver's staging copies.  Release with mdbg_host_free. */
 int  mdbg_host_alloc(mdbg_ctx *ctx, size_t bytes, void **out);

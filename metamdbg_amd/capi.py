@@ -122,6 +122,7 @@ SIGNATURES = {
     "mdbg_bytes_free": (None, [_P]),
     "mdbg_minimizers_from_record_bytes": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.POINTER(_P)]),
     "mdbg_prev_from_record_bytes": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
+    "mdbg_reads_from_fastx_bytes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
 }
 
 _lib = None
@@ -339,7 +340,7 @@ class Context:
         """A file's bytes on the device, uploaded in pieces (tests: from ordinary memory, so every piece is a blocking copy)."""
         h = C.c_void_p()
         self.check(lib().mdbg_bytes_create(self.h, len(raw), C.byref(h)))
-        b = DeviceBytes(self, h)
+        b = DeviceBytes(self, h, len(raw))
         buf = np.frombuffer(raw, dtype=np.uint8)
         last = C.c_uint64(0)
         for at in range(0, len(raw), piece):
@@ -365,6 +366,18 @@ class Context:
         h = C.c_void_p()
         self.check(lib().mdbg_prev_from_record_bytes(self.h, b.h, n_records, C.byref(h)))
         return Table(self, h)
+
+    def reads_from_fastx_bytes(self, b: "DeviceBytes", begin: int = 0, end: int | None = None) -> "Reads":
+        """FASTA / FASTQ text on the device -> reads (mdbg_reads_from_fastx_bytes); [begin, end) holds whole records.  The returned
+        object's ``fastx_info`` is dict(format, n_reads, n_bases, n_masked)."""
+        if end is None:
+            end = b.n
+        h = C.c_void_p()
+        info = (C.c_uint64 * 4)()
+        self.check(lib().mdbg_reads_from_fastx_bytes(self.h, b.h, begin, end, C.byref(h), info))
+        r = Reads(self, h)
+        r.fastx_info = dict(format=int(info[0]), n_reads=int(info[1]), n_bases=int(info[2]), n_masked=int(info[3]))
+        return r
 
     def small_contigs(self, unitigs: "Minimizers", k: int, k_prev: int, prev: "Table") -> np.ndarray:
         """1 per unitig that IndexKminmerFunctor writes to smallContigs_k<k>.bin instead of indexing (k > 8 is the caller's test)."""
@@ -609,8 +622,8 @@ class Reads:
 
 
 class DeviceBytes:
-    def __init__(self, ctx: "Context", h):
-        self.ctx, self.h = ctx, h
+    def __init__(self, ctx: "Context", h, n: int):
+        self.ctx, self.h, self.n = ctx, h, n
 
     def free(self) -> None:
         if self.h:

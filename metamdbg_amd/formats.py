@@ -228,3 +228,69 @@ def table_digests(records, vectors, k: int) -> dict:
         raw = vectors if isinstance(vectors, (bytes, bytearray)) else np.asarray(vectors, dtype="<u4").tobytes()
         out["min_sorted_sha256"] = _sha(sorted_vector_records(raw, k))
     return out
+
+
+# ---- FASTA / FASTQ text: the record rules of mdbg_reads_from_fastx_bytes -------------------------------------------------------
+_FASTX_STRIP = b"\r \t"
+
+
+def _fastx_lines(data: bytes) -> list[bytes]:
+    """The lines of the text without their \\n; a text that ends with \\n has no empty last line."""
+    lines = data.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    return lines
+
+
+def _drop_cr(line: bytes) -> bytes:
+    return line[:-1] if line.endswith(b"\r") else line
+
+
+def fastx_records(data: bytes):
+    """(fmt, seqs, quals_or_None) of a plain FASTA (fmt 0) or FASTQ (fmt 1) text: what mdbg_reads_from_fastx_bytes builds on the
+    device, and where it refuses (ValueError here, MDBG_EINVAL there).  The rules are those of FastxReader::next
+    (metamdbg_amd/host/fastx.hpp, the reference's kseq loop) for the forms this entry point accepts:
+
+    * FASTA: a record starts at every line whose first byte is '>'; that line is skipped; the sequence is every byte of the
+      following lines except \\n, \\r, space and tab.  A non-header line that starts with '@' or '+' is refused.
+    * FASTQ: four lines per record, counted: line 4i starts with '@', line 4i+2 with '+', line 4i+3 is as long as line 4i+1 (one
+      trailing \\r dropped from both).  Lines of nothing but \\r after the last record are ignored; lines the text does not have count
+      as empty.  Bases are stripped of \\r, space and tab, and the quality of a stripped byte goes with it.
+    """
+    if not data:
+        return 0, [], None
+    if data[:1] not in (b">", b"@"):
+        raise ValueError("the text must begin with '>' or '@'")
+    lines = _fastx_lines(data)
+    if data[:1] == b">":
+        seqs: list[bytearray] = []
+        for i, line in enumerate(lines):
+            if line[:1] == b">":
+                seqs.append(bytearray())
+            elif line[:1] in (b"@", b"+"):
+                raise ValueError(f"FASTA line {i + 1} starts with '@' or '+'")
+            else:
+                seqs[-1] += line.translate(None, _FASTX_STRIP)
+        return 0, [bytes(s) for s in seqs], None
+    last = max(i for i, line in enumerate(lines) if line.strip(b"\r"))
+    n = (last + 1 + 3) // 4
+
+    def line_at(i: int) -> bytes | None:
+        return lines[i] if i < len(lines) else None
+
+    seqs2, quals = [], []
+    for r in range(n):
+        if lines[4 * r][:1] != b"@":
+            raise ValueError(f"FASTQ line {4 * r + 1} should start with '@'")
+        plus = line_at(4 * r + 2)
+        if plus is None or plus[:1] != b"+":
+            raise ValueError(f"FASTQ line {4 * r + 3} should start with '+'")
+        s, q = _drop_cr(line_at(4 * r + 1) or b""), _drop_cr(line_at(4 * r + 3) or b"")
+        if len(s) != len(q):
+            raise ValueError(f"FASTQ line {4 * r + 4}: {len(q)} qualities for a sequence line of {len(s)} bytes")
+        keep = [j for j in range(len(s)) if s[j] not in _FASTX_STRIP]
+        if len(keep) == len(s):
+            seqs2.append(s); quals.append(q)
+        else:
+            seqs2.append(bytes(s[j] for j in keep)); quals.append(bytes(q[j] for j in keep))
+    return 1, seqs2, quals

@@ -648,6 +648,12 @@ public:
         }
     }
 
+    // How the feeder looks at a plain file, for a caller that moves the text itself (mdbg_tool, MDBG_TOOL_DEVICE_PARSE): gzip or not,
+    // four-line FASTQ or not, and the last record start in (p, lim] (p if there is none).
+    static bool file_is_gzip(const std::string &path) { return is_gzip(path); }
+    static bool fastq_is_four_line(const char *p, const char *end) { return looks_four_line(p, end); }
+    static const char *cut_at_record_start(const char *p, const char *lim, const char *end, bool fastq) { return last_record_before(p, lim, end, fastq); }
+
     void recycle(ReadBatch *b) {
         b->clear();
         {

@@ -303,6 +303,54 @@ mdbg_reads *upload_batch(mdbg_ctx *ctx, ReadBatch &b, bool withQual) {
     return reads;
 }
 
+// ---- MDBG_TOOL_DEVICE_PARSE=1: plain FASTA / FASTQ files travel as text and are taken apart on the device ------------------------
+// (mdbg_reads_from_fastx_bytes).  The symbol is looked up weakly: a library without it (the CPU tests' double) means the host feed.
+extern "C" int mdbg_reads_from_fastx_bytes(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, mdbg_reads **out, uint64_t info[4])
+    __attribute__((weak));
+
+struct DeviceParsePlan {
+    struct Slab { const char *p; size_t n; int file; };
+    std::vector<Slab> slabs;            // whole records each, in read order
+    size_t maxSlab = 0;
+    std::vector<std::pair<void *, size_t>> maps;
+    // true: every file of the list is plain text that begins with '>' or '@' (FASTQ: four lines a record), mapped and cut at record
+    // starts by the feeder's own search into slabs of at most batchBases bytes; false: `why` says what stands against it
+    bool make(const std::vector<std::string> &files, size_t batchBases, std::string &why) {
+        using mdbg_host::ReadFeeder;
+        if (!mdbg_reads_from_fastx_bytes) { why = "the library has no mdbg_reads_from_fastx_bytes"; return false; }
+        for (size_t f = 0; f < files.size(); f++) {
+            const std::string &path = files[f];
+            if (ReadFeeder::file_is_gzip(path)) { why = path + " is compressed"; return false; }
+            const int fd = open(path.c_str(), O_RDONLY);
+            if (fd < 0) die("File not found: " + path);
+            struct stat st;
+            fstat(fd, &st);
+            if (st.st_size == 0) { close(fd); continue; }
+            const char *addr = (const char *)mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            close(fd);
+            if (addr == MAP_FAILED) die("mmap failed: " + path);
+            madvise((void *)addr, (size_t)st.st_size, MADV_SEQUENTIAL);
+            maps.emplace_back((void *)addr, (size_t)st.st_size);
+            const char *end = addr + st.st_size;
+            const bool fastq = *addr == '@';
+            if (!fastq && *addr != '>') { why = path + " does not begin with '>' or '@'"; return false; }
+            if (fastq && !ReadFeeder::fastq_is_four_line(addr, end)) { why = path + " is not four-line FASTQ, which the device parse refuses"; return false; }
+            for (const char *p = addr; p < end;) {
+                const char *q = end;
+                if ((size_t)(end - p) > batchBases) {
+                    q = ReadFeeder::cut_at_record_start(p, p + batchBases, end, fastq);
+                    if (q == p) die("a single read is larger than the batch size; raise --batch-bases");
+                }
+                slabs.push_back(Slab{p, (size_t)(q - p), (int)f});
+                maxSlab = std::max(maxSlab, (size_t)(q - p));
+                p = q;
+            }
+        }
+        return true;
+    }
+    void unmap() { for (auto &m : maps) munmap(m.first, m.second); maps.clear(); }
+};
+
 mdbg_scan_params scan_params(const Parameters &P, float density, const std::vector<uint32_t> &rep, float minQ, bool filters) {
     mdbg_scan_params p{};
     p.minimizer_size = (uint32_t)P.minimizerSize;
@@ -601,10 +649,24 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         auto alloc = [](size_t n) -> void * { void *p = nullptr; return mdbg_host_alloc(g_ctx, n, &p) == MDBG_OK ? p : nullptr; };
         auto release = [](void *p) { mdbg_host_free(g_ctx, p); };
         std::unique_ptr<mdbg_host::ReadFeeder> feeder;
-        try { feeder.reset(new mdbg_host::ReadFeeder(read_input_list(inputList), a.batchBases, a.threads, 0, alloc, release, nConsumers)); }
-        catch (const std::exception &e) { die(e.what()); }
+        // MDBG_TOOL_DEVICE_PARSE=1 (this pass has no per-file read cap): the files' text goes to the device slab by slab and is parsed there
+        DeviceParsePlan devParse;
+        bool deviceParse = false;
+        if (const char *e = getenv("MDBG_TOOL_DEVICE_PARSE")) {
+            if (atoi(e) != 0) {
+                std::string why;
+                deviceParse = devParse.make(read_input_list(inputList), std::max<size_t>(1, a.batchBases), why);
+                if (deviceParse) g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size()) + " slab(s)").c_str());
+                else { devParse.unmap(); g_trace.mark(("device parse: falling back to the host feed: " + why).c_str()); }
+            }
+        }
+        if (!deviceParse) {
+            try { feeder.reset(new mdbg_host::ReadFeeder(read_input_list(inputList), a.batchBases, a.threads, 0, alloc, release, nConsumers)); }
+            catch (const std::exception &e) { die(e.what()); }
+        }
         std::mutex feedMu, statMu;
         uint64_t nextSeq = 0;
+        size_t nextSlab = 0;
         auto consume = [&](int ci) {
             mdbg_ctx *ctx = ctxs[(size_t)ci];
             double up = 0, sc = 0, dn = 0, qu = 0, wt = 0;
@@ -614,7 +676,36 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
             // minimizers in the other while the kernels run.  Packed chunks take this route, with or without qualities; chunks
             // delivered as ASCII (a character with bit 3 set) are uploaded synchronously as before.
             struct Staged { ReadBatch *b = nullptr; uint64_t seq = 0; mdbg_reads *reads = nullptr; bool live = false; };
+            void *textSlab = nullptr;             // device parse: this consumer's page-locked slab
+            auto stage_text = [&]() -> Staged {
+                Staged st;
+                size_t idx;
+                {
+                    std::lock_guard<std::mutex> g(feedMu);       // slabs are handed out in read order
+                    idx = nextSlab;
+                    if (idx < devParse.slabs.size()) { nextSlab++; st.seq = nextSeq++; }
+                }
+                if (idx >= devParse.slabs.size()) return st;
+                st.live = true;
+                const double t0 = g_trace.now();
+                const DeviceParsePlan::Slab &sl = devParse.slabs[idx];
+                if (!textSlab) check_on(ctx, mdbg_host_alloc(ctx, devParse.maxSlab + 64, &textSlab), "mdbg_host_alloc");
+                memcpy(textSlab, sl.p, sl.n);
+                if (st.seq == 0) g_trace.mark("first slab copied");
+                mdbg_bytes *text = nullptr;
+                check_on(ctx, mdbg_bytes_create(ctx, sl.n, &text), "mdbg_bytes_create");
+                check_on(ctx, mdbg_bytes_upload_async(ctx, text, 0, textSlab, sl.n, nullptr), "mdbg_bytes_upload_async");
+                // (the call returns when its kernels have run, so behind the upload: the slab is free for the next piece of text)
+                const int rc = mdbg_reads_from_fastx_bytes(ctx, text, 0, sl.n, &st.reads, nullptr);
+                mdbg_bytes_free(text);
+                if (rc != MDBG_OK)
+                    die(std::string("mdbg_reads_from_fastx_bytes (slab ") + std::to_string(idx) + " of the input, MDBG_TOOL_DEVICE_PARSE): " + mdbg_last_error(ctx) +
+                        " -- run without MDBG_TOOL_DEVICE_PARSE for the host feed");
+                up += g_trace.now() - t0;
+                return st;
+            };
             auto stage = [&]() -> Staged {
+                if (deviceParse) return stage_text();
                 Staged st;
                 const double tw = g_trace.now();
                 try {
@@ -704,6 +795,7 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                 const double t4 = g_trace.now();
                 sc += t2 - t1; dn += t3 - t2; qu += t4 - t3; nb++;
             }
+            if (textSlab) mdbg_host_free(ctx, textSlab);
             std::lock_guard<std::mutex> g(statMu);
             tWait += wt; tUpload += up; tScan += sc; tDownload += dn; tQueue += qu; nBatches += nb;
         };
@@ -713,6 +805,7 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         consume(0);
         for (auto &t : consumers) t.join();
         g_trace.mark("last batch scanned and handed to the writer");
+        devParse.unmap();                       // every slab has been copied and parsed
         // the feeder is taken apart behind the purge pass, not in front of it: un-pinning its 27 buffers and unmapping the input cost
         // 0.45 s of a 1.85 s run when it sat here (and as much under the process's exit when it was simply left to the system)
         std::thread([f = feeder.release()] { delete f; }).detach();
