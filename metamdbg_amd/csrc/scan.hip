@@ -755,8 +755,9 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
 //     positions of a block (about 10 of 2048) are materialised ONCE PER BLOCK, the lanes that own one recomputing its
 //     value from the ring -- instead of ballots, prefix counts and exec-masked stores after every 256 positions;
 //   * the minimizers of a read are staged in LDS and leave in coalesced rows;
-//   * the tail of a read (fewer than 2048 positions) runs the same code on spans of 4 G <= 32 positions per lane, the
-//     stream words fetched from the ring for every group of four.
+//   * the tail of a read (at most 2048 positions) runs the same arithmetic on spans of exactly ceil(npos / 64) <= 32
+//     positions per lane, two half spans side by side like the block, its stream words read once and the steps counted
+//     by a scalar loop.
 // ================================================================================================================
 constexpr int FAST_BLOCK = 256;                       // threads per workgroup (4 independent waves)
 constexpr int FAST_WAVES = FAST_BLOCK / 64;
@@ -1204,39 +1205,77 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             // be left with 2049 positions -- 36 per lane, four more than a lane's verdict vector holds)
             while (fill - done >= BLOCK_POS + K + a.trim) aligned_block(std::integral_constant<int, (int)SPAN>());
         }
-        // (a last half block of 1024 positions, 16 per lane, before the tail was measured: 11.73 against 11.76 ms -- the tail's
-        // positions cost about what a block's do; not kept)
+        // (a last half block of 1024 positions, 16 per lane, in front of the group-of-four, one-chain tail of rounds 2 - 6 was measured:
+        // 11.73 against 11.76 ms, not kept.  What that tail cost was its padding -- spans of 4 ceil(npos / 256) positions, 1536 hashed
+        // for the 1341 of a 10 kb HiFi read -- and its single chain; the exact-span, two-chain tail below hashes 1408 of them in 43
+        // vector instructions per position where it took 45: 66.08 -> 65.51 G wave instructions per launch of 10 M reads, busy cycles
+        // - 1.9 %, the scan in the bench 111.8 -> 110.0 ms and the step 112.9 -> 111.2 ms, three runs each, alternating
+        // (profiles/tail_two_chains_*) -- about half of the 3 % reasoned beforehand)
 
         // ---- tail: the positions left (each followed by a known base; with _trimBps == 0 also the last l-mer) ----
         {
             const uint32_t live = fill - done;
             uint32_t npos = live > K ? live - K : 0u;
             if (a.trim == 0u && live >= K) npos = live - K + 1u;
+            // (the same in every lane, but derived from loads the compiler takes for per-lane values: as a scalar, so that the walk
+            // below is counted and branched on by the scalar unit)
+            npos = (uint32_t)__builtin_amdgcn_readfirstlane((int)npos);
             if (npos) {
-                // groups of four positions per lane: at most 8, the verdicts of a lane are a 32-bit vector (the block loop above
-                // leaves at most 2048 positions whatever _trimBps is)
+                // spans of exactly P = ceil(npos / 64) <= 32 positions per lane (the block loop above leaves at most 2048 positions
+                // whatever _trimBps is; the verdicts of a lane are a 32-bit vector): lane l owns done + l P ... done + l P + P - 1, at
+                // most 63 positions are hashed for nothing.  A lane walks its span as two half spans of Ph = ceil(P / 2) positions side
+                // by side, as aligned_block does: chain a from the span's first position, chain b Ph positions on.
                 if (npos > BLOCK_POS) __builtin_trap();
-                const unsigned G = (npos + 255u) / 256u;
-                const unsigned P = 4u * G;
-                SpanState st{0u, 0u};
+                const unsigned P = (npos + 63u) >> 6;
+                const unsigned Ph = (P + 1u) >> 1;
+                // A chain needs 32 + 2 (Ph - 1) <= 62 stream bits from its first position on: three ring words, read once and aligned
+                // to the position (a per-lane shift); the walk then takes its window with the uniform shift 2 u and reads no LDS.
+                // The words may lie up to 48 bases past a chain's first position, i.e. below done + 63 P + Ph + 48 <= done + 2080:
+                // with the DEFER_BLOCKS blocks kept behind `done` that is 8224 of the ring's 16384 bases, so they never lap into kept
+                // bases; what they hold beyond `fill` is zero, and positions at or beyond npos are masked in emit whatever they hash to.
+                auto chain_words = [&](unsigned p, uint32_t &lo, uint32_t &hi) {
+                    const unsigned b = 2u * p, w = (b >> 5) & RING_WMASK, sh = b & 31u;
+                    const uint32_t w0 = S[w], w1 = S[(w + 1) & RING_WMASK], w2 = S[(w + 2) & RING_WMASK];
+                    lo = __builtin_amdgcn_alignbit(w1, w0, sh); hi = __builtin_amdgcn_alignbit(w2, w1, sh);
+                };
+                uint32_t bits = 0u;
                 auto tail_walk = [&](auto k15_tag) {
                     constexpr bool K15 = decltype(k15_tag)::value;
-                    uint32_t Tprev = 0u;               // a lane's positions are consecutive across its groups: the roll of l = 15 carries over
-                    for (unsigned g = 0; g < G; g++) {
-                        const unsigned p = done + lane * P + 4u * g;     // ring position of the group's first position
-                        const unsigned b = 2u * p, w = (b >> 5) & RING_WMASK, sh = b & 31u;
-                        const uint32_t w0 = S[w], w1 = S[(w + 1) & RING_WMASK], w2 = S[(w + 2) & RING_WMASK];
-                        const uint32_t a0 = __builtin_amdgcn_alignbit(w1, w0, sh), a1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const uint32_t T = u == 0 ? a0 : __builtin_amdgcn_alignbit(a1, a0, 2 * u);
-                            span_step<APPROX, K15>(st, T, g == 0 && u == 0, kmask, comp_mask, top_shift, K, threshold, cand_limit, Tprev);
-                            Tprev = T;
+                    uint32_t A0, A1, B0, B1;
+                    chain_words(done + lane * P, A0, A1);
+                    chain_words(done + lane * P + Ph, B0, B1);
+                    uint32_t Ta = A0, Tb = B0;
+                    uint32_t fa = digit_reverse(Ta & kmask, K), fb = digit_reverse(Tb & kmask, K);     // the first position of EACH chain
+                    uint32_t ba = 0u, bb = 0u;
+                    // one body for every P, counted by a scalar (an unrolled body per P would not fit the instruction cache); the roll
+                    // behind the last step is not used -- without a way out in the middle the loop stays one block with one scalar branch
+                    unsigned u = 0u;
+#pragma nounroll
+                    do {
+                        const uint32_t reva = (Ta ^ comp_mask) & kmask, revb = (Tb ^ comp_mask) & kmask;
+                        const uint32_t va = fa < reva ? fa : reva, vb = fb < revb ? fb : revb;
+                        if (APPROX) {
+                            uint32_t ra, rb;
+                            kmer_hash32_hi_merged_x2(va, vb, ra, rb);
+                            asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ra), "s"(cand_limit) : "vcc");
+                            asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bb) : "v"(rb), "s"(cand_limit) : "vcc");
+                        } else {
+                            const uint64_t ha = kmer_hash32(va), hb = kmer_hash32(vb);
+                            asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ha), "s"(threshold) : "vcc");
+                            asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bb) : "v"(hb), "s"(threshold) : "vcc");
                         }
-                    }
+                        u++;
+                        const uint32_t Na = __builtin_amdgcn_alignbit(A1, A0, 2u * u), Nb = __builtin_amdgcn_alignbit(B1, B0, 2u * u);
+                        if (K15) { fa = __builtin_amdgcn_alignbit(fa, Ta, 30) & kmask; fb = __builtin_amdgcn_alignbit(fb, Tb, 30) & kmask; }
+                        else { fa = ((fa << 2) | ((Na >> top_shift) & 3u)) & kmask; fb = ((fb << 2) | ((Nb >> top_shift) & 3u)) & kmask; }
+                        Ta = Na; Tb = Nb;
+                    } while (u < Ph);
+                    // the oldest position in bit P - 1.  With P odd chain b has hashed one position more than it owns (the next lane's
+                    // first: a guarded last step would need a second, one-chain copy of the hash): its youngest bit is dropped here
+                    bits = (ba << (P - Ph)) | (bb >> (2u * Ph - P));
                 };
                 if (K == 15u) tail_walk(std::true_type()); else tail_walk(std::false_type());
-                emit(st.bits, P, npos);
+                emit(bits, P, npos);
             }
             wave_lds_sync();
             materialise();
