@@ -714,6 +714,18 @@ def make_fn() -> None:
             out["scan_notrim_block"][f"K{K}_hpc{hpc}"] = dict(
                 K=K, density=dens, hpc=hpc, inputs=breads,
                 outputs=refdrv_lines(["fn_scan_notrim", str(K), str(dens), str(hpc)], breads))
+    # purgePalindrome on lists as long as real reads' (the crafted ones above stop at 60): lengths on both sides of the device
+    # kernel's 96-minimizer LDS row and up to 400, alphabets 2 .. 12, firstK 2 .. 5, a lastK at, near and far above firstK.  The
+    # inputs are stored once.  A file of its own, purge_long.json: fn_golden.json is 2.4 MB already and stays as it is (own
+    # generator, too)
+    rng5 = np.random.default_rng(20261018)
+    plens = (90, 96, 97, 98, 110, 130, 160, 200, 300, 400)
+    plists = [rng5.integers(0, a, n).tolist() for i, n in enumerate(plens) for a in ((2, 4, 8), (3, 6, 12), (2, 3, 12))[i % 3]]
+    plines = [" ".join(map(str, v)) for v in plists]
+    purge_long = dict(inputs=plines, outputs={f"{fk}_{lk}": refdrv_lines(["fn_purge", str(fk), str(lk)], plines)
+                                              for fk, lk in ((2, 100), (3, 4), (4, 100), (5, 100), (4, 12))})
+    with open(os.path.join(dst, "purge_long.json"), "w") as f:
+        json.dump(dict(purge_long=purge_long), f, indent=0, sort_keys=True)
     with open(os.path.join(dst, "fn_golden.json"), "w") as f:
         json.dump(out, f, indent=0, sort_keys=True)
 

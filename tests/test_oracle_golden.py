@@ -61,6 +61,25 @@ def test_purge_palindrome(fn_golden):
             assert got == [int(x) for x in out.split()], (key, line)
 
 
+def test_purge_palindrome_long_lists():
+    """Lists of 90 .. 400 minimizers, firstK 2 .. 5, lastK next to firstK and far above it (fn/purge_long.json, the reference's
+    own outputs): the oracle is what the device's purge is compared with at these lengths (tests/test_gpu_purge_palindromes.py)."""
+    with open(os.path.join(H.GOLDEN, "fn", "purge_long.json")) as f:
+        g = json.load(f)["purge_long"]
+    lists = [[int(x) for x in line.split()] for line in g["inputs"]]
+    assert len(lists) == 30 and min(map(len, lists)) == 90 and max(map(len, lists)) == 400
+    assert set(g["outputs"]) == {"2_100", "3_4", "4_100", "5_100", "4_12"}
+    dropped = 0
+    for key, outs in g["outputs"].items():
+        fk, lk = map(int, key.split("_"))
+        assert len(outs) == len(lists)
+        for lst, out in zip(lists, outs):
+            want = [int(x) for x in out.split()]
+            assert orc.purge_palindrome(lst, fk, lk).tolist() == want, (key, len(lst))
+            dropped += len(lst) - len(want)
+    assert dropped > 5000
+
+
 def test_last_k(fn_golden):
     for c in fn_golden["lastk"]:
         d, n50, fk, mk = c["args"]
