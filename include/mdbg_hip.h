@@ -384,6 +384,42 @@ int  mdbg_prev_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records, uint6
  * A read longer than 0xFFFFFFF0 bases is MDBG_ERANGE. */
 int  mdbg_reads_from_fastx_bytes(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, mdbg_reads **out, uint64_t info[4]);
 
+/* ---- BGZF blocks inflated on the device ------------------------------------------------------------------------------------------------
+ * Replaces gzread under the same kseq loop (KSEQ_INIT(gzFile, gzread), Commons.hpp:82; the read loop, Commons.hpp:5842-5870) for BGZF
+ * input -- what samtools fastq, bam2fastq and bgzip write: independent gzip members of at most 64 KB, each stating its compressed and
+ * its uncompressed size.  The caller reads the block table from the members' headers and trailers; the compressed bytes travel as they
+ * are (mdbg_bytes_*) and are inflated into an mdbg_bytes that mdbg_reads_from_fastx_bytes reads.
+ *
+ * mdbg_bgzf_block   src: offset in `comp` of the block's raw DEFLATE payload (behind the 12 + XLEN header bytes); csize: payload bytes;
+ *                   isize, crc: the member's trailer.  csize <= 65536 and isize <= 65536.
+ * mdbg_bytes_inflate_bgzf
+ *     Block i inflates to text[text_at + sum(isize[0..i)) ...); *n_text is the total.  Uploads still in flight on `comp` (and `text`)
+ *     are waited for on the device.  The call returns after the per-block status words have been read back: a later
+ *     mdbg_reads_from_fastx_bytes on `text` needs no extra synchronisation.  n_blocks == 0 and blocks with isize == 0 (the EOF marker)
+ *     are fine.
+ *     MDBG_EINVAL: a null argument; a block whose [src, src + csize) lies outside `comp`; csize > 65536; isize > 65536; a total that does not fit
+ *     `text` behind text_at (nothing has run then); or a block that does not decode -- the message names the first such block's index
+ *     and the reason: reserved block type / stored LEN/NLEN mismatch / over-subscribed or unusably incomplete code / invalid symbol /
+ *     distance beyond the block's own output / input exhausted / output not equal to isize / CRC-32 mismatch.  On error nothing is
+ *     promised about the bytes of `text` inside [text_at, text_at + total); bytes outside it are never written in any case.
+ *     Decoding: a raw DEFLATE stream (RFC 1951) per block, any number of stored, fixed and dynamic deflate blocks -- everything zlib's
+ *     deflate emits at every level and strategy.  A distance code with a single length-1 code, or with none, is accepted (as zlib and
+ *     host/inflate.hpp do); every other incomplete code is refused.  A BGZF block never refers to bytes before its own output: the
+ *     window is the block.  The CRC-32 (gzip polynomial, reflected) is computed on the device over the produced bytes.
+ * mdbg_bytes_download
+ *     a plain synchronous device-to-host copy of [at, at + n) of `b`; MDBG_EINVAL outside the buffer.
+ * mdbg_fastx_whole_records
+ *     where the last whole record of text[begin, end) ends when more text may follow `end`: text[begin] must start a record; *format is
+ *     0 for '>' and 1 for '@' (anything else, or an empty range: MDBG_EINVAL).  *cut is the largest offset in (begin, end] up to which
+ *     [begin, cut) is known to hold whole records.  FASTA: the offset of the last '>' that directly follows a '\n'; none behind begin:
+ *     begin.  FASTQ: the four-line rule of mdbg_reads_from_fastx_bytes -- with N the '\n' in the range, the offset just behind
+ *     newline number 4 * floor(N / 4); N < 4: begin. */
+typedef struct { uint64_t src; uint32_t csize, isize, crc, reserved; } mdbg_bgzf_block;
+int  mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, const mdbg_bgzf_block *blocks, uint64_t n_blocks,
+                             mdbg_bytes *text, uint64_t text_at, uint64_t *n_text);
+int  mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n);
+int  mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format);
+
 /* Page-locked host memory for read batches handed to mdbg_reads_from_ascii / _from_packed: uploads from it
  * run at PCIe rate instead of through the driver's staging copies.  Release with mdbg_host_free. */
 int  mdbg_host_alloc(mdbg_ctx *ctx, size_t bytes, void **out);

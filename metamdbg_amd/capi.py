@@ -123,7 +123,13 @@ SIGNATURES = {
     "mdbg_minimizers_from_record_bytes": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.POINTER(_P)]),
     "mdbg_prev_from_record_bytes": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "mdbg_reads_from_fastx_bytes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
+    "mdbg_bytes_inflate_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _u64p]),
+    "mdbg_bytes_download": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
+    "mdbg_fastx_whole_records": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _u64p, C.POINTER(C.c_int)]),
 }
+
+# mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
+BGZF_BLOCK = np.dtype([("src", "<u8"), ("csize", "<u4"), ("isize", "<u4"), ("crc", "<u4"), ("reserved", "<u4")])
 
 _lib = None
 
@@ -379,6 +385,29 @@ class Context:
         r.fastx_info = dict(format=int(info[0]), n_reads=int(info[1]), n_bases=int(info[2]), n_masked=int(info[3]))
         return r
 
+    # -- BGZF blocks inflated on the device ---------------------------------------------------------
+    def bytes_create(self, n: int) -> "DeviceBytes":
+        """An empty device buffer of n bytes (mdbg_bytes_create): the text a BGZF file inflates to."""
+        h = C.c_void_p()
+        self.check(lib().mdbg_bytes_create(self.h, n, C.byref(h)))
+        return DeviceBytes(self, h, n)
+
+    def inflate_bgzf(self, comp: "DeviceBytes", blocks, text: "DeviceBytes", text_at: int = 0) -> int:
+        """``blocks`` -- (src, csize, isize, crc) per BGZF block, as formats.bgzf_blocks gives them -- inflated from ``comp`` to
+        ``text[text_at ...)`` (mdbg_bytes_inflate_bgzf); returns the bytes of text."""
+        table = np.zeros(len(blocks), dtype=BGZF_BLOCK)
+        for i, (src, csize, isize, crc) in enumerate(blocks):
+            table[i] = (src, csize, isize, crc, 0)
+        n_text = C.c_uint64(0)
+        self.check(lib().mdbg_bytes_inflate_bgzf(self.h, comp.h, _ptr(table) if len(table) else None, len(table), text.h, text_at, C.byref(n_text)))
+        return int(n_text.value)
+
+    def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
+        """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
+        cut, fmt = C.c_uint64(0), C.c_int(0)
+        self.check(lib().mdbg_fastx_whole_records(self.h, text.h, begin, end, C.byref(cut), C.byref(fmt)))
+        return int(cut.value), int(fmt.value)
+
     def small_contigs(self, unitigs: "Minimizers", k: int, k_prev: int, prev: "Table") -> np.ndarray:
         """1 per unitig that IndexKminmerFunctor writes to smallContigs_k<k>.bin instead of indexing (k > 8 is the caller's test)."""
         n = unitigs.info()["n_reads"]
@@ -624,6 +653,12 @@ class Reads:
 class DeviceBytes:
     def __init__(self, ctx: "Context", h, n: int):
         self.ctx, self.h, self.n = ctx, h, n
+
+    def download(self, at: int, n: int) -> bytes:
+        """Bytes [at, at + n) of the buffer, copied back (mdbg_bytes_download)."""
+        out = np.zeros(n, dtype=np.uint8)
+        self.ctx.check(lib().mdbg_bytes_download(self.ctx.h, self.h, at, _ptr(out) if n else None, n))
+        return out.tobytes()
 
     def free(self) -> None:
         if self.h:

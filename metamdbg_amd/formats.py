@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import gzip
 import struct
+import zlib
 from dataclasses import dataclass
 
 import numpy as np
@@ -294,3 +295,56 @@ def fastx_records(data: bytes):
         else:
             seqs2.append(bytes(s[j] for j in keep)); quals.append(bytes(q[j] for j in keep))
     return 1, seqs2, quals
+
+
+# ---- BGZF (the blocked gzip of htslib: samtools fastq, bam2fastq, bgzip) ------------------------------------------------------------
+def bgzf_blocks(raw: bytes):
+    """The block table of a BGZF file: [(src, csize, isize, crc)] -- offset and size of every member's raw DEFLATE payload and its
+    trailer -- or None when ``raw`` is not a pure sequence of BGZF members.  The acceptance rule is BgzfReader::index's
+    (metamdbg_amd/host/hostfeed.hpp): FEXTRA and no other flag, a 'BC' subfield of two bytes giving the member's size, the member
+    inside the file, isize <= 65536, at least one member."""
+    out = []
+    o, n = 0, len(raw)
+    while o < n:
+        if n - o < 18 + 8:
+            return None
+        if raw[o] != 0x1F or raw[o + 1] != 0x8B or raw[o + 2] != 8 or raw[o + 3] != 4:
+            return None
+        xlen = raw[o + 10] | (raw[o + 11] << 8)
+        if n - o < 12 + xlen + 8:
+            return None
+        bsize = 0
+        x = 0
+        while x + 4 <= xlen:
+            sf = o + 12 + x
+            slen = raw[sf + 2] | (raw[sf + 3] << 8)
+            if raw[sf] == ord("B") and raw[sf + 1] == ord("C") and slen == 2 and x + 6 <= xlen:
+                bsize = (raw[sf + 4] | (raw[sf + 5] << 8)) + 1
+            x += 4 + slen
+        if bsize < 12 + xlen + 8 or bsize > n - o:
+            return None
+        crc, isize = struct.unpack_from("<II", raw, o + bsize - 8)
+        if isize > 65536:
+            return None
+        out.append((o + 12 + xlen, bsize - 12 - xlen - 8, isize, crc))
+        o += bsize
+    return out or None
+
+
+def bgzf_member(data: bytes, level: int = 6, strategy: int = 0) -> bytes:
+    """One BGZF member holding ``data`` (at most 65536 bytes whose member stays within 64 KB)."""
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+    payload = c.compress(data) + c.flush()
+    bsize = 18 + len(payload) + 8
+    if len(data) > 65536 or bsize > 65536:
+        raise ValueError(f"{len(data)} bytes make a member of {bsize}: more than a BGZF block holds")
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize - 1) + payload
+            + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
+
+
+def bgzf_compress(data: bytes, block: int = 0xFF00, level: int = 6, strategy: int = 0, eof_marker: bool = True) -> bytes:
+    """``data`` as a BGZF file: members of ``block`` text bytes each, then (eof_marker) htslib's empty last member."""
+    out = [bgzf_member(data[at:at + block], level, strategy) for at in range(0, len(data), block)]
+    if eof_marker:
+        out.append(bgzf_member(b""))
+    return b"".join(out)

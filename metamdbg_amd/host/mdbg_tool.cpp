@@ -304,23 +304,62 @@ mdbg_reads *upload_batch(mdbg_ctx *ctx, ReadBatch &b, bool withQual) {
 }
 
 // ---- MDBG_TOOL_DEVICE_PARSE=1: plain FASTA / FASTQ files travel as text and are taken apart on the device ------------------------
-// (mdbg_reads_from_fastx_bytes).  The symbol is looked up weakly: a library without it (the CPU tests' double) means the host feed.
+// (mdbg_reads_from_fastx_bytes); BGZF files travel compressed and are inflated there first (mdbg_bytes_inflate_bgzf).  The symbols are
+// looked up weakly: a library without them (the CPU tests' double) means the host feed.
 extern "C" int mdbg_reads_from_fastx_bytes(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, mdbg_reads **out, uint64_t info[4])
     __attribute__((weak));
+extern "C" int mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, const mdbg_bgzf_block *blocks, uint64_t n_blocks, mdbg_bytes *text, uint64_t text_at,
+                                       uint64_t *n_text) __attribute__((weak));
+extern "C" int mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n) __attribute__((weak));
+extern "C" int mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format) __attribute__((weak));
 
 struct DeviceParsePlan {
-    struct Slab { const char *p; size_t n; int file; };
+    // a BGZF file: its mapping, its block table (BgzfReader::index) and the text offset of every block
+    struct Bgzf {
+        std::string path;
+        const unsigned char *addr = nullptr;
+        std::vector<mdbg_host::BgzfReader::Block> blocks;
+        std::vector<uint64_t> cum;
+    };
+    struct Slab { const char *p; size_t n; int file; int bgzf; };        // bgzf >= 0: the whole of bgzfs[bgzf], cut into slabs as it is inflated
     std::vector<Slab> slabs;            // whole records each, in read order
+    std::vector<Bgzf> bgzfs;
     size_t maxSlab = 0;
     std::vector<std::pair<void *, size_t>> maps;
-    // true: every file of the list is plain text that begins with '>' or '@' (FASTQ: four lines a record), mapped and cut at record
-    // starts by the feeder's own search into slabs of at most batchBases bytes; false: `why` says what stands against it
+
+    // The first blocks of a BGZF file inflated on the host, until 256 records or 1 MB of text: what the plain files' checks look at.
+    // false: a block of the prefix does not inflate
+    static bool bgzf_prefix(const Bgzf &z, std::string &text) {
+        mdbg_host::Inflater inf;
+        std::vector<uint8_t> buf(65536 + 512);            // the decoder wants Inflater::MIN_ROOM bytes of room in front of every symbol
+        size_t lines = 0, headers = 0;
+        for (size_t b = 0; b < z.blocks.size() && text.size() < ((size_t)1 << 20) && headers <= 256 && lines < 4 * 256 + 4; b++) {
+            const auto &blk = z.blocks[b];
+            inf.reset(z.addr + blk.payload, z.addr + blk.payload + blk.csize);
+            size_t produced = 0;
+            if (inf.run(buf.data(), buf.data() + buf.size(), 0, &produced) != mdbg_host::Inflater::STREAM_END || produced != blk.isize) return false;
+            for (size_t i = 0; i < produced; i++) {
+                if (buf[i] == '\n') lines++;
+                if (buf[i] == '>' && (i ? buf[i - 1] == '\n' : text.empty() || text.back() == '\n')) headers++;
+            }
+            text.append((const char *)buf.data(), produced);
+        }
+        return true;
+    }
+
+    // true: every file of the list is plain text or pure BGZF that begins with '>' or '@' (FASTQ: four lines a record).  Plain files are
+    // mapped and cut at record starts by the feeder's own search into slabs of at most batchBases bytes; a BGZF file is one entry that
+    // the consumers cut as its text appears on the device.  false: `why` says what stands against it
     bool make(const std::vector<std::string> &files, size_t batchBases, std::string &why) {
         using mdbg_host::ReadFeeder;
         if (!mdbg_reads_from_fastx_bytes) { why = "the library has no mdbg_reads_from_fastx_bytes"; return false; }
         for (size_t f = 0; f < files.size(); f++) {
             const std::string &path = files[f];
-            if (ReadFeeder::file_is_gzip(path)) { why = path + " is compressed"; return false; }
+            const bool gz = ReadFeeder::file_is_gzip(path);
+            if (gz && (!mdbg_bytes_inflate_bgzf || !mdbg_bytes_download || !mdbg_fastx_whole_records)) {
+                why = path + " is compressed and the library has no mdbg_bytes_inflate_bgzf, mdbg_bytes_download or mdbg_fastx_whole_records";
+                return false;
+            }
             const int fd = open(path.c_str(), O_RDONLY);
             if (fd < 0) die("File not found: " + path);
             struct stat st;
@@ -331,6 +370,26 @@ struct DeviceParsePlan {
             if (addr == MAP_FAILED) die("mmap failed: " + path);
             madvise((void *)addr, (size_t)st.st_size, MADV_SEQUENTIAL);
             maps.emplace_back((void *)addr, (size_t)st.st_size);
+            if (gz) {
+                Bgzf z;
+                z.path = path;
+                z.addr = (const unsigned char *)addr;
+                if (!mdbg_host::BgzfReader::index(z.addr, (size_t)st.st_size, z.blocks)) { why = path + " is gzip but not BGZF"; return false; }
+                z.cum.assign(z.blocks.size() + 1, 0);
+                for (size_t i = 0; i < z.blocks.size(); i++) z.cum[i + 1] = z.cum[i] + z.blocks[i].isize;
+                if (z.cum.back() == 0) continue;                        // nothing but empty blocks: no reads
+                std::string head;
+                if (!bgzf_prefix(z, head)) { why = path + " has a BGZF block among its first that does not inflate"; return false; }
+                const bool fastq = head[0] == '@';
+                if (!fastq && head[0] != '>') { why = path + " does not begin with '>' or '@'"; return false; }
+                if (fastq && !ReadFeeder::fastq_is_four_line(head.data(), head.data() + head.size())) {
+                    why = path + " is not four-line FASTQ, which the device parse refuses";
+                    return false;
+                }
+                slabs.push_back(Slab{nullptr, 0, (int)f, (int)bgzfs.size()});
+                bgzfs.push_back(std::move(z));
+                continue;
+            }
             const char *end = addr + st.st_size;
             const bool fastq = *addr == '@';
             if (!fastq && *addr != '>') { why = path + " does not begin with '>' or '@'"; return false; }
@@ -341,7 +400,7 @@ struct DeviceParsePlan {
                     q = ReadFeeder::cut_at_record_start(p, p + batchBases, end, fastq);
                     if (q == p) die("a single read is larger than the batch size; raise --batch-bases");
                 }
-                slabs.push_back(Slab{p, (size_t)(q - p), (int)f});
+                slabs.push_back(Slab{p, (size_t)(q - p), (int)f, -1});
                 maxSlab = std::max(maxSlab, (size_t)(q - p));
                 p = q;
             }
@@ -656,7 +715,11 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
             if (atoi(e) != 0) {
                 std::string why;
                 deviceParse = devParse.make(read_input_list(inputList), std::max<size_t>(1, a.batchBases), why);
-                if (deviceParse) g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size()) + " slab(s)").c_str());
+                if (deviceParse && devParse.bgzfs.empty())
+                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size()) + " slab(s)").c_str());
+                else if (deviceParse)
+                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size() - devParse.bgzfs.size()) +
+                                  " slab(s) of plain text and " + std::to_string(devParse.bgzfs.size()) + " BGZF file(s) cut into slabs as they are inflated there").c_str());
                 else { devParse.unmap(); g_trace.mark(("device parse: falling back to the host feed: " + why).c_str()); }
             }
         }
@@ -667,6 +730,11 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         std::mutex feedMu, statMu;
         uint64_t nextSeq = 0;
         size_t nextSlab = 0;
+        // where the BGZF file at slabs[nextSlab] stands (under feedMu): its next slab begins `bgzfBegin` bytes into the text of block `bgzfBlock`
+        size_t bgzfBlock = 0;
+        uint64_t bgzfBegin = 0;
+        uint64_t bgzfSlabs = 0, bgzfInflated = 0, bgzfBlocks = 0;
+        const size_t batchText = std::max<size_t>(1, a.batchBases);
         auto consume = [&](int ci) {
             mdbg_ctx *ctx = ctxs[(size_t)ci];
             double up = 0, sc = 0, dn = 0, qu = 0, wt = 0;
@@ -677,30 +745,112 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
             // delivered as ASCII (a character with bit 3 set) are uploaded synchronously as before.
             struct Staged { ReadBatch *b = nullptr; uint64_t seq = 0; mdbg_reads *reads = nullptr; bool live = false; };
             void *textSlab = nullptr;             // device parse: this consumer's page-locked slab
+            auto parse_failed = [&](uint64_t seq) {
+                die(std::string("mdbg_reads_from_fastx_bytes (slab ") + std::to_string(seq) + " of the input, MDBG_TOOL_DEVICE_PARSE): " + mdbg_last_error(ctx) +
+                    " -- run without MDBG_TOOL_DEVICE_PARSE for the host feed");
+            };
+            // The next slab of the BGZF file `z` (feedMu held: where a slab ends is known only when its text is on the device, and the next
+            // begins there).  A slab is a run of blocks of at most batchText bytes of text, and one block more when it begins inside its first
+            // block; its compressed bytes go up from the mapping and are inflated to offset 0 of *text.  All but the file's last slab end
+            // behind their last whole record (mdbg_fastx_whole_records); the next slab begins with the block that holds that place, inflated a
+            // second time.  Returns false when the file has no text left; otherwise [*begin, *end) of *text is to be parsed.
+            // A block that does not inflate ends the run with the library's message: the reads in front of it are already on their way.
+            auto next_bgzf_slab = [&](const DeviceParsePlan::Bgzf &z, mdbg_bytes **text, uint64_t *begin, uint64_t *end) -> bool {
+                const size_t nb = z.blocks.size();
+                while (bgzfBlock < nb && z.blocks[bgzfBlock].isize == 0 && bgzfBegin == 0) bgzfBlock++;
+                if (bgzfBlock >= nb) return false;
+                const size_t b0 = bgzfBlock;
+                size_t b1 = b0;
+                uint64_t sum = 0;
+                while (b1 < nb && (b1 == b0 || sum + z.blocks[b1].isize <= batchText)) sum += z.blocks[b1++].isize;
+                if (bgzfBegin && b1 < nb) sum += z.blocks[b1++].isize;           // a cut is pending: the first block is mostly the last slab's
+                std::vector<mdbg_bgzf_block> table;
+                for (;;) {
+                    const uint64_t base = z.blocks[b0].payload, top = z.blocks[b1 - 1].payload + z.blocks[b1 - 1].csize;
+                    table.resize(b1 - b0);
+                    for (size_t i = b0; i < b1; i++) table[i - b0] = mdbg_bgzf_block{z.blocks[i].payload - base, z.blocks[i].csize, z.blocks[i].isize, z.blocks[i].crc, 0};
+                    mdbg_bytes *comp = nullptr;
+                    check_on(ctx, mdbg_bytes_create(ctx, top - base, &comp), "mdbg_bytes_create");
+                    check_on(ctx, mdbg_bytes_create(ctx, std::max<uint64_t>(1, sum), text), "mdbg_bytes_create");
+                    check_on(ctx, mdbg_bytes_upload_async(ctx, comp, 0, z.addr + base, top - base, nullptr), "mdbg_bytes_upload_async");
+                    uint64_t n_text = 0;
+                    const int rc = mdbg_bytes_inflate_bgzf(ctx, comp, table.data(), table.size(), *text, 0, &n_text);
+                    mdbg_bytes_free(comp);
+                    if (rc != MDBG_OK)
+                        die(z.path + ": " + mdbg_last_error(ctx) + " (the table of this call begins with block " + std::to_string(b0) + " of the file, MDBG_TOOL_DEVICE_PARSE)");
+                    bgzfInflated += b1 - b0;
+                    *begin = bgzfBegin;
+                    *end = n_text;
+                    if (b1 == nb) {                                              // the file's last slab is parsed whole
+                        bgzfBlock = nb;
+                        bgzfBegin = 0;
+                        if (*begin >= n_text) { mdbg_bytes_free(*text); *text = nullptr; return false; }
+                        return true;
+                    }
+                    uint64_t cut = *begin;
+                    int format = 0;
+                    if (*begin < n_text) check_on(ctx, mdbg_fastx_whole_records(ctx, *text, *begin, n_text, &cut, &format), "mdbg_fastx_whole_records");
+                    if (cut > *begin) {
+                        *end = cut;
+                        const uint64_t at = z.cum[b0] + cut;                     // in the file's text
+                        if (at == z.cum[b1]) { bgzfBlock = b1; bgzfBegin = 0; }
+                        else {
+                            bgzfBlock = (size_t)(std::upper_bound(z.cum.begin(), z.cum.end(), at) - z.cum.begin()) - 1;
+                            bgzfBegin = at - z.cum[bgzfBlock];
+                        }
+                        return true;
+                    }
+                    // not one whole record yet: more blocks, up to a batch of them
+                    mdbg_bytes_free(*text);
+                    *text = nullptr;
+                    if (sum > batchText) die("a single read is larger than the batch size; raise --batch-bases");
+                    const uint64_t upto = std::max<uint64_t>(2 * sum, 65536);
+                    do sum += z.blocks[b1++].isize; while (b1 < nb && sum < upto && sum + z.blocks[b1].isize <= batchText);
+                }
+            };
             auto stage_text = [&]() -> Staged {
                 Staged st;
                 size_t idx;
+                mdbg_bytes *text = nullptr;
+                uint64_t begin = 0, end = 0;
                 {
                     std::lock_guard<std::mutex> g(feedMu);       // slabs are handed out in read order
-                    idx = nextSlab;
-                    if (idx < devParse.slabs.size()) { nextSlab++; st.seq = nextSeq++; }
+                    for (;;) {
+                        idx = nextSlab;
+                        if (idx >= devParse.slabs.size()) return st;
+                        const int zi = devParse.slabs[idx].bgzf;
+                        if (zi < 0) { nextSlab++; break; }
+                        const double t0 = g_trace.now();
+                        const bool got = next_bgzf_slab(devParse.bgzfs[(size_t)zi], &text, &begin, &end);
+                        up += g_trace.now() - t0;
+                        if (got) { bgzfSlabs++; break; }
+                        bgzfBlocks += devParse.bgzfs[(size_t)zi].blocks.size();
+                        nextSlab++;                              // this file is done
+                        bgzfBlock = 0;
+                        bgzfBegin = 0;
+                    }
+                    st.seq = nextSeq++;
                 }
-                if (idx >= devParse.slabs.size()) return st;
                 st.live = true;
                 const double t0 = g_trace.now();
+                if (text) {                                      // a slab of a BGZF file, inflated above
+                    if (st.seq == 0) g_trace.mark("first slab inflated");
+                    const int rc = mdbg_reads_from_fastx_bytes(ctx, text, begin, end, &st.reads, nullptr);
+                    mdbg_bytes_free(text);
+                    if (rc != MDBG_OK) parse_failed(st.seq);
+                    up += g_trace.now() - t0;
+                    return st;
+                }
                 const DeviceParsePlan::Slab &sl = devParse.slabs[idx];
                 if (!textSlab) check_on(ctx, mdbg_host_alloc(ctx, devParse.maxSlab + 64, &textSlab), "mdbg_host_alloc");
                 memcpy(textSlab, sl.p, sl.n);
                 if (st.seq == 0) g_trace.mark("first slab copied");
-                mdbg_bytes *text = nullptr;
                 check_on(ctx, mdbg_bytes_create(ctx, sl.n, &text), "mdbg_bytes_create");
                 check_on(ctx, mdbg_bytes_upload_async(ctx, text, 0, textSlab, sl.n, nullptr), "mdbg_bytes_upload_async");
                 // (the call returns when its kernels have run, so behind the upload: the slab is free for the next piece of text)
                 const int rc = mdbg_reads_from_fastx_bytes(ctx, text, 0, sl.n, &st.reads, nullptr);
                 mdbg_bytes_free(text);
-                if (rc != MDBG_OK)
-                    die(std::string("mdbg_reads_from_fastx_bytes (slab ") + std::to_string(idx) + " of the input, MDBG_TOOL_DEVICE_PARSE): " + mdbg_last_error(ctx) +
-                        " -- run without MDBG_TOOL_DEVICE_PARSE for the host feed");
+                if (rc != MDBG_OK) parse_failed(st.seq);
                 up += g_trace.now() - t0;
                 return st;
             };
@@ -806,6 +956,10 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         for (auto &t : consumers) t.join();
         g_trace.mark("last batch scanned and handed to the writer");
         devParse.unmap();                       // every slab has been copied and parsed
+        if (!devParse.bgzfs.empty() && getenv("MDBG_TRACE"))
+            fprintf(stderr, "[mdbg_tool] device parse: %llu BGZF block(s) of %zu file(s) inflated on the device in %llu slab(s) (%llu block inflations: a slab's first block may "
+                            "be the one its predecessor ended in)\n", (unsigned long long)bgzfBlocks, devParse.bgzfs.size(), (unsigned long long)bgzfSlabs,
+                    (unsigned long long)bgzfInflated);
         // the feeder is taken apart behind the purge pass, not in front of it: un-pinning its 27 buffers and unmapping the input cost
         // 0.45 s of a 1.85 s run when it sat here (and as much under the process's exit when it was simply left to the system)
         std::thread([f = feeder.release()] { delete f; }).detach();
