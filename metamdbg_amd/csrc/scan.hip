@@ -25,6 +25,7 @@
 // the ORIGINAL coordinates [rle[pos], rle[pos+K]) its per-minimizer minimum quality spans
 // (ReadSelection.hpp:1047-1142) -- the quality bytes themselves are read by the gather kernel.
 #include "common.hpp"
+#include "complexity_dev.hpp"
 #include "murmur.hpp"
 #include "objects.hpp"
 
@@ -121,7 +122,7 @@ __device__ __forceinline__ uint64_t compress_pairs(uint64_t x, uint64_t d) {
 // start a run depends on those 10 bits only, so a 1024-entry table gives the squeezed bits (low byte)
 // and twice the number kept (high byte) in one LDS lookup per 4 bases.
 constexpr int HPC_LUT_SIZE = 1024;
-__device__ __forceinline__ uint16_t hpc_lut_entry(unsigned idx) {
+constexpr uint16_t hpc_lut_entry(unsigned idx) {
     unsigned prev = idx & 3u, out = 0, n = 0;
     for (int i = 0; i < 4; i++) {
         unsigned b = (idx >> (2 + 2 * i)) & 3u;
@@ -129,6 +130,31 @@ __device__ __forceinline__ uint16_t hpc_lut_entry(unsigned idx) {
         prev = b;
     }
     return (uint16_t)(out | (n << 8));
+}
+static_assert(hpc_lut_entry(0x000u) == 0x0000u, "AAAA after A: nothing kept");
+static_assert(hpc_lut_entry(0x001u) == 0x0200u, "AAAA after C: the first A");
+static_assert(hpc_lut_entry(0x390u) == 0x0639u, "ACTG (codes 0 1 2 3) after A: the A is dropped, C T G are kept");
+static_assert(hpc_lut_entry(0x391u) == 0x08E4u, "ACTG after C: all four kept");
+static_assert(hpc_lut_entry(0x3FFu) == 0x0000u, "GGGG after G: nothing kept");
+
+// The two byte tables a block works from (compress_pairs_lut), built by the compiler from the one rule above and copied to LDS
+// 16 bytes a thread when a block starts (the blocks used to evaluate the rule themselves: 4 entries and 8 byte stores a thread,
+// once per 8 reads)
+struct alignas(16) HpcLutImage {
+    uint8_t bits[HPC_LUT_SIZE], twice_kept[HPC_LUT_SIZE];
+};
+constexpr HpcLutImage make_hpc_lut_image() {
+    HpcLutImage t{};
+    for (unsigned i = 0; i < (unsigned)HPC_LUT_SIZE; i++) { const uint16_t e = hpc_lut_entry(i); t.bits[i] = (uint8_t)e; t.twice_kept[i] = (uint8_t)(e >> 8); }
+    return t;
+}
+static __device__ const HpcLutImage hpc_lut_image = make_hpc_lut_image();
+static_assert(sizeof(HpcLutImage) == 2 * HPC_LUT_SIZE && sizeof(HpcLutImage) % 16 == 0, "copied as uint4");
+
+// all of a block's threads: the image into a block's LDS copy (`lut`, 16-byte aligned); the caller synchronises
+__device__ __forceinline__ void hpc_lut_to_lds(uint8_t *lut, unsigned tid, unsigned n_threads) {
+    for (unsigned i = tid; i < sizeof(HpcLutImage) / 16u; i += n_threads)
+        reinterpret_cast<uint4 *>(lut)[i] = reinterpret_cast<const uint4 *>(&hpc_lut_image)[i];
 }
 
 // x squeezed to its run starts given the base `pl` preceding the word; *nbits = 2 * kept
@@ -253,58 +279,17 @@ __device__ __forceinline__ uint32_t window_sq_sum(uint64_t x0, uint64_t x1, uint
     return sum;
 }
 
-// sum over the 16 2-mers of (count among the 32 positions of word x)^2; nb = first base of the next word
-__device__ __forceinline__ uint32_t word_pair_sq_sum(uint64_t x, uint32_t nb) {
-    uint64_t eq[4], sh[4];
-    base_eq_masks(x, eq);
-#pragma unroll
-    for (int c = 0; c < 4; c++) sh[c] = (eq[c] >> 2) | ((uint64_t)(nb == (uint32_t)c) << 62);   // base(i+1) == c
-    uint32_t sum = 0;
-#pragma unroll
-    for (int c0 = 0; c0 < 4; c0++) {
-#pragma unroll
-        for (int c1 = 0; c1 < 4; c1++) {
-            uint32_t c = (uint32_t)__popcll(eq[c0] & sh[c1]);
-            sum += c * c;
-        }
-    }
-    return sum;
-}
-
-// The same sum on 32-bit bit planes.  The two halves of the word are interleaved so that every mask is one register:
-// base i < 16 sits at bit 2i, base 16 + i at bit 2i + 1 ("slot" order); L / H = low / high bit of the 2-bit code.  The
-// successor of a slot is the slot two bits up, except slot 30 (base 15 -> base 16 = slot 1) and slot 31 (base 31 -> the first
-// base of the next word).  Built from the instructions that issue at the fast rate on gfx950 (and / or / xor / add / right
-// shift / v_bitop3, tools/ubench/op_rates.hip) plus two rotates; then 16 x (and, popcount, multiply-add).
-__device__ __forceinline__ uint32_t word_pair_sq_sum32(uint64_t x, uint32_t next_lo32) {
-    const uint32_t M = 0x55555555u;
-    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
-    const uint32_t th = xh & M;
-    const uint32_t L = (xl & M) | (th + th);                       // low code bits in slot order
-    const uint32_t H = ((xl >> 1) & M) | (xh & ~M);                // high code bits in slot order
-    // successor planes: slot s <- slot s + 2; slot 30 <- slot 1; slot 31 <- base 0 of the next word
-    const uint32_t nl = __builtin_amdgcn_alignbit(next_lo32, next_lo32, 1);      // bit 31 = low code bit of the next word's base 0
-    const uint32_t nh = __builtin_amdgcn_alignbit(next_lo32, next_lo32, 2);      // bit 31 = its high code bit
-    const uint32_t NL = (L >> 2) | (__builtin_amdgcn_alignbit(L, L, 3) & 0x40000000u) | (nl & 0x80000000u);
-    const uint32_t NH = (H >> 2) | (__builtin_amdgcn_alignbit(H, H, 3) & 0x40000000u) | (nh & 0x80000000u);
-    const uint32_t e[4] = {~(L | H), L & ~H, H & ~L, L & H};       // base == A, C, T, G (codes 0..3)
-    const uint32_t n[4] = {~(NL | NH), NL & ~NH, NH & ~NL, NL & NH};
-    uint32_t sum = 0;
-#pragma unroll
-    for (int c0 = 0; c0 < 4; c0++) {
-#pragma unroll
-        for (int c1 = 0; c1 < 4; c1++) {
-            const uint32_t c = (uint32_t)__popc(e[c0] & n[c1]);
-            sum = __umul24(c, c) + sum;
-        }
-    }
-    return sum;
-}
-
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
+}
+
+// sum of a 32-bit value over the wave, as a scalar; the caller sees to it that the sum fits 32 bits.  The ladder of
+// wave_inclusive_sum_dpp and one v_readlane: 7 vector instructions and no LDS crossbar where six rounds of 64-bit
+// __shfl_xor took 12 ds_bpermute, their addresses and 12 adds with carry.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_sum_dpp(v), 63);
 }
 
 // Exact complexity decision for one read (second pass, rare): returns 1 when the reference's
@@ -479,9 +464,10 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
     __shared__ uint32_t lds_stream[SCAN_WAVES][STREAM_WORDS];
     __shared__ uint32_t lds_istream[HAS_N ? SCAN_WAVES : 1][HAS_N ? ISTREAM_WORDS : 1];
     __shared__ QualMap lds_qmap[(HAS_QUAL && HPC) ? SCAN_WAVES : 1];
-    __shared__ uint8_t lds_lut_b[(HPC && !HAS_N) ? HPC_LUT_SIZE : 1], lds_lut_n[(HPC && !HAS_N) ? HPC_LUT_SIZE : 1];
+    __shared__ alignas(16) uint8_t lds_lut[(HPC && !HAS_N) ? 2 * HPC_LUT_SIZE : 16];
+    const uint8_t *lds_lut_b = lds_lut, *lds_lut_n = lds_lut + ((HPC && !HAS_N) ? HPC_LUT_SIZE : 0);
     if (HPC && !HAS_N) {
-        for (unsigned i = threadIdx.x; i < HPC_LUT_SIZE; i += SCAN_BLOCK) { const uint16_t e = hpc_lut_entry(i); lds_lut_b[i] = (uint8_t)e; lds_lut_n[i] = (uint8_t)(e >> 8); }
+        hpc_lut_to_lds(lds_lut, threadIdx.x, SCAN_BLOCK);
         __syncthreads();
     }
     const unsigned lane = threadIdx.x & 63u;
@@ -538,7 +524,8 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
             // ---- complexity: upper bound from per-word 2-mer counts --------------------------------
             // window w = words w, w+1 (64 positions).  With a_v / b_v the 2-mer counts of the two words,
             // sum_v (a_v + b_v)^2 <= 2 (Q_w + Q_{w+1}),  Q = sum_v count^2, and 3-mer collisions <= 2-mer
-            // collisions, so  S_w <= Q_w + Q_{w+1} - 32.  Each word's Q enters at most two windows.
+            // collisions, so  S_w <= Q_w + Q_{w+1} - 32.  Each word's Q enters at most two windows.  (Q here is sq(w) of
+            // complexity_dev.hpp, which computes it as 64 + Q'/4 and moves the constants into the one compare per read.)
             // Lane l evaluates the word BEFORE its own (lane 0: the last word of the previous tile): the base
             // after that word is the lane's own first base, so nothing here waits for the prefetched tile.
 #if defined(SCAN_ABLATE) && SCAN_ABLATE == 3
@@ -551,9 +538,8 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
                 prev_word = __shfl(x, 63, 64);
                 if (wi >= 1u && (uint64_t)wi * 32u + 1u <= L) {          // word wi-1 is full and has a successor base
                     const uint32_t wq = wi - 1u;
-                    const uint32_t nW = L >= 66u ? (L - 66u) / 32u + 1u : 0u;
-                    uint32_t mult = (wq < nW ? 1u : 0u) + ((wq >= 1u && wq - 1u < nW) ? 1u : 0u);
-                    if (mult) cx_bound += (uint64_t)mult * word_pair_sq_sum(xp, (uint32_t)x & 3u);
+                    const uint32_t mult = complexity_word_weight(wq, complexity_windows(L));
+                    if (mult) cx_bound += (uint64_t)mult * word_pair_q(xp, (uint32_t)x);
                 }
             }
 
@@ -727,11 +713,10 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
         // ---- per-read epilogue -----------------------------------------------------------------
         uint8_t flags = 0;
         if (a.apply_filters && L >= 66) {
-            uint32_t nW = (L - 66u) / 32u + 1u;
-            uint64_t bound = wave_sum_u64(cx_bound);    // sum_w (Q_w + Q_{w+1}); subtract 32 per window
-            // (bound - 32 nW)/(61 nW) >= true mean score; only reads whose bound exceeds ~4.9 need the exact
+            // sum_w (sq_w + sq_{w+1}) - 32 nW over 61 nW >= true mean score; only reads whose bound exceeds ~4.9 need the exact
             // pass, which runs as its own (rare) kernel so its registers do not cap this kernel's occupancy
-            if (bound > (300ull + 32ull) * nW) flags |= READ_SUSPECT;
+            // (sum of sq > 332 nW, taken on the +-1 form: complexity_dev.hpp)
+            if (complexity_suspect(wave_sum_u64(cx_bound), complexity_windows(L))) flags |= READ_SUSPECT;
         }
         if (lane == 0) {
             a.out_count[r] = nout;
@@ -820,18 +805,20 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
     __shared__ uint8_t lds_stage_q[QUAL ? FAST_WAVES : 1][QUAL ? STAGE_CAP : 1];
     __shared__ uint16_t lds_hist_o[(QUAL && HPC) ? FAST_WAVES * HIST_TILES * 64 : 1];
     __shared__ uint32_t lds_hist_c[(QUAL && HPC) ? FAST_WAVES : 1][(QUAL && HPC) ? HIST_TILES : 1];
-    __shared__ uint32_t lds_ring[FAST_WAVES][RING_WORDS];
+    __shared__ alignas(16) uint32_t lds_ring[FAST_WAVES][RING_WORDS];
     __shared__ uint2 lds_stage[FAST_WAVES][STAGE_CAP];
-    __shared__ uint8_t lds_lut_b[HPC ? HPC_LUT_SIZE : 1], lds_lut_n[HPC ? HPC_LUT_SIZE : 1];
+    __shared__ alignas(16) uint8_t lds_lut[HPC ? 2 * HPC_LUT_SIZE : 16];
+    const uint8_t *lds_lut_b = lds_lut, *lds_lut_n = lds_lut + (HPC ? HPC_LUT_SIZE : 0);
     // the repetitive minimizers (ONT: a hundred or so values, sorted, in global memory) behind a filter of REP_FILTER_BITS bits: a
     // candidate whose bit is clear is not among them, and only the others pay the binary search -- eight dependent loads that a
     // lane of every block used to wait for (9 % of the ONT scan: profiles/round6_p_scan_ablation_ont_before_the_repetitive_filter_in_lds.txt, round6_q_* after)
-    __shared__ uint32_t lds_rep_filter[REP_FILTER_BITS / 32];
-    if (HPC) {
-        for (unsigned i = threadIdx.x; i < HPC_LUT_SIZE; i += FAST_BLOCK) { const uint16_t e = hpc_lut_entry(i); lds_lut_b[i] = (uint8_t)e; lds_lut_n[i] = (uint8_t)(e >> 8); }
-    }
-    for (unsigned i = threadIdx.x; i < FAST_WAVES * RING_WORDS; i += FAST_BLOCK) (&lds_ring[0][0])[i] = 0;
-    for (unsigned i = threadIdx.x; i < REP_FILTER_BITS / 32; i += FAST_BLOCK) lds_rep_filter[i] = 0;
+    __shared__ alignas(16) uint32_t lds_rep_filter[REP_FILTER_BITS / 32];
+    // block set-up, once per 8 reads: everything in 16-byte LDS stores (the table image: one load and one store for half the threads)
+    if (HPC) hpc_lut_to_lds(lds_lut, threadIdx.x, FAST_BLOCK);
+    static_assert((FAST_WAVES * RING_WORDS) % (4 * FAST_BLOCK) == 0 && (REP_FILTER_BITS / 32) % 4 == 0, "cleared as uint4");
+#pragma unroll
+    for (unsigned i = 0; i < FAST_WAVES * RING_WORDS / 4u; i += FAST_BLOCK) reinterpret_cast<uint4 *>(&lds_ring[0][0])[i + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    if (threadIdx.x < REP_FILTER_BITS / 128u) reinterpret_cast<uint4 *>(lds_rep_filter)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
     for (unsigned i = threadIdx.x; i < a.n_rep; i += FAST_BLOCK) {
         const uint32_t b = rep_filter_bit(a.rep[i]);
@@ -951,9 +938,16 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
         uint32_t n_mat = 0;        // ... of which materialised (rows [n_mat, nout) of the stage hold a position only)
         uint32_t zero_from = 0;    // ring position from which bases are still kept (<= done): the oldest block with listed positions
         uint32_t prev_last = 0;
-        uint64_t cx_acc = 0;       // per lane: sum of weight x Q over its words
+        // complexity bound: sum of weight x Q over the read's words (complexity_dev.hpp).  Q <= CX_Q_MAX = 3840 and the weights of a
+        // read sum to 2 nW <= L / 16, so below 2^24 bases the whole sum is under 240 * 2^24 < 2^32: a lane adds its words up in 32
+        // bits and the wave sum is taken once per read, in 32 bits.  A longer read (wave-uniform test on L) folds the lanes' sums
+        // into a scalar 64-bit total after every tile instead (a tile adds at most 64 x 2 x 3840).
+        static_assert((uint64_t)CX_Q_MAX * ((1ull << 24) / 16u) < (1ull << 32), "the 32-bit sum of a read below 2^24 bases");
+        uint32_t cx_acc = 0;       // per lane
+        uint64_t cx_total = 0;     // wave-uniform: what the tiles of a long read have folded so far
+        const bool cx_long = L >= (1u << 24);
         uint64_t prev_word = 0;
-        const uint32_t cx_nW = L >= 66u ? (L - 66u) / 32u + 1u : 0u;      // number of complexity windows (ReadSelection.hpp:1171-1228)
+        const uint32_t cx_nW = complexity_windows(L);      // number of complexity windows (ReadSelection.hpp:1171-1228)
 
         // ---- materialisation of the listed positions, one per lane: window, canonical form, direction and, with qualities, the
         // look-ups behind min_quality.  Deferred over up to DEFER_BLOCKS blocks (a block lists about ten positions: materialised
@@ -1150,10 +1144,15 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                 const uint32_t pl32 = lane_below(xl, (uint32_t)prev_word), ph32 = lane_below(xh, (uint32_t)(prev_word >> 32));
                 prev_word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)xh, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)xl, 63);
                 // word wq = wi - 1 enters window wq (if wq < nW) and window wq - 1 (if 1 <= wq <= nW): weight 1 at wq = 0 and nW, 2 between
-                const uint32_t q = word_pair_sq_sum32(((uint64_t)ph32 << 32) | pl32, xl);
-                const uint32_t wq = wi - 1u;                      // lane 0 of tile 0: wraps around, weight 0
-                const uint32_t w2 = wq < cx_nW ? q : 0u, w1 = (wq - 1u) < cx_nW ? q : 0u;
-                cx_acc += w2 + w1;
+                const uint32_t q = word_pair_q(((uint64_t)ph32 << 32) | pl32, xl);
+                if (t != 0u && t * TILE_WORDS + (TILE_WORDS - 1u) <= cx_nW) {
+                    cx_acc += q + q;                              // a tile in the middle of the read (wave-uniform test): words 1 .. nW - 1 only
+                } else {
+                    const uint32_t wq = wi - 1u;                  // lane 0 of tile 0: wraps around, weight 0
+                    const uint32_t w2 = wq < cx_nW ? q : 0u, w1 = (wq - 1u) < cx_nW ? q : 0u;
+                    cx_acc += w2 + w1;
+                }
+                if (cx_long) { cx_total += wave_sum_u32(cx_acc); cx_acc = 0; }
             }
 
             // ---- run starts / compaction of this lane's word ----
@@ -1297,8 +1296,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                                                                                         // the general kernel redoes the read
         uint8_t flags = 0;
         if (a.apply_filters && L >= 66) {
-            const uint64_t bound = wave_sum_u64(cx_acc);
-            if (bound > (300ull + 32ull) * cx_nW) flags |= READ_SUSPECT;
+            if (complexity_suspect(cx_total + wave_sum_u32(cx_acc), cx_nW)) flags |= READ_SUSPECT;
         }
         // ---- the staged minimizers leave in rows ----
         if (bump) {
