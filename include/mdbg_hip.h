@@ -75,6 +75,10 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *                           hash and confirms each with the full hash; a read with a false candidate is re-run.  False
  *                           candidates occur about once in 2^31 positions; this widens the test (units of 2^32 of the
  *                           hash range) so that the re-run path can be exercised.  Default 0; results never depend on it
+ *   "scan_guard_slack"      tests only: the block-structured scan hashes a position with the two finalisers' upper half shared, which
+ *                           is exact unless a guard word is below 68; a lane that saw one walks its span again with the exact test.
+ *                           This raises the 68 (clamped to [0, 2^32 - 69]; 2^31 sends practically every span down the exact walk) so
+ *                           that the slow path can be exercised.  Default 0; results never depend on it
  *   "index_tuning"          the passes above firstK over the one-slot tables (bits; default 19; negative: the default): 1 = a slot's key and
  *                           value fetched in one trip, 2 = the insert first looks at a window's home slot with plain loads (a key found
  *                           there is done without an atomic), 4 = two windows of a lane in flight (measured: no gain), 8 = look-up and

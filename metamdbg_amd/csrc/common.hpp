@@ -144,6 +144,7 @@ struct mdbg_ctx {
     int test_exchange_fail_phase = 0;       // tests: this rank fails in phase 1 (before the counts) / 2 (buffers) / 3 (reduction) of the next exchange
     bool test_corrupt_replies = false;      // tests: the next exchange hands back one reply with a wrong count (the job's self-check must see it)
     uint32_t scan_cand_slack = 0;           // tests: widens the candidate test of the block-structured scan (see span_step)
+    uint32_t scan_guard_slack = 0;          // tests: widens the guard test of its shared hash, up to every span redone exactly (scan.hip)
     // distinct keys per k-min-mer instance seen by the last call OF THE SAME KIND (table sizing): the first pass keeps every
     // key, refined / index only those above abundance 1 -- one shared hint made every first pass after an index pass rebuild its table
     double key_ratio_hint[4] = {0.0625, 0.0625, 0.0625, 0.0625};   // [0] first pass, [1] refined, [2] index, [3] sharded first pass

@@ -124,6 +124,69 @@ __host__ __device__ __forceinline__ void kmer_hash32_hi_merged_x2(uint32_t va, u
     rb = (uint32_t)(tb >> 32) + slb * 0xc4ceb9feu + shb * 0x1a85ec53u;
 }
 
+// The candidate test's value with the finalisers' UPPER HALF shared.  Both finalisers start from the key k = h:l after the c2
+// multiplication:  h1 = (k ^ 34) + 34,  h2 = h1 + 34.  With x = l ^ 34 (34 < 2^32: the xor leaves h alone) and, in 32 bits,
+// al = x + 34, bl = x + 68:  if neither addition carries out of the lower half -- exactly when bl >= 68, since x + 68 not
+// wrapping means x + 34 did not either -- then
+//     hi(h1) = hi(h2) = h,   lo(h1) = al,   lo(h2) = bl,
+// so the two 64-bit additions are two 32-bit ones, the finalisers' first  k ^= k >> 33  shares one h >> 1, and the term
+// h * 0xed558ccd that enters the upper half of either finaliser's first multiplication (mul64_halves) is one product for both.
+// From there on the statements are kmer_hash32_hi_merged's.  The ONE precondition: the guard word bl (before the xor with
+// h >> 1) is >= 68; the function hands it back and the caller decides (68 of every 2^32 values of l fail it; of the 2^32 keys
+// v, 65 do -- tests/host/test_murmur_shared_hi.cpp lists them).  Where it holds the result is kmer_hash32_hi_merged(v) bit for bit.
+__host__ __device__ __forceinline__ uint32_t kmer_hash32_hi_shared(uint32_t v, uint32_t &guard) {
+    const uint64_t p = (uint64_t)v * 0x114253d5u;
+    uint32_t l = (uint32_t)p, h = (uint32_t)(p >> 32) + v * 0x87c37b91u;
+    const uint32_t rl = (l << 31) | (h >> 1), rh = (h << 31) | (l >> 1);
+    l = rl; h = rh;
+    mul64_halves(l, h, 0x2745937fu, 0x4cf5ad43u);
+    const uint32_t x = l ^ 34u;
+    uint32_t al = x + 34u, bl = x + 68u;
+    guard = bl;
+    const uint32_t hs = h >> 1, hc = h * 0xed558ccdu;                    // shared by both finalisers
+    al ^= hs; bl ^= hs;
+    const uint64_t pa = (uint64_t)al * 0xed558ccdu, pb = (uint64_t)bl * 0xed558ccdu;
+    const uint32_t ah = (uint32_t)(pa >> 32) + al * 0xff51afd7u + hc, bh = (uint32_t)(pb >> 32) + bl * 0xff51afd7u + hc;
+    al = (uint32_t)pa ^ (ah >> 1); bl = (uint32_t)pb ^ (bh >> 1);
+    const uint64_t s = (((uint64_t)ah << 32) | al) + (((uint64_t)bh << 32) | bl);
+    const uint32_t sl = (uint32_t)s, sh = (uint32_t)(s >> 32);
+    const uint64_t q = (uint64_t)sl * 0x1a85ec53u + (1ull << 32);
+    return (uint32_t)(q >> 32) + sl * 0xc4ceb9feu + sh * 0x1a85ec53u;
+}
+
+// Two of them side by side, statement by statement like kmer_hash32_hi_merged_x2.  GUARD: both guard words are folded into the
+// caller's running minimum g (one v_min3_u32), to be tested once after a whole span; without it g is left alone.
+template <bool GUARD>
+__host__ __device__ __forceinline__ void kmer_hash32_hi_shared_x2(uint32_t va, uint32_t vb, uint32_t &ra, uint32_t &rb, uint32_t &g) {
+    const uint64_t pa = (uint64_t)va * 0x114253d5u, pb = (uint64_t)vb * 0x114253d5u;
+    uint32_t la = (uint32_t)pa, lb = (uint32_t)pb;
+    uint32_t ha = (uint32_t)(pa >> 32) + va * 0x87c37b91u, hb = (uint32_t)(pb >> 32) + vb * 0x87c37b91u;
+    const uint32_t rla = (la << 31) | (ha >> 1), rlb = (lb << 31) | (hb >> 1);
+    const uint32_t rha = (ha << 31) | (la >> 1), rhb = (hb << 31) | (lb >> 1);
+    la = rla; lb = rlb; ha = rha; hb = rhb;
+    const uint64_t qa = (uint64_t)la * 0x2745937fu, qb = (uint64_t)lb * 0x2745937fu;
+    const uint32_t nha = (uint32_t)(qa >> 32) + la * 0x4cf5ad43u + ha * 0x2745937fu, nhb = (uint32_t)(qb >> 32) + lb * 0x4cf5ad43u + hb * 0x2745937fu;
+    const uint32_t xa = (uint32_t)qa ^ 34u, xb = (uint32_t)qb ^ 34u;
+    uint32_t ala = xa + 34u, alb = xb + 34u;
+    uint32_t bla = xa + 68u, blb = xb + 68u;
+    if (GUARD) { const uint32_t m = g < bla ? g : bla; g = m < blb ? m : blb; }       // min(min(g, bla), blb)
+    const uint32_t hsa = nha >> 1, hsb = nhb >> 1;
+    const uint32_t hca = nha * 0xed558ccdu, hcb = nhb * 0xed558ccdu;
+    ala ^= hsa; alb ^= hsb;
+    bla ^= hsa; blb ^= hsb;
+    const uint64_t paa = (uint64_t)ala * 0xed558ccdu, pab = (uint64_t)alb * 0xed558ccdu;
+    const uint32_t aha = (uint32_t)(paa >> 32) + ala * 0xff51afd7u + hca, ahb = (uint32_t)(pab >> 32) + alb * 0xff51afd7u + hcb;
+    ala = (uint32_t)paa ^ (aha >> 1); alb = (uint32_t)pab ^ (ahb >> 1);
+    const uint64_t pba = (uint64_t)bla * 0xed558ccdu, pbb = (uint64_t)blb * 0xed558ccdu;
+    const uint32_t bha = (uint32_t)(pba >> 32) + bla * 0xff51afd7u + hca, bhb = (uint32_t)(pbb >> 32) + blb * 0xff51afd7u + hcb;
+    bla = (uint32_t)pba ^ (bha >> 1); blb = (uint32_t)pbb ^ (bhb >> 1);
+    const uint64_t sa = (((uint64_t)aha << 32) | ala) + (((uint64_t)bha << 32) | bla), sb = (((uint64_t)ahb << 32) | alb) + (((uint64_t)bhb << 32) | blb);
+    const uint32_t sla = (uint32_t)sa, sha = (uint32_t)(sa >> 32), slb = (uint32_t)sb, shb = (uint32_t)(sb >> 32);
+    const uint64_t ta = (uint64_t)sla * 0x1a85ec53u + (1ull << 32), tb = (uint64_t)slb * 0x1a85ec53u + (1ull << 32);
+    ra = (uint32_t)(ta >> 32) + sla * 0xc4ceb9feu + sha * 0x1a85ec53u;
+    rb = (uint32_t)(tb >> 32) + slb * 0xc4ceb9feu + shb * 0x1a85ec53u;
+}
+
 // Streaming Murmur3 x64-128 over a sequence of u32 words (little-endian), seed 0.
 struct Murmur128Stream {
     uint64_t h1 = 0, h2 = 0;

@@ -92,6 +92,7 @@ struct ScanArgs {
     uint32_t *list_counters;      // [0] = reads in over_list, [1] = reads in suspect_list
     const uint8_t *skip;          // scan_fast_kernel: reads flagged here carry side-mask bits (N, mixed case) and are left to the general kernel
     uint32_t cand_slack;          // scan_fast_kernel<.., APPROX>: extra width of the candidate test (0 but in tests)
+    uint32_t guard_slack;         // scan_fast_kernel<.., APPROX>: extra width of the shared hash's guard test (0 but in tests)
     uint32_t wave_priority;       // scan_fast_kernel: s_setprio level of its waves (0 = leave alone)
 };
 
@@ -847,6 +848,19 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
     // (saturating: a threshold near 2^64 -- densities close to 1 -- must not wrap the limit around to "nothing is a candidate")
     const uint64_t cand_limit64 = (threshold >> 32) + 3ull + (uint64_t)a.cand_slack;
     const uint32_t cand_limit = cand_limit64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cand_limit64;
+    // APPROX: the position loops hash with the finalisers' upper half shared (kmer_hash32_hi_shared_x2, murmur.hpp), which is the
+    // candidate value exactly when the guard word is >= 68.  A lane keeps the minimum g of its span's guard words; a lane with
+    // g < guard_limit walks its span again with the exact candidate test (guarded_redo), so the candidates are the same set in
+    // every case.  guard_slack widens the test on purpose (tests of that slow path: any value is valid, the slow path is exact)
+    const uint64_t guard_limit64 = 68ull + (uint64_t)a.guard_slack;
+    const uint32_t guard_limit = guard_limit64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)guard_limit64;
+    // GUARD (compile-time, beside K15): under HPC with l = 15 no guard is needed.  Every hashed window of a compressed read, forward
+    // or reverse complement, has no two equal adjacent digits; of the 2^32 keys 65 fail the guard, 14 of them are below 2^30 and
+    // every one of those has an adjacent repeat -- proved by enumeration, tests/test_murmur_shared_hi_host.py.  (A window that
+    // reaches past `fill` holds zeros and may hash to anything: emit masks those positions whatever they hash to.)  So that
+    // instantiation carries no minimum, no ballot and no slow path; every other l, uncompressed reads and any guard_slack take
+    // the guarded one.
+    const bool unguarded = HPC && K == 15u && a.guard_slack == 0u;
 
     const uint32_t wave_global = blockIdx.x * FAST_WAVES + wv;
     const uint32_t n_waves = gridDim.x * FAST_WAVES;
@@ -1065,6 +1079,17 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             nout += total;
         };
 
+        // ---- the slow path of the shared hash (APPROX, guarded walks): this lane's span of P positions once more, position by
+        // position from the ring with the exact candidate test, the oldest position in the highest used bit as the walks leave it.
+        // Called by the lanes whose guard minimum is below guard_limit only -- about 3 blocks in 10^5 have one ----
+        auto guarded_redo = [&](unsigned P) -> uint32_t {
+            SpanState rs{0u, 0u};
+#pragma nounroll
+            for (unsigned u = 0; u < P; u++)
+                span_step<APPROX>(rs, ring_window(S, done + lane * P + u), u == 0u, kmask, comp_mask, top_shift, K, threshold, cand_limit);
+            return rs.bits;
+        };
+
         // ---- 64 * SP positions from `done` on, each followed by a known base: lane l owns positions SP l .. SP l + SP - 1, i.e.
         // 2 SP stream bits that start on a word boundary of the ring; walked in registers with compile-time shifts ----
         auto aligned_block = [&](auto sp_tag) {
@@ -1073,13 +1098,15 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             const unsigned wb = ((done >> 4) + WPL * lane) & RING_WMASK;
             const uint32_t W0 = S[wb], W1 = S[(wb + 1) & RING_WMASK], W2 = SP > 16 ? S[(wb + 2) & RING_WMASK] : 0u;
             SpanState st{0u, 0u};
-            auto walk = [&](auto k15_tag) {
+            auto walk = [&](auto k15_tag, auto guard_tag) {
                 constexpr bool K15 = decltype(k15_tag)::value;
+                constexpr bool GUARD = APPROX && decltype(guard_tag)::value;
                 if (SP == 32 && DUAL_CHAIN) {
                     // two independent chains per lane -- positions 0 .. 15 and 16 .. 31 side by side -- so that a wave has another
                     // instruction to issue while a multiply's result is on its way (at 4 - 5 waves per SIMD one chain leaves gaps:
                     // tools/ubench/hash_rates.hip, chains=1 against chains=2)
                     uint32_t fa = 0u, fb = 0u, ba = 0u, bb = 0u, pa = 0u, pb = 0u;
+                    uint32_t g = 0xFFFFFFFFu;      // GUARD: the minimum of the span's guard words
 #pragma unroll
                     for (int u = 0; u < 16; u++) {
                         const uint32_t Ta = u == 0 ? W0 : __builtin_amdgcn_alignbit(W1, W0, 2 * u);
@@ -1091,7 +1118,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                         const uint32_t va = fa < reva ? fa : reva, vb = fb < revb ? fb : revb;
                         if (APPROX) {
                             uint32_t ra, rb;
-                            kmer_hash32_hi_merged_x2(va, vb, ra, rb);
+                            kmer_hash32_hi_shared_x2<GUARD>(va, vb, ra, rb, g);
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ra), "s"(cand_limit) : "vcc");
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bb) : "v"(rb), "s"(cand_limit) : "vcc");
                         } else {
@@ -1102,6 +1129,9 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                         pa = Ta; pb = Tb;
                     }
                     st.bits = (ba << 16) | bb;
+                    if (GUARD && __ballot(g < guard_limit) != 0ull) {
+                        if (g < guard_limit) st.bits = guarded_redo(32u);
+                    }
                     return;
                 }
                 uint32_t Tprev = 0u;
@@ -1113,7 +1143,8 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     Tprev = T;
                 }
             };
-            if (K == 15u) walk(std::true_type()); else walk(std::false_type());
+            if (K == 15u) { if (APPROX && !unguarded) walk(std::true_type(), std::true_type()); else walk(std::true_type(), std::false_type()); }
+            else walk(std::false_type(), std::integral_constant<bool, APPROX>());
             emit(st.bits, (unsigned)SP, 64u * (unsigned)SP);
             wave_lds_sync();
             done += 64u * (unsigned)SP;
@@ -1238,14 +1269,17 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     lo = __builtin_amdgcn_alignbit(w1, w0, sh); hi = __builtin_amdgcn_alignbit(w2, w1, sh);
                 };
                 uint32_t bits = 0u;
-                auto tail_walk = [&](auto k15_tag) {
+                auto tail_walk = [&](auto k15_tag, auto guard_tag) {
                     constexpr bool K15 = decltype(k15_tag)::value;
+                    constexpr bool GUARD = APPROX && decltype(guard_tag)::value;
                     uint32_t A0, A1, B0, B1;
                     chain_words(done + lane * P, A0, A1);
                     chain_words(done + lane * P + Ph, B0, B1);
                     uint32_t Ta = A0, Tb = B0;
                     uint32_t fa = digit_reverse(Ta & kmask, K), fb = digit_reverse(Tb & kmask, K);     // the first position of EACH chain
                     uint32_t ba = 0u, bb = 0u;
+                    uint32_t g = 0xFFFFFFFFu;      // GUARD: the minimum of the guard words of both chains (with P odd also of the one
+                                                   // position chain b hashes beyond its own: at worst a span redone for nothing)
                     // one body for every P, counted by a scalar (an unrolled body per P would not fit the instruction cache); the roll
                     // behind the last step is not used -- without a way out in the middle the loop stays one block with one scalar branch
                     unsigned u = 0u;
@@ -1255,7 +1289,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                         const uint32_t va = fa < reva ? fa : reva, vb = fb < revb ? fb : revb;
                         if (APPROX) {
                             uint32_t ra, rb;
-                            kmer_hash32_hi_merged_x2(va, vb, ra, rb);
+                            kmer_hash32_hi_shared_x2<GUARD>(va, vb, ra, rb, g);
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ra), "s"(cand_limit) : "vcc");
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(bb) : "v"(rb), "s"(cand_limit) : "vcc");
                         } else {
@@ -1272,8 +1306,12 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     // the oldest position in bit P - 1.  With P odd chain b has hashed one position more than it owns (the next lane's
                     // first: a guarded last step would need a second, one-chain copy of the hash): its youngest bit is dropped here
                     bits = (ba << (P - Ph)) | (bb >> (2u * Ph - P));
+                    if (GUARD && __ballot(g < guard_limit) != 0ull) {
+                        if (g < guard_limit) bits = guarded_redo(P);
+                    }
                 };
-                if (K == 15u) tail_walk(std::true_type()); else tail_walk(std::false_type());
+                if (K == 15u) { if (APPROX && !unguarded) tail_walk(std::true_type(), std::true_type()); else tail_walk(std::true_type(), std::false_type()); }
+                else tail_walk(std::false_type(), std::integral_constant<bool, APPROX>());
                 emit(bits, P, npos);
             }
             wave_lds_sync();
@@ -1823,6 +1861,7 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
         a.cursor = d_ctl.p; a.n_regions = n_regions; a.out_capacity = region_cap; a.out_begin = m->d_begin.p;
         a.over_list = d_over.p; a.suspect_list = d_susp.p; a.list_counters = (uint32_t *)(d_ctl.p + CTL_OVER);
         a.cand_slack = ctx->scan_cand_slack;
+        a.guard_slack = ctx->scan_guard_slack;
         a.wave_priority = ctx->scan_wave_priority;
         a.skip = route_masked ? reads->d_masked.p : nullptr;
         unsigned long long h_ctl[CTL_WORDS];

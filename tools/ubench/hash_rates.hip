@@ -56,9 +56,29 @@ __global__ __launch_bounds__(256) void k(uint32_t *out, uint32_t seed, int iters
     uint32_t v[CHAINS];
     for (int c = 0; c < CHAINS; c++) v[c] = seed * (c + 1) + threadIdx.x * 977u + blockIdx.x;
     uint32_t acc = 0;
+    uint32_t g = 0xFFFFFFFFu;      // V == 6: the running minimum of the guard words
     for (int i = 0; i < iters; i++) {
+        if ((V == 5 || V == 6) && CHAINS == 2) {
+            // the finalisers' upper half shared (kmer_hash32_hi_shared_x2), as the position loops call it: without (5) and with
+            // (6) the v_min3_u32 that folds both guard words into the running minimum
+            uint32_t ra, rb;
+            kmer_hash32_hi_shared_x2<V == 6>(v[0], v[CHAINS - 1], ra, rb, g);
+            acc += (ra < (uint32_t)(92233718306963448ull >> 32) + 3u) ? 1u : 0u;
+            acc += (rb < (uint32_t)(92233718306963448ull >> 32) + 3u) ? 1u : 0u;
+            v[0] = v[0] * 1664525u + 1013904223u + (ra >> 28);
+            v[CHAINS - 1] = v[CHAINS - 1] * 1664525u + 1013904223u + (rb >> 28);
+            continue;
+        }
 #pragma unroll
         for (int c = 0; c < CHAINS; c++) {
+            if (V == 5 || V == 6) {         // one chain: kmer_hash32_hi_shared, the guard word folded with one v_min_u32 (6) or dropped (5)
+                uint32_t gw;
+                const uint32_t s1 = kmer_hash32_hi_shared(v[c], gw);
+                if (V == 6) g = g < gw ? g : gw;
+                acc += (s1 < (uint32_t)(92233718306963448ull >> 32) + 3u) ? 1u : 0u;
+                v[c] = v[c] * 1664525u + 1013904223u + (s1 >> 28);
+                continue;
+            }
             if (V == 3) {         // the candidate test of scan_fast_kernel<.., APPROX>: upper half without the carry (murmur.hpp)
                 const uint32_t s1 = kmer_hash32_hi_nocarry(v[c]) + 1u;
                 acc += (s1 < (uint32_t)(92233718306963448ull >> 32) + 2u) ? 1u : 0u;
@@ -76,7 +96,7 @@ __global__ __launch_bounds__(256) void k(uint32_t *out, uint32_t seed, int iters
             v[c] = v[c] * 1664525u + 1013904223u + (uint32_t)(h >> 60);   // next input (cheap, dependent)
         }
     }
-    out[blockIdx.x * blockDim.x + threadIdx.x] = acc + v[0];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = acc + v[0] + (V == 6 ? (g < 68u ? 1u : 0u) : 0u);
 }
 
 template <int V, int CHAINS>
@@ -93,7 +113,7 @@ void run(const char *name, uint32_t *d, int waves) {
     (void)hipEventSynchronize(e1);
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
     double hashes_per_simd = (double)iters * CHAINS * waves;    // wave-level hashes (64 lanes each) per SIMD
-    printf("%-10s chains=%d waves/SIMD=%d  %.3f ms  %.1f ns per 64 hashes per SIMD (= %.0f cycles @2.36GHz)\n", name, CHAINS, waves, ms,
+    printf("%-14s chains=%d waves/SIMD=%d  %.3f ms  %.1f ns per 64 hashes per SIMD (= %.0f cycles @2.36GHz)\n", name, CHAINS, waves, ms,
            ms * 1e6 / hashes_per_simd, ms * 1e6 / hashes_per_simd * 2.36);
 }
 
@@ -106,6 +126,8 @@ int main() {
         run<2, 1>("mul_lo_hi", d, w); run<2, 2>("mul_lo_hi", d, w);
         run<3, 1>("hi_nocarry", d, w); run<3, 2>("hi_nocarry", d, w);
         run<4, 1>("hi_merged", d, w); run<4, 2>("hi_merged", d, w);
+        run<5, 1>("hi_shared", d, w); run<5, 2>("hi_shared", d, w);
+        run<6, 1>("hi_shared+min3", d, w); run<6, 2>("hi_shared+min3", d, w);
     }
     return 0;
 }
