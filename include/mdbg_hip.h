@@ -79,6 +79,19 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *                           is exact unless a guard word is below 68; a lane that saw one walks its span again with the exact test.
  *                           This raises the 68 (clamped to [0, 2^32 - 69]; 2^31 sends practically every span down the exact walk) so
  *                           that the slow path can be exercised.  Default 0; results never depend on it
+ *   "scan_prefilter"        1 (default; negative too) = the block-structured scan takes its pre-filtered variant where that applies:
+ *                           homopolymer compression, minimizer_size 15, no qualities, the two slacks above 0, a batch whose average
+ *                           read is expected to select fewer rows than that variant stages (176: 27 kb at density 0.005) and whose reads
+ *                           above that length hold at most 1/32 of its bases (the four-wave kernel scans those in the same call), a bitmap of
+ *                           the selected keys at most a quarter full (densities up to about 0.013) and room for one workgroup of 16 or
+ *                           8 waves beside "scan_lds_reserve".  The variant asks a 64 KB bitmap in LDS whether a position's key can be
+ *                           selected and hashes only the positions that pass; the bitmap is built on the device when the density
+ *                           changes and kept with the context.  0 = never (the four-wave kernels, as before).  The environment variable
+ *                           MDBG_SCAN_PREFILTER=0 / 1 sets the default of new contexts.  Results never depend on it; mdbg_scan_info
+ *                           tells which kernel ran
+ *   "scan_prefilter_log2_bits"  tests only: the bitmap is built and probed with 2^value bits (10 .. 19; 0 = the kernel's own 2^19) and
+ *                           used whatever its fill, so that nearly every position reaches the confirmation with the full hash and its
+ *                           list overflows.  Results never depend on it
  *   "index_tuning"          the passes above firstK over the one-slot tables (bits; default 19; negative: the default): 1 = a slot's key and
  *                           value fetched in one trip, 2 = the insert first looks at a window's home slot with plain loads (a key found
  *                           there is done without an atomic), 4 = two windows of a lane in flight (measured: no gain), 8 = look-up and
@@ -312,6 +325,11 @@ int  mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]);
  * the scan leave that much of every CU's LDS free; for tests "partition_bits", "partition_lds_slots" (256 / 1024 / 2048),
  * "partition_max_records" (instances per group).  mdbg_shard_begin counts a rank's share the same way. */
 int  mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]);
+/* Which block-structured scan kernels the context has launched (mdbg_scan; "scan_prefilter" above): info[0] = launches of the pre-filtered
+ * variant, [1] = launches of the four-wave block kernels, [2] = selected-key bitmaps built, [3] = bits set in the last one, [4] = log2 of
+ * its size in bits, [5] = waves per workgroup of the last pre-filtered launch (16, or 8 under a large "scan_lds_reserve"), [6] = 1 when
+ * the last block-kernel launch was the pre-filtered variant, [7] = 0.  No reference analogue: the reference hashes every position. */
+int  mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]);
 /* Order-independent sums over the rows, wrapping at 2^64, computed on the device (nothing but 32 bytes travels):
  *   sums[0] = sum abundance * hash_lo -- the "Checksum kminmer abundance" the reference logs when it loads the table again
  *             (CreateMdbg::loadRefinedAbundances, graph/CreateMdbg.cpp:3300-3321, :3397: `abundance * vecHash` truncated to u64),

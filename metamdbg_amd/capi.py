@@ -87,6 +87,7 @@ SIGNATURES = {
     "mdbg_table_checksum": (C.c_int, [_P, _P, _u64p]),
     "mdbg_table_stats": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_info": (C.c_int, [_P, _u64p]),
+    "mdbg_scan_info": (C.c_int, [_P, _u64p]),
     "mdbg_stream_spin": (C.c_int, [_P, C.c_uint32]),
     "mdbg_minimizers_slice": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mdbg_shard_exchange_local": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p)]),
@@ -200,6 +201,14 @@ class Context:
         a = (C.c_uint64 * 8)()
         self.check(lib().mdbg_first_pass_info(self.h, a))
         names = ("path", "groups", "bucket_bits", "levels", "attempts", "lds_slots", "buckets", "instances")
+        return {k: int(v) for k, v in zip(names, a)}
+
+    def scan_info(self) -> dict:
+        """Which block-structured scan kernels this context has launched (mdbg_scan_info)."""
+        a = (C.c_uint64 * 8)()
+        self.check(lib().mdbg_scan_info(self.h, a))
+        names = ("prefiltered_launches", "block_launches", "bitmaps_built", "bitmap_bits_set", "bitmap_log2_bits", "prefilter_waves",
+                 "last_prefiltered")
         return {k: int(v) for k, v in zip(names, a)}
 
     # -- timing ---------------------------------------------------------------------------

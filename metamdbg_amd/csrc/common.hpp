@@ -145,6 +145,17 @@ struct mdbg_ctx {
     bool test_corrupt_replies = false;      // tests: the next exchange hands back one reply with a wrong count (the job's self-check must see it)
     uint32_t scan_cand_slack = 0;           // tests: widens the candidate test of the block-structured scan (see span_step)
     uint32_t scan_guard_slack = 0;          // tests: widens the guard test of its shared hash, up to every span redone exactly (scan.hip)
+    // the block-structured scan's pre-filtered variant (scan.hip, prefilter.hpp): its selected-key bitmap, built when (threshold, geometry)
+    // change -- l = 15 and homopolymer compression are the variant's conditions -- and freed with the context
+    uint32_t scan_prefilter = 1;            // "scan_prefilter": 1 = taken where its conditions hold (default), 0 = never (mdbg_set_option, MDBG_SCAN_PREFILTER)
+    uint32_t scan_prefilter_log2_bits = 0;  // tests: a smaller bitmap (2^10 bits up) in which nearly every position passes; 0 = the kernel's own
+    uint32_t *prefilter_bits = nullptr;     // device: PREFILTER_BYTES of bitmap + the count of set bits
+    bool prefilter_valid = false;
+    uint64_t prefilter_threshold = 0;
+    uint32_t prefilter_log2 = 0, prefilter_set = 0;
+    uint64_t scan_info[8] = {0};            // mdbg_scan_info: [0] launches of the pre-filtered variant, [1] of the four-wave block kernels, [2] bitmaps built,
+                                            // [3] bits set in the last, [4] its log2 size, [5] waves a workgroup of the last pre-filtered launch, [6] 1 when
+                                            // the last block-kernel launch was pre-filtered
     // distinct keys per k-min-mer instance seen by the last call OF THE SAME KIND (table sizing): the first pass keeps every
     // key, refined / index only those above abundance 1 -- one shared hint made every first pass after an index pass rebuild its table
     double key_ratio_hint[4] = {0.0625, 0.0625, 0.0625, 0.0625};   // [0] first pass, [1] refined, [2] index, [3] sharded first pass

@@ -66,6 +66,7 @@ extern "C" int mdbg_create(int device, mdbg_ctx **out) try {
     if (const char *e = getenv("MDBG_SCAN_WAVE_PRIORITY")) ctx->scan_wave_priority = (uint32_t)std::max(0, std::min(3, atoi(e)));
     if (const char *e = getenv("MDBG_SCAN_READS_PER_WAVE")) if (atoi(e) > 0) ctx->scan_reads_per_wave = (unsigned)atoi(e);
     if (const char *e = getenv("MDBG_SCAN_LDS_RESERVE")) ctx->scan_lds_reserve = (uint32_t)std::max(0, std::min(131072, atoi(e)));
+    if (const char *e = getenv("MDBG_SCAN_PREFILTER")) ctx->scan_prefilter = atoi(e) != 0;
     if (const char *e = getenv("MDBG_SCAN_LDS_PAD")) ctx->scan_lds_pad = (uint32_t)std::max(0, std::min(32768, atoi(e)));
     if (const char *e = getenv("MDBG_PARTITION_TILE")) ctx->part_tile = atoi(e) == 2048 ? 2048u : 0u;
     if (const char *e = getenv("MDBG_PARTITION_SLOT_LIST")) ctx->part_slot_list = atoi(e) != 0;
@@ -99,6 +100,7 @@ extern "C" void mdbg_destroy(mdbg_ctx *ctx) {
     if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); (void)hipStreamDestroy(ctx->upload_stream); }
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->prefilter_bits) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->prefilter_bits); }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -183,6 +185,11 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
     if (n == "scan_wave_priority") { ctx->scan_wave_priority = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(3, value)); return MDBG_OK; }
     if (n == "scan_candidate_slack") { ctx->scan_cand_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 1 << 24) : 0u; return MDBG_OK; }
     if (n == "scan_guard_slack") { ctx->scan_guard_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll - 68) : 0u; return MDBG_OK; }
+    if (n == "scan_prefilter") { ctx->scan_prefilter = value != 0; return MDBG_OK; }
+    if (n == "scan_prefilter_log2_bits") {
+        if (value != 0 && (value < 10 || value > 19)) return set_error(ctx, MDBG_EINVAL, "scan_prefilter_log2_bits: 0 (the kernel's own) or 10 .. 19");
+        ctx->scan_prefilter_log2_bits = (uint32_t)value; return MDBG_OK;
+    }
     if (n == "scan_reads_per_wave") { ctx->scan_reads_per_wave = value > 0 ? (unsigned)std::min<int64_t>(value, 1 << 20) : 2u; return MDBG_OK; }
     if (n == "first_pass_mode") { ctx->first_pass_mode = (int)std::max<int64_t>(0, std::min<int64_t>(2, value)); return MDBG_OK; }
     if (n == "partition_auto_min") { ctx->part_auto_min = value > 0 ? (uint64_t)value : (1ull << 17); return MDBG_OK; }

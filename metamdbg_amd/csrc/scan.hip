@@ -28,6 +28,7 @@
 #include "complexity_dev.hpp"
 #include "murmur.hpp"
 #include "objects.hpp"
+#include "prefilter.hpp"
 
 #include <fcntl.h>
 #include <sys/file.h>
@@ -94,6 +95,12 @@ struct ScanArgs {
     uint32_t cand_slack;          // scan_fast_kernel<.., APPROX>: extra width of the candidate test (0 but in tests)
     uint32_t guard_slack;         // scan_fast_kernel<.., APPROX>: extra width of the shared hash's guard test (0 but in tests)
     uint32_t wave_priority;       // scan_fast_kernel: s_setprio level of its waves (0 = leave alone)
+    // scan_fast_kernel<.., PFW> (the pre-filtered variant): the selected-key bitmap (prefilter.hpp; PREFILTER_BYTES whatever its geometry)
+    const uint32_t *pf_bits;
+    uint32_t pf_shift;            // 32 - log2(bits of the bitmap): a key's bit is (v * 0x9E3779B1) >> pf_shift
+    uint32_t pf_chunk;            // reads a workgroup deals out to its waves
+    uint32_t pf_len_split;        // > 0: that variant passes over the reads of this many bases or more -- too long for its stage, they are
+                                  // the four-wave kernel's, launched in front of it with the other reads flagged in `skip` (launch_scan)
 };
 
 // squeeze the 2-bit fields of x whose flag bit (bit 2i of d) is set down to the low end
@@ -749,8 +756,6 @@ constexpr int FAST_BLOCK = 256;                       // threads per workgroup (
 constexpr int FAST_WAVES = FAST_BLOCK / 64;
 constexpr unsigned RING_BASES = 16384;                // per wave: DEFER_BLOCKS blocks awaiting materialisation + 2 * 2048 + 16 + 1 live bases
 constexpr unsigned DEFER_BLOCKS = 3;                  // blocks whose selected positions may wait in the list before they are materialised
-constexpr unsigned RING_WORDS = RING_BASES / 16;      // u32
-constexpr unsigned RING_WMASK = RING_WORDS - 1;
 constexpr unsigned SPAN = 32;                         // positions per lane in a full block
 constexpr unsigned BLOCK_POS = 64 * SPAN;             // 2048
 constexpr bool DUAL_CHAIN = true;                      // the unrolled block walks two half spans of a lane side by side (aligned_block)
@@ -789,9 +794,9 @@ __device__ __forceinline__ void span_step(SpanState &st, uint32_t T, bool first,
 }
 
 // the 32 stream bits that start at ring position p (any p), from LDS
-__device__ __forceinline__ uint32_t ring_window(const uint32_t *S, unsigned p) {
-    const unsigned b = 2u * p, w = (b >> 5) & RING_WMASK, sh = b & 31u;
-    return __builtin_amdgcn_alignbit(S[(w + 1) & RING_WMASK], S[w], sh);
+__device__ __forceinline__ uint32_t ring_window(const uint32_t *S, unsigned p, unsigned wmask) {
+    const unsigned b = 2u * p, w = (b >> 5) & wmask, sh = b & 31u;
+    return __builtin_amdgcn_alignbit(S[(w + 1) & wmask], S[w], sh);
 }
 
 // QUAL (reads with qualities): the minimum quality over every minimizer's ORIGINAL bases (getMinQuality,
@@ -801,27 +806,71 @@ __device__ __forceinline__ uint32_t ring_window(const uint32_t *S, unsigned p) {
 // of them: per tile every lane keeps its offset in the compressed stream (HIST_TILES tiles back, 2 bytes per word), a selected
 // lane finds the tile, then the word (binary search over the 64 offsets), re-reads that word and picks the k-th run start.
 constexpr int HIST_TILES = 8;
-template <bool HPC, bool QUAL, bool APPROX>
-__global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
-    __shared__ uint8_t lds_stage_q[QUAL ? FAST_WAVES : 1][QUAL ? STAGE_CAP : 1];
-    __shared__ uint16_t lds_hist_o[(QUAL && HPC) ? FAST_WAVES * HIST_TILES * 64 : 1];
-    __shared__ uint32_t lds_hist_c[(QUAL && HPC) ? FAST_WAVES : 1][(QUAL && HPC) ? HIST_TILES : 1];
-    __shared__ alignas(16) uint32_t lds_ring[FAST_WAVES][RING_WORDS];
-    __shared__ uint2 lds_stage[FAST_WAVES][STAGE_CAP];
+
+// PFW > 0: the PRE-FILTERED variant (HPC, l = 15, no qualities, APPROX, no slack: launch_scan).  Which canonical keys a compressed
+// read can produce and which of them are selected is fixed by (l, threshold): the walks probe a bitmap of the selected keys in LDS
+// (prefilter.hpp) instead of hashing -- one multiply, one shift, one ds_read_u8 and two field extracts a position where the candidate
+// hash takes 28 instructions -- and the positions that pass (8.65 % false positives + the selected ones, about 190 of a block's
+// 2048) are listed, hashed in full 64 at a time and only the survivors go on (confirm): behind it emit sees exact verdicts.
+// The bitmap exists once per CU: ONE workgroup of PFW = 16 (or 8) waves per CU copies its 64 KB at set-up.  What a wave owns shrinks
+// to make room beside it: a ring of 8192 bases (one block deferred instead of three), a stage of PF_STAGE_CAP rows, a list of
+// PF_LIST_CAP candidate positions and 64 words the confirmed verdicts come back through.  The waves of a workgroup take reads from a
+// counter in LDS over the workgroup's chunk of reads, so that a CU is not left to the slowest of 16 fixed shares.
+constexpr unsigned PF_RING_BASES = 8192;              // per wave: 1 deferred block + 2 * 2048 + 16 + 1 live bases = 6161
+constexpr unsigned PF_DEFER_BLOCKS = 1;
+constexpr int PF_STAGE_CAP = 176;
+constexpr unsigned PF_LIST_CAP = 224;                 // candidate positions confirmed per pass (a block has 187 +- 13; more take further passes)
+template <int PFW> struct FastGeometry {
+    static constexpr bool PF = PFW > 0;
+    static constexpr int WAVES = PF ? PFW : FAST_WAVES, BLOCK = 64 * WAVES, STAGE = PF ? PF_STAGE_CAP : STAGE_CAP;
+    static constexpr unsigned RING = PF ? PF_RING_BASES : RING_BASES, DEFER = PF ? PF_DEFER_BLOCKS : DEFER_BLOCKS;
+    static constexpr unsigned RING_WORDS = RING / 16, RING_WMASK = RING_WORDS - 1;      // u32 words of the ring
+    // LDS of a workgroup of the pre-filtered variant: bitmap, tables, per wave ring + stage + list + verdict words, the read counter
+    static constexpr size_t PF_LDS = PREFILTER_BYTES + 2 * HPC_LUT_SIZE + REP_FILTER_BITS / 8 + 16 +
+                                     (size_t)WAVES * (RING / 4 + STAGE * 8 + PF_LIST_CAP * 2 + 64 * 4);
+};
+static_assert(FastGeometry<16>::PF_LDS + 28672 <= 163840, "16 waves fit beside the 28 KB the benchmark's other batch asks for");
+
+template <bool HPC, bool QUAL, bool APPROX, int PFW = 0>
+__global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void scan_fast_kernel(ScanArgs a) {
+    using Geo = FastGeometry<PFW>;          // this instantiation's workgroup, ring and stage
+    constexpr bool PF = Geo::PF;
+    static_assert(!PF || (HPC && !QUAL && APPROX), "the bitmap holds the keys of compressed reads; its candidates are confirmed like APPROX ones");
+    static_assert(Geo::DEFER * BLOCK_POS + 2 * BLOCK_POS + 17 <= Geo::RING, "deferred blocks + live bases fit the ring");
+    __shared__ uint8_t lds_stage_q[QUAL ? Geo::WAVES : 1][QUAL ? Geo::STAGE : 1];
+    __shared__ uint16_t lds_hist_o[(QUAL && HPC) ? Geo::WAVES * HIST_TILES * 64 : 1];
+    __shared__ uint32_t lds_hist_c[(QUAL && HPC) ? Geo::WAVES : 1][(QUAL && HPC) ? HIST_TILES : 1];
+    __shared__ alignas(16) uint32_t lds_ring[Geo::WAVES][Geo::RING_WORDS];
+    __shared__ uint2 lds_stage[Geo::WAVES][Geo::STAGE];
     __shared__ alignas(16) uint8_t lds_lut[HPC ? 2 * HPC_LUT_SIZE : 16];
     const uint8_t *lds_lut_b = lds_lut, *lds_lut_n = lds_lut + (HPC ? HPC_LUT_SIZE : 0);
     // the repetitive minimizers (ONT: a hundred or so values, sorted, in global memory) behind a filter of REP_FILTER_BITS bits: a
     // candidate whose bit is clear is not among them, and only the others pay the binary search -- eight dependent loads that a
     // lane of every block used to wait for (9 % of the ONT scan: profiles/round6_p_scan_ablation_ont_before_the_repetitive_filter_in_lds.txt, round6_q_* after)
     __shared__ alignas(16) uint32_t lds_rep_filter[REP_FILTER_BITS / 32];
-    // block set-up, once per 8 reads: everything in 16-byte LDS stores (the table image: one load and one store for half the threads)
-    if (HPC) hpc_lut_to_lds(lds_lut, threadIdx.x, FAST_BLOCK);
-    static_assert((FAST_WAVES * RING_WORDS) % (4 * FAST_BLOCK) == 0 && (REP_FILTER_BITS / 32) % 4 == 0, "cleared as uint4");
+    // block set-up, once per workgroup (8 reads of the four-wave kernel, 32 of the 16-wave variant): everything in 16-byte LDS stores (the table image: one load and one store for half the threads)
+    if (HPC) hpc_lut_to_lds(lds_lut, threadIdx.x, Geo::BLOCK);
+    static_assert((Geo::WAVES * Geo::RING_WORDS) % (4 * Geo::BLOCK) == 0 && (REP_FILTER_BITS / 32) % 4 == 0, "cleared as uint4");
 #pragma unroll
-    for (unsigned i = 0; i < FAST_WAVES * RING_WORDS / 4u; i += FAST_BLOCK) reinterpret_cast<uint4 *>(&lds_ring[0][0])[i + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    for (unsigned i = 0; i < Geo::WAVES * Geo::RING_WORDS / 4u; i += Geo::BLOCK) reinterpret_cast<uint4 *>(&lds_ring[0][0])[i + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     if (threadIdx.x < REP_FILTER_BITS / 128u) reinterpret_cast<uint4 *>(lds_rep_filter)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    // PF: the bitmap from global memory (it stays in L2 between workgroups), the workgroup's read counter, the waves' lists
+    const uint8_t *pf_map = nullptr;
+    uint16_t *pf_list_all = nullptr;
+    uint32_t *pf_surv_all = nullptr, *pf_next = nullptr;
+    if constexpr (PF) {
+        __shared__ alignas(16) uint32_t lds_pf_map[PREFILTER_BYTES / 4];
+        __shared__ uint16_t lds_pf_list[Geo::WAVES][PF_LIST_CAP];
+        __shared__ uint32_t lds_pf_surv[Geo::WAVES][64];
+        __shared__ uint32_t lds_pf_next;
+        for (unsigned i = threadIdx.x; i < PREFILTER_BYTES / 16u; i += Geo::BLOCK)
+            reinterpret_cast<uint4 *>(lds_pf_map)[i] = reinterpret_cast<const uint4 *>(a.pf_bits)[i];
+        if (threadIdx.x == 0) lds_pf_next = 0u;
+        pf_map = reinterpret_cast<const uint8_t *>(lds_pf_map);
+        pf_list_all = &lds_pf_list[0][0]; pf_surv_all = &lds_pf_surv[0][0]; pf_next = &lds_pf_next;
+    }
     __syncthreads();
-    for (unsigned i = threadIdx.x; i < a.n_rep; i += FAST_BLOCK) {
+    for (unsigned i = threadIdx.x; i < a.n_rep; i += Geo::BLOCK) {
         const uint32_t b = rep_filter_bit(a.rep[i]);
         atomicOr(&lds_rep_filter[b >> 5], 1u << (b & 31u));
     }
@@ -862,9 +911,24 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
     // the guarded one.
     const bool unguarded = HPC && K == 15u && a.guard_slack == 0u;
 
-    const uint32_t wave_global = blockIdx.x * FAST_WAVES + wv;
-    const uint32_t n_waves = gridDim.x * FAST_WAVES;
-    for (uint32_t r = wave_global; r < a.n_reads; r += n_waves) {
+    const uint32_t wave_global = blockIdx.x * Geo::WAVES + wv;
+    const uint32_t n_waves = gridDim.x * Geo::WAVES;
+    // PF: this wave's list of candidate positions, the words their verdicts come back through, the bitmap's shift
+    uint16_t *pf_list = PF ? pf_list_all + wv * PF_LIST_CAP : nullptr;
+    uint32_t *pf_surv = PF ? pf_surv_all + wv * 64u : nullptr;
+    const uint32_t pf_shift = a.pf_shift;
+    // PF: the workgroup's chunk of reads [chunk0, chunk0 + chunk_n) is dealt out read by read; NO_READ when it is used up
+    constexpr uint32_t NO_READ = 0xFFFFFFFFu;               // no read has this index: n_reads is a 32-bit count
+    const uint64_t chunk0 = (uint64_t)blockIdx.x * a.pf_chunk;
+    const uint32_t chunk_n = PF ? (chunk0 >= a.n_reads ? 0u : (uint32_t)(a.n_reads - chunk0 < a.pf_chunk ? a.n_reads - chunk0 : a.pf_chunk)) : 0u;
+    auto take_read = [&]() -> uint32_t {
+        uint32_t k = 0;
+        if (lane == 0) k = atomicAdd(pf_next, 1u);
+        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        return k < chunk_n ? (uint32_t)chunk0 + k : NO_READ;
+    };
+    for (uint32_t r = PF ? take_read() : wave_global; PF ? r != NO_READ : r < a.n_reads; r = PF ? take_read() : r + n_waves) {
+        if constexpr (PF) { if (a.pf_len_split && a.len[r] >= a.pf_len_split) continue; }      // the four-wave launch's read
         if (a.skip && a.skip[r]) {          // a read with an N or a case flip: the host sends it through the general kernel
             if (a.cursor && lane == 0) { a.out_begin[r] = 0; a.out_count[r] = 0; a.out_flags[r] = 0; }
             continue;
@@ -964,7 +1028,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
         const uint32_t cx_nW = complexity_windows(L);      // number of complexity windows (ReadSelection.hpp:1171-1228)
 
         // ---- materialisation of the listed positions, one per lane: window, canonical form, direction and, with qualities, the
-        // look-ups behind min_quality.  Deferred over up to DEFER_BLOCKS blocks (a block lists about ten positions: materialised
+        // look-ups behind min_quality.  Deferred over up to Geo::DEFER blocks (a block lists about ten positions: materialised
         // there, five lanes in six idled through the longest dependent chain of the kernel) ----
         auto materialise = [&]() {
             const uint32_t pend = nout - n_mat;
@@ -973,7 +1037,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             const uint32_t base = n_mat - flushed;
             for (uint32_t i = lane; i < pend; i += 64) {
                 const uint32_t j = stage[base + i].y;
-                const uint32_t e = ring_window(S, j) & kmask;
+                const uint32_t e = ring_window(S, j, Geo::RING_WMASK) & kmask;
                 const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
                 // direction 1 iff the reverse complement is the canonical form, ties included (Kmer.hpp:427)
                 const uint32_t d = fw < rev ? 0u : 1u;
@@ -986,7 +1050,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
         // bases of [zero_from, upto) are not needed any more: back to zero for the next lap of the ring
         auto release_ring = [&](uint32_t upto) {
             const unsigned zb = zero_from >> 4, nz = (upto - zero_from) >> 4;
-            for (unsigned i = lane; i < nz; i += 64) S[(zb + i) & RING_WMASK] = 0;
+            for (unsigned i = lane; i < nz; i += 64) S[(zb + i) & Geo::RING_WMASK] = 0;
             zero_from = upto;
         };
 
@@ -1007,7 +1071,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     const unsigned bit = 31u - (unsigned)__clz((int)b2);
                     b2 &= ~(1u << bit);
                     const unsigned u = P - 1u - bit;
-                    const uint32_t e = ring_window(S, done + lane * P + u) & kmask;
+                    const uint32_t e = ring_window(S, done + lane * P + u, Geo::RING_WMASK) & kmask;
                     const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
                     const uint32_t v = fw < rev ? fw : rev, fb = rep_filter_bit(v);
                     if (((lds_rep_filter[fb >> 5] >> (fb & 31u)) & 1u) && rep_contains(a.rep, a.n_rep, v)) bits &= ~(1u << bit);
@@ -1018,14 +1082,14 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
             if (total == 0u) return;
             if (bump) {
-                if (outgrown || nout + total > (unsigned)STAGE_CAP) {
+                if (outgrown || nout + total > (unsigned)Geo::STAGE) {
                     if (!outgrown) { materialise(); n_staged_at_outgrowth = nout; }
                     if (APPROX) {          // the count the host places the read by must be exact: hash the candidates in full
                         uint32_t bad = 0;
                         while (bits) {
                             const unsigned bit = 31u - (unsigned)__clz((int)bits);
                             bits &= ~(1u << bit);
-                            const uint32_t e = ring_window(S, done + lane * P + (P - 1u - bit)) & kmask;
+                            const uint32_t e = ring_window(S, done + lane * P + (P - 1u - bit), Geo::RING_WMASK) & kmask;
                             const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
                             if (!(kmer_hash32(fw < rev ? fw : rev) < threshold)) bad++;
                         }
@@ -1033,7 +1097,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     }
                     outgrown = true; nout += total; return;
                 }
-            } else if (nout - flushed + total > (unsigned)STAGE_CAP) {       // make room: the staged rows leave for the output slot
+            } else if (nout - flushed + total > (unsigned)Geo::STAGE) {       // make room: the staged rows leave for the output slot
                 materialise();
                 const uint32_t ns = nout - flushed;
                 for (uint32_t i = lane; i < ns; i += 64) {
@@ -1047,7 +1111,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                 flushed = nout;
                 wave_lds_sync();
             }
-            if (total <= (unsigned)STAGE_CAP) {
+            if (total <= (unsigned)Geo::STAGE) {
                 // the selected positions are listed in the stage; materialise() takes them one per lane later
                 uint32_t at = nout - flushed + incl - cnt;
                 while (bits) {
@@ -1064,7 +1128,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     bits &= ~(1u << bit);
                     const unsigned u = P - 1u - bit;
                     const uint32_t j = done + lane * P + u;
-                    const uint32_t e = ring_window(S, j) & kmask;
+                    const uint32_t e = ring_window(S, j, Geo::RING_WMASK) & kmask;
                     const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
                     const uint32_t d = fw < rev ? 0u : 1u;
                     if (at < cap) {
@@ -1079,6 +1143,54 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             nout += total;
         };
 
+        // ---- PF: one probe of the bitmap for key v, the answer shifted into b ----
+        auto pf_probe = [&](uint32_t v, uint32_t &b) {
+            const uint32_t h = v * 0x9E3779B1u;                  // prefilter_index(v) = h >> pf_shift
+            const uint32_t byte = pf_map[h >> (pf_shift + 3u)];
+            b = (b << 1) | ((byte >> ((h >> pf_shift) & 7u)) & 1u);
+        };
+        // ---- PF: confirmation, between a walk and emit.  `bits` (span length P per lane, oldest position in bit P - 1) holds the
+        // positions whose probe passed; what comes back holds those whose full hash is below the threshold.  The set positions are
+        // listed in LDS in lane order (6 bits of lane, 5 of bit), the lanes take listed positions 64 at a time, rebuild the key from
+        // the ring and hash it, and a survivor is ORed into its owner's word.  The list holds PF_LIST_CAP positions: what a pass
+        // cannot list stays in `bits` for the next pass, so a block with any number of candidates is confirmed exactly ----
+        auto confirm = [&](uint32_t bits, unsigned P, uint32_t npos_limit) -> uint32_t {
+            // positions at or beyond npos_limit and the trimmed first position of the read are nobody's (emit masks them again)
+            if (P < 32u) bits &= (1u << P) - 1u;
+            {
+                const uint32_t first_j = lane * P;
+                if (first_j >= npos_limit) bits = 0;
+                else if (first_j + P > npos_limit) bits &= ~((1u << (first_j + P - npos_limit)) - 1u);
+                if (done == 0u && lane == 0u && a.trim) bits &= ~(1u << (P - 1u));
+            }
+            uint32_t kept = 0u;
+            for (;;) {
+                const unsigned cnt = (unsigned)__popc(bits);
+                const unsigned incl = wave_inclusive_sum_dpp(cnt);
+                const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+                if (total == 0u) break;
+                pf_surv[lane] = 0u;
+                unsigned at = incl - cnt;
+                while (bits && at < PF_LIST_CAP) {
+                    const unsigned bit = 31u - (unsigned)__clz((int)bits);
+                    bits &= ~(1u << bit);
+                    pf_list[at++] = (uint16_t)((lane << 5) | bit);
+                }
+                const unsigned n = total < PF_LIST_CAP ? total : PF_LIST_CAP;
+                wave_lds_sync();
+                for (unsigned i = lane; i < n; i += 64u) {
+                    const uint32_t q = pf_list[i], owner = q >> 5, bit = q & 31u;
+                    const uint32_t e = ring_window(S, done + owner * P + (P - 1u - bit), Geo::RING_WMASK) & kmask;
+                    const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
+                    if (kmer_hash32(fw < rev ? fw : rev) < threshold) atomicOr(&pf_surv[owner], 1u << bit);
+                }
+                wave_lds_sync();
+                kept |= pf_surv[lane];
+                wave_lds_sync();          // read before the next pass clears the words
+            }
+            return kept;
+        };
+
         // ---- the slow path of the shared hash (APPROX, guarded walks): this lane's span of P positions once more, position by
         // position from the ring with the exact candidate test, the oldest position in the highest used bit as the walks leave it.
         // Called by the lanes whose guard minimum is below guard_limit only -- about 3 blocks in 10^5 have one ----
@@ -1086,7 +1198,7 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
             SpanState rs{0u, 0u};
 #pragma nounroll
             for (unsigned u = 0; u < P; u++)
-                span_step<APPROX>(rs, ring_window(S, done + lane * P + u), u == 0u, kmask, comp_mask, top_shift, K, threshold, cand_limit);
+                span_step<APPROX>(rs, ring_window(S, done + lane * P + u, Geo::RING_WMASK), u == 0u, kmask, comp_mask, top_shift, K, threshold, cand_limit);
             return rs.bits;
         };
 
@@ -1095,8 +1207,8 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
         auto aligned_block = [&](auto sp_tag) {
             constexpr int SP = decltype(sp_tag)::value;              // 32 or 16
             constexpr unsigned WPL = (unsigned)SP / 16u;               // stream words per lane
-            const unsigned wb = ((done >> 4) + WPL * lane) & RING_WMASK;
-            const uint32_t W0 = S[wb], W1 = S[(wb + 1) & RING_WMASK], W2 = SP > 16 ? S[(wb + 2) & RING_WMASK] : 0u;
+            const unsigned wb = ((done >> 4) + WPL * lane) & Geo::RING_WMASK;
+            const uint32_t W0 = S[wb], W1 = S[(wb + 1) & Geo::RING_WMASK], W2 = SP > 16 ? S[(wb + 2) & Geo::RING_WMASK] : 0u;
             SpanState st{0u, 0u};
             auto walk = [&](auto k15_tag, auto guard_tag) {
                 constexpr bool K15 = decltype(k15_tag)::value;
@@ -1116,7 +1228,9 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                         else if (K15) { fa = __builtin_amdgcn_alignbit(fa, pa, 30) & kmask; fb = __builtin_amdgcn_alignbit(fb, pb, 30) & kmask; }
                         else { fa = ((fa << 2) | ((Ta >> top_shift) & 3u)) & kmask; fb = ((fb << 2) | ((Tb >> top_shift) & 3u)) & kmask; }
                         const uint32_t va = fa < reva ? fa : reva, vb = fb < revb ? fb : revb;
-                        if (APPROX) {
+                        if (PF) {
+                            pf_probe(va, ba); pf_probe(vb, bb);
+                        } else if (APPROX) {
                             uint32_t ra, rb;
                             kmer_hash32_hi_shared_x2<GUARD>(va, vb, ra, rb, g);
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ra), "s"(cand_limit) : "vcc");
@@ -1143,14 +1257,17 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     Tprev = T;
                 }
             };
-            if (K == 15u) { if (APPROX && !unguarded) walk(std::true_type(), std::true_type()); else walk(std::true_type(), std::false_type()); }
+            if constexpr (PF) {          // l = 15, compressed, no slack (launch_scan): the one walk, then the exact verdicts
+                walk(std::true_type(), std::false_type());
+                st.bits = confirm(st.bits, (unsigned)SP, 64u * (unsigned)SP);
+            } else if (K == 15u) { if (APPROX && !unguarded) walk(std::true_type(), std::true_type()); else walk(std::true_type(), std::false_type()); }
             else walk(std::false_type(), std::integral_constant<bool, APPROX>());
             emit(st.bits, (unsigned)SP, 64u * (unsigned)SP);
             wave_lds_sync();
             done += 64u * (unsigned)SP;
             // materialise when most of a wave's lanes have a position to take, or when the ring cannot keep the blocks any longer
             // (with qualities under HPC the run starts of a listed position must still be in the tile history: one block less)
-            constexpr unsigned defer = (QUAL && HPC) ? DEFER_BLOCKS - 1u : DEFER_BLOCKS;
+            constexpr unsigned defer = (QUAL && HPC) ? Geo::DEFER - 1u : Geo::DEFER;
             if (nout - n_mat >= 48u || nout == n_mat || done - zero_from > defer * BLOCK_POS) {
                 materialise();
                 release_ring(done);
@@ -1213,14 +1330,14 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
 
             // ---- append to the ring (the region ahead of `fill` is zero) ----
             if (c) {
-                const unsigned dst = 2u * ((fill + o) & (RING_BASES - 1u)), w = dst >> 5, sh = dst & 31u;
+                const unsigned dst = 2u * ((fill + o) & (Geo::RING - 1u)), w = dst >> 5, sh = dst & 31u;
                 const uint32_t yl = (uint32_t)y, yh = (uint32_t)(y >> 32);
                 const uint32_t p0 = yl << sh;
                 const uint32_t p1 = sh ? ((yl >> (32u - sh)) | (yh << sh)) : yh;
                 const uint32_t p2 = sh ? (yh >> (32u - sh)) : 0u;
                 atomicOr(&S[w], p0);
-                if (p1) atomicOr(&S[(w + 1) & RING_WMASK], p1);
-                if (p2) atomicOr(&S[(w + 2) & RING_WMASK], p2);
+                if (p1) atomicOr(&S[(w + 1) & Geo::RING_WMASK], p1);
+                if (p2) atomicOr(&S[(w + 2) & Geo::RING_WMASK], p2);
             }
             if (HPC && QUAL) {         // where this tile's words start in the compressed stream (for rlePositions look-ups)
                 hist_o[(t % HIST_TILES) * 64u + lane] = (uint16_t)o;
@@ -1261,11 +1378,11 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                 // A chain needs 32 + 2 (Ph - 1) <= 62 stream bits from its first position on: three ring words, read once and aligned
                 // to the position (a per-lane shift); the walk then takes its window with the uniform shift 2 u and reads no LDS.
                 // The words may lie up to 48 bases past a chain's first position, i.e. below done + 63 P + Ph + 48 <= done + 2080:
-                // with the DEFER_BLOCKS blocks kept behind `done` that is 8224 of the ring's 16384 bases, so they never lap into kept
+                // with the Geo::DEFER blocks kept behind `done` that is 8224 of the four-wave ring's 16384 bases (4128 of the variant's 8192), so they never lap into kept
                 // bases; what they hold beyond `fill` is zero, and positions at or beyond npos are masked in emit whatever they hash to.
                 auto chain_words = [&](unsigned p, uint32_t &lo, uint32_t &hi) {
-                    const unsigned b = 2u * p, w = (b >> 5) & RING_WMASK, sh = b & 31u;
-                    const uint32_t w0 = S[w], w1 = S[(w + 1) & RING_WMASK], w2 = S[(w + 2) & RING_WMASK];
+                    const unsigned b = 2u * p, w = (b >> 5) & Geo::RING_WMASK, sh = b & 31u;
+                    const uint32_t w0 = S[w], w1 = S[(w + 1) & Geo::RING_WMASK], w2 = S[(w + 2) & Geo::RING_WMASK];
                     lo = __builtin_amdgcn_alignbit(w1, w0, sh); hi = __builtin_amdgcn_alignbit(w2, w1, sh);
                 };
                 uint32_t bits = 0u;
@@ -1287,7 +1404,9 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                     do {
                         const uint32_t reva = (Ta ^ comp_mask) & kmask, revb = (Tb ^ comp_mask) & kmask;
                         const uint32_t va = fa < reva ? fa : reva, vb = fb < revb ? fb : revb;
-                        if (APPROX) {
+                        if (PF) {
+                            pf_probe(va, ba); pf_probe(vb, bb);
+                        } else if (APPROX) {
                             uint32_t ra, rb;
                             kmer_hash32_hi_shared_x2<GUARD>(va, vb, ra, rb, g);
                             asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(ba) : "v"(ra), "s"(cand_limit) : "vcc");
@@ -1310,7 +1429,10 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
                         if (g < guard_limit) bits = guarded_redo(P);
                     }
                 };
-                if (K == 15u) { if (APPROX && !unguarded) tail_walk(std::true_type(), std::true_type()); else tail_walk(std::true_type(), std::false_type()); }
+                if constexpr (PF) {
+                    tail_walk(std::true_type(), std::false_type());
+                    bits = confirm(bits, P, npos);
+                } else if (K == 15u) { if (APPROX && !unguarded) tail_walk(std::true_type(), std::true_type()); else tail_walk(std::true_type(), std::false_type()); }
                 else tail_walk(std::false_type(), std::integral_constant<bool, APPROX>());
                 emit(bits, P, npos);
             }
@@ -1378,6 +1500,30 @@ __global__ __launch_bounds__(FAST_BLOCK, 5) void scan_fast_kernel(ScanArgs a) {
         }
         wave_lds_sync();       // ring zeroed, stage drained: the next read starts clean
     }
+}
+
+// The selected-key bitmap of the pre-filtered variant, built once per (l, hpc, threshold, geometry): every 15-digit key through
+// prefilter.hpp's rule, the selected ones ORed into `bitmap` (zeroed by the caller), the bits newly set counted in *n_set.
+__global__ __launch_bounds__(256) void prefilter_build_kernel(uint32_t *bitmap, uint64_t threshold, unsigned log2_bits, uint32_t *n_set) {
+    prefilter_build_range(blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, threshold, log2_bits, [&](uint32_t idx) {
+        const uint32_t bit = 1u << (idx & 31u);
+        if (!(atomicOr(&bitmap[idx >> 5], bit) & bit)) atomicAdd(n_set, 1u);
+    });
+}
+
+// A batch the pre-filtered variant shares with the four-wave kernel: the reads the four-wave launch leaves alone -- those shorter than
+// `limit` (the variant's) and those flagged in `masked` (the general kernel's; may be null)
+// ; *long_bases: the bases of the reads of `limit` bases or more (grid-stride, one atomic a wave)
+__global__ __launch_bounds__(256) void split_skip_kernel(const uint32_t *len, const uint8_t *masked, uint32_t n_reads, uint32_t limit, uint8_t *skip,
+                                                         unsigned long long *long_bases) {
+    uint64_t sum = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t L = len[i];
+        skip[i] = (uint8_t)((L < limit || (masked && masked[i])) ? 1u : 0u);
+        if (L >= limit) sum += L;
+    }
+    sum = wave_sum_u64(sum);
+    if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(long_bases, (unsigned long long)sum);
 }
 
 // ---- padded -> dense CSR (+ per-minimizer minimum quality) -------------------------------------
@@ -1602,6 +1748,38 @@ struct ScanTurn {
     ~ScanTurn() { unlock(); }
 };
 
+// The context's bitmap for (l = 15, compressed, threshold, log2_bits): built on the context's stream when the key changes (a run of
+// the tool has one key; tests change it), kept until the context goes.  *fill_ok: the bitmap is sparse enough to pay -- at most a
+// quarter of its bits set (density 0.005f: 45 657 of 524 288, 8.7 %; from about density 0.013f on the existing walk is taken).  A
+// geometry forced by "scan_prefilter_log2_bits" is a test's and is used whatever its fill.
+static int prefilter_ensure(mdbg_ctx *ctx, uint64_t threshold, unsigned log2_bits, bool forced, bool *fill_ok) {
+    constexpr size_t WORDS = PREFILTER_BYTES / 4;               // the buffer: the bitmap (always 64 KB: the kernel copies all of it) + the count
+    if (!ctx->prefilter_bits) {
+        std::lock_guard<std::mutex> g(hip_mem_mutex());
+        hipError_t e = hipMalloc((void **)&ctx->prefilter_bits, (WORDS + 4) * 4);
+        if (e != hipSuccess) { ctx->prefilter_bits = nullptr; return set_error(ctx, MDBG_ENOMEM, "hipMalloc of the scan's key bitmap: %s", hipGetErrorString(e)); }
+        ctx->prefilter_valid = false;
+    }
+    if (!ctx->prefilter_valid || ctx->prefilter_threshold != threshold || ctx->prefilter_log2 != log2_bits) {
+        ctx->prefilter_valid = false;
+        MDBG_HIP_CHECK(ctx, hipMemsetAsync(ctx->prefilter_bits, 0, (WORDS + 4) * 4, ctx->stream));
+        {
+            LaunchTimer timer(ctx, "scan_prefilter_build");
+            hipLaunchKernelGGL(prefilter_build_kernel, dim3((unsigned)ctx->n_cu * 16u), dim3(256), 0, ctx->stream, ctx->prefilter_bits, threshold, log2_bits,
+                               ctx->prefilter_bits + WORDS);
+        }
+        MDBG_HIP_CHECK(ctx, hipGetLastError());
+        uint32_t n_set = 0;
+        hipError_t e = memcpy_sync(ctx, &n_set, ctx->prefilter_bits + WORDS, 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "the scan's key bitmap: %s", hipGetErrorString(e));
+        ctx->prefilter_threshold = threshold; ctx->prefilter_log2 = log2_bits; ctx->prefilter_set = n_set;
+        ctx->prefilter_valid = true;
+        ctx->scan_info[2]++; ctx->scan_info[3] = n_set; ctx->scan_info[4] = log2_bits;
+    }
+    *fill_ok = forced || (uint64_t)ctx->prefilter_set * 4ull <= (1ull << log2_bits);
+    return MDBG_OK;
+}
+
 template <bool HPC, bool Q, bool N>
 static void launch_variant(mdbg_ctx *ctx, const ScanArgs &a, unsigned max_blocks, uint32_t n_items) {
     // A few reads per wave, then the wave retires.  One resident generation of persistent waves (the first design)
@@ -1619,12 +1797,64 @@ static void launch_variant(mdbg_ctx *ctx, const ScanArgs &a, unsigned max_blocks
     hipLaunchKernelGGL((scan_kernel<HPC, Q, N>), dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, ctx->stream, a);
 }
 
-static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool has_n, uint32_t n_items) {
+// static LDS of a kernel, asked once (0: the query failed)
+static size_t kernel_static_lds(const void *kernel) {
+    hipFuncAttributes at;
+    if (hipFuncGetAttributes(&at, kernel) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return at.sharedSizeBytes;
+}
+
+// pf_len_limit > 0: the batch may take the pre-filtered variant, whose stage a read shorter than that is expected to fit; pf_split:
+// the batch also holds longer reads -- a launch of the four-wave kernel in front of it scans those (ScanArgs::pf_len_split)
+static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool has_n, uint32_t n_items, uint32_t pf_len_limit = 0, bool pf_split = false,
+                       uint64_t batch_bases = 0) {
     a.n_reads = n_items;
     const unsigned max_blocks = (unsigned)ctx->n_cu * 8u;
     static const bool no_fast = getenv("MDBG_SCAN_NO_FAST") != nullptr;      // A/B: the general kernel for everything
     static const bool no_approx = getenv("MDBG_SCAN_NO_APPROX") != nullptr;  // A/B: full 64-bit verdict at every position
     const bool fast = (!has_q || a.cursor) && !has_n && !a.subset && !no_fast;
+    using FastKernel = void (*)(ScanArgs);
+    // (not when the candidate limit would saturate -- a threshold within a few 2^32 of 2^64, density 1.0f: the full verdict then)
+    const bool approx = fast && a.cursor && !no_approx && (a.threshold >> 32) + 3ull + (uint64_t)a.cand_slack < 0xFFFFFFFFull;
+    // The pre-filtered variant ("scan_prefilter", MDBG_SCAN_PREFILTER): compressed reads at l = 15 without qualities, the candidate
+    // test as it is by default, a batch most of whose reads fit its smaller stage (mdbg_scan), a bitmap sparse enough (prefilter_ensure) -- and as many
+    // waves a workgroup as leave "scan_lds_reserve" free: 16, else 8, else the four-wave kernels with their padding.  Decided, and
+    // the bitmap queued on the context's stream, before the "scan" timer and the hand-over to the scan's stream.
+    FastKernel pf_kernel = nullptr;
+    unsigned pf_waves = 0;
+    if (approx && hpc && !has_q && a.K == PREFILTER_L && a.cand_slack == 0u && a.guard_slack == 0u && pf_len_limit &&
+        ctx->scan_prefilter && !ctx->scan_lds_pad) {
+        const size_t total = ctx->lds_per_cu ? ctx->lds_per_cu : 163840u;
+        const size_t room = total > ctx->scan_lds_reserve ? total - ctx->scan_lds_reserve : 0;
+        const FastKernel pf16 = scan_fast_kernel<true, false, true, 16>, pf8 = scan_fast_kernel<true, false, true, 8>;
+        static const size_t lds16 = kernel_static_lds(reinterpret_cast<const void *>(pf16)), lds8 = kernel_static_lds(reinterpret_cast<const void *>(pf8));
+        if (!lds16 || !lds8) return set_error(ctx, MDBG_EHIP, "hipFuncGetAttributes of the pre-filtered scan kernels failed");
+        if (lds16 <= room) { pf_kernel = pf16; pf_waves = 16; }
+        else if (lds8 <= room) { pf_kernel = pf8; pf_waves = 8; }
+        if (pf_kernel) {
+            const bool forced = ctx->scan_prefilter_log2_bits != 0u;
+            bool fill_ok = false;
+            MDBG_TRY(prefilter_ensure(ctx, a.threshold, forced ? ctx->scan_prefilter_log2_bits : PREFILTER_LOG2_BITS, forced, &fill_ok));
+            if (!fill_ok) pf_kernel = nullptr;
+        }
+    }
+    // Reads too long for the variant's stage: when they hold at most 1/32 of the batch's bases the four-wave kernel scans them in a launch
+    // of its own (every other read flagged in its `skip`), the variant the rest.  That launch is sparse -- most waves of a block idle -- so
+    // a batch with many long reads loses more there than the variant gains (measured: profiles/prefilter_varied_lengths.txt) and keeps
+    // the four-wave kernel for all its reads.
+    pf_split = pf_split && pf_kernel;
+    DevBuf<uint8_t> d_split;        // pf_split: what the four-wave launch skips (back to the pool on return: reuse is ordered on the context's stream)
+    if (pf_split) {
+        DevBuf<unsigned long long> d_long;
+        MDBG_TRY(d_split.alloc(ctx, n_items));
+        MDBG_TRY(d_long.alloc(ctx, 1));
+        MDBG_HIP_CHECK(ctx, hipMemsetAsync(d_long.p, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(split_skip_kernel, dim3(grid_for(n_items, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0, ctx->stream, a.len, a.skip, n_items, pf_len_limit,
+                           d_split.p, d_long.p);
+        unsigned long long long_bases = 0;
+        if (memcpy_sync(ctx, &long_bases, d_long.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan: the long reads' bases could not be counted");
+        if (long_bases * 32ull > batch_bases) { pf_split = false; pf_kernel = nullptr; }
+    }
     // "table_cu_count": the context's own stream is confined to a few CUs; the block-structured kernel goes to a stream over all of
     // them, ordered after what the context has queued so far and before what it queues next
     hipStream_t on = ctx->stream;
@@ -1636,9 +1866,12 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
         if (e != hipSuccess) { (void)hipEventDestroy(ordered); return set_error(ctx, MDBG_EHIP, "scan stream hand-over: %s", hipGetErrorString(e)); }
         on = ctx->scan_stream;
     }
+    if (fast) ctx->scan_info[6] = pf_kernel ? 1 : 0;
     {
         LaunchTimer timer(ctx, "scan", on);
-        if (fast) {
+        const uint8_t *const batch_skip = a.skip;
+        if (pf_split) a.skip = d_split.p;           // first the long reads, by the four-wave kernel below
+        if (fast && (!pf_kernel || pf_split)) {
             // plain ACGT without qualities: the block-structured kernel; a few reads per wave, then the wave retires
             const uint64_t per_wave = ctx->scan_reads_per_wave;
             uint64_t blocks = ((uint64_t)n_items + FAST_WAVES * per_wave - 1) / (FAST_WAVES * per_wave);
@@ -1646,9 +1879,7 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;
             // bump mode: candidates by the upper half of the hash (span_step<APPROX>); the host's re-run of a read covers a false one
             const dim3 g((unsigned)blocks), b(FAST_BLOCK);
-            using FastKernel = void (*)(ScanArgs);
-            // (not when the candidate limit would saturate -- a threshold within a few 2^32 of 2^64, density 1.0f: the full verdict then)
-            const bool approx = a.cursor && !no_approx && (a.threshold >> 32) + 3ull + (uint64_t)a.cand_slack < 0xFFFFFFFFull;
+            ctx->scan_info[1]++;
             const FastKernel fk = approx ? (hpc ? (has_q ? scan_fast_kernel<true, true, true> : scan_fast_kernel<true, false, true>)
                                                 : (has_q ? scan_fast_kernel<false, true, true> : scan_fast_kernel<false, false, true>))
                                          : (hpc ? (has_q ? scan_fast_kernel<true, true, false> : scan_fast_kernel<true, false, false>)
@@ -1674,12 +1905,26 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
                 } else (void)hipGetLastError();
             }
             hipLaunchKernelGGL(fk, g, b, lds_pad, on, a);
+        } else if (fast) {
+            // (the pre-filtered variant below takes every read)
         } else if (hpc) {
             if (has_n) { if (has_q) launch_variant<true, true, true>(ctx, a, max_blocks, n_items); else launch_variant<true, false, true>(ctx, a, max_blocks, n_items); }
             else { if (has_q) launch_variant<true, true, false>(ctx, a, max_blocks, n_items); else launch_variant<true, false, false>(ctx, a, max_blocks, n_items); }
         } else {
             if (has_n) { if (has_q) launch_variant<false, true, true>(ctx, a, max_blocks, n_items); else launch_variant<false, false, true>(ctx, a, max_blocks, n_items); }
             else { if (has_q) launch_variant<false, true, false>(ctx, a, max_blocks, n_items); else launch_variant<false, false, false>(ctx, a, max_blocks, n_items); }
+        }
+        a.skip = batch_skip;
+        if (pf_kernel) {
+            // one workgroup of pf_waves waves per CU; it deals its chunk of reads out to its waves
+            a.pf_bits = ctx->prefilter_bits;
+            a.pf_shift = 32u - ctx->prefilter_log2;
+            const uint64_t chunk = std::min<uint64_t>((uint64_t)pf_waves * ctx->scan_reads_per_wave, 1u << 24);
+            a.pf_chunk = (uint32_t)chunk;
+            const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, ((uint64_t)n_items + chunk - 1) / chunk), 0x7FFFFFFFull);
+            a.pf_len_split = pf_split ? pf_len_limit : 0u;
+            hipLaunchKernelGGL(pf_kernel, dim3((unsigned)blocks), dim3(64u * pf_waves), 0, on, a);
+            ctx->scan_info[0]++; ctx->scan_info[5] = pf_waves;
         }
     }
     if (ordered) {
@@ -1863,12 +2108,19 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
         a.cand_slack = ctx->scan_cand_slack;
         a.guard_slack = ctx->scan_guard_slack;
         a.wave_priority = ctx->scan_wave_priority;
+        // The pre-filtered variant stages PF_STAGE_CAP rows a read, under half of the above.  A read is expected to fit it below pf_len_limit
+        // bases (the expectation above against that stage: 27 kb at density 0.005f).  The variant is taken when the AVERAGE read is below that;
+        // a few longer reads in such a batch are scanned by the four-wave kernel in a launch of its own (launch_scan), so that a tail of
+        // long reads neither keeps the batch from the variant nor is left to the general kernel
+        const double pf_limit_bases = ((double)PF_STAGE_CAP - 24.0) / ((double)p->density * 0.8 * 1.4);
+        const uint32_t pf_len_limit = hpc && (double)reads->n_bases / (double)n < pf_limit_bases ? (uint32_t)std::min(pf_limit_bases, 4294967295.0) : 0u;
+        const bool pf_split = pf_len_limit && reads->max_len >= pf_len_limit;
         a.skip = route_masked ? reads->d_masked.p : nullptr;
         unsigned long long h_ctl[CTL_WORDS];
         {
             ScanTurn scan_turn(ctx->device);      // one scan kernel at a time per device (see below)
             if (!scans_may_interleave()) scan_turn.lock();
-            if ((rc = launch_scan(ctx, a, hpc, has_q, false, n))) return fail(rc);
+            if ((rc = launch_scan(ctx, a, hpc, has_q, false, n, pf_len_limit, pf_split, reads->n_bases))) return fail(rc);
             if ((rc = quality_finish())) return fail(rc);          // host work while the kernel runs
             e = memcpy_sync(ctx, h_ctl, d_ctl.p, CTL_WORDS * 8, hipMemcpyDeviceToHost);
         }
@@ -2114,3 +2366,9 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
     *out = m;
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
+
+extern "C" int mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]) {
+    if (!ctx || !info) return MDBG_EINVAL;
+    for (int i = 0; i < 8; i++) info[i] = ctx->scan_info[i];
+    return MDBG_OK;
+}
