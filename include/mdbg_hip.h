@@ -92,6 +92,20 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *   "scan_prefilter_log2_bits"  tests only: the bitmap is built and probed with 2^value bits (10 .. 19; 0 = the kernel's own 2^19) and
  *                           used whatever its fill, so that nearly every position reaches the confirmation with the full hash and its
  *                           list overflows.  Results never depend on it
+ *   "scan_segments"         long reads, contigs and unitigs cut into segments that the block-structured scan takes one wave each: a plain read
+ *                           (no N, no case flip) of more than one segment is scanned as several views -- each owns the windows that start
+ *                           in its segment and reads one 2048-base tile on behind it -- and the views' rows are joined in read order.
+ *                           1 (default; negative too) = automatic: only in a batch that would otherwise leave the block-structured kernels
+ *                           because of its reads' length alone (the average read expected to select more rows than a wave stages, 384:
+ *                           about 64 kb at density 0.005) -- such a batch stays on them with its long reads cut; 0 = never (the routing
+ *                           as before); 2 = what 1 does, and every such read in any batch that takes the block-structured kernels.  A read with a cut
+ *                           behind which 2048 bases hold fewer than minimizer_size run starts (a homopolymer of about 2000 bases) stays
+ *                           whole, and a read one of whose views outgrows its stage goes whole the way outgrown reads go.  The
+ *                           environment variable MDBG_SCAN_SEGMENTS=0 / 1 / 2 sets the default of new contexts.  Results never depend
+ *                           on it; mdbg_scan_info tells how many reads were cut
+ *   "scan_segment_bases"    raw bases of a segment: a multiple of 2048 (anything else is MDBG_EINVAL); <= 0 restores the default, 16384
+ *                           (expected to select 16384 * 0.005 * 0.8 * 1.4 + 24 = 116 rows, inside the pre-filtered variant's stage of
+ *                           176).  The views are scanned by the variant a batch of reads of that length would take
  *   "index_tuning"          the passes above firstK over the one-slot tables (bits; default 19; negative: the default): 1 = a slot's key and
  *                           value fetched in one trip, 2 = the insert first looks at a window's home slot with plain loads (a key found
  *                           there is done without an atomic), 4 = two windows of a lane in flight (measured: no gain), 8 = look-up and
@@ -328,7 +342,8 @@ int  mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]);
 /* Which block-structured scan kernels the context has launched (mdbg_scan; "scan_prefilter" above): info[0] = launches of the pre-filtered
  * variant, [1] = launches of the four-wave block kernels, [2] = selected-key bitmaps built, [3] = bits set in the last one, [4] = log2 of
  * its size in bits, [5] = waves per workgroup of the last pre-filtered launch (16, or 8 under a large "scan_lds_reserve"), [6] = 1 when
- * the last block-kernel launch was the pre-filtered variant, [7] = 0.  No reference analogue: the reference hashes every position. */
+ * the last block-kernel launch was the pre-filtered variant, [7] = reads the context's last mdbg_scan scanned as segments ("scan_segments";
+ * reads that fell back whole are not counted).  No reference analogue: the reference hashes every position. */
 int  mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]);
 /* Order-independent sums over the rows, wrapping at 2^64, computed on the device (nothing but 32 bytes travels):
  *   sums[0] = sum abundance * hash_lo -- the "Checksum kminmer abundance" the reference logs when it loads the table again

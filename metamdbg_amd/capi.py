@@ -208,7 +208,7 @@ class Context:
         a = (C.c_uint64 * 8)()
         self.check(lib().mdbg_scan_info(self.h, a))
         names = ("prefiltered_launches", "block_launches", "bitmaps_built", "bitmap_bits_set", "bitmap_log2_bits", "prefilter_waves",
-                 "last_prefiltered")
+                 "last_prefiltered", "reads_segmented")
         return {k: int(v) for k, v in zip(names, a)}
 
     # -- timing ---------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/mdbg_hip.h"
+#include "segments_dev.hpp"
 
 namespace mdbg {
 
@@ -153,9 +154,13 @@ struct mdbg_ctx {
     bool prefilter_valid = false;
     uint64_t prefilter_threshold = 0;
     uint32_t prefilter_log2 = 0, prefilter_set = 0;
+    uint32_t scan_segments = 1;             // "scan_segments": plain reads of more than one segment are cut into views, one wave each (scan.hip, segments_dev.hpp) --
+                                            // 1 = automatic (default): in a batch that would leave the block-structured kernels for its reads' length alone, 0 = never,
+                                            // 2 = in every batch those kernels take (opt-in: its pre-pass costs more than it gains) (mdbg_set_option, MDBG_SCAN_SEGMENTS)
+    uint32_t scan_segment_bases = mdbg::SEG_DEFAULT_BASES;    // "scan_segment_bases": raw bases of a segment, a multiple of 2048
     uint64_t scan_info[8] = {0};            // mdbg_scan_info: [0] launches of the pre-filtered variant, [1] of the four-wave block kernels, [2] bitmaps built,
                                             // [3] bits set in the last, [4] its log2 size, [5] waves a workgroup of the last pre-filtered launch, [6] 1 when
-                                            // the last block-kernel launch was pre-filtered
+                                            // the last block-kernel launch was pre-filtered, [7] reads the last mdbg_scan scanned as segments
     // distinct keys per k-min-mer instance seen by the last call OF THE SAME KIND (table sizing): the first pass keeps every
     // key, refined / index only those above abundance 1 -- one shared hint made every first pass after an index pass rebuild its table
     double key_ratio_hint[4] = {0.0625, 0.0625, 0.0625, 0.0625};   // [0] first pass, [1] refined, [2] index, [3] sharded first pass

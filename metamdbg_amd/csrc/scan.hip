@@ -29,6 +29,7 @@
 #include "murmur.hpp"
 #include "objects.hpp"
 #include "prefilter.hpp"
+#include "segments_dev.hpp"
 
 #include <fcntl.h>
 #include <sys/file.h>
@@ -101,6 +102,11 @@ struct ScanArgs {
     uint32_t pf_chunk;            // reads a workgroup deals out to its waves
     uint32_t pf_len_split;        // > 0: that variant passes over the reads of this many bases or more -- too long for its stage, they are
                                   // the four-wave kernel's, launched in front of it with the other reads flagged in `skip` (launch_scan)
+    // scan_fast_kernel<.., SEG> (views of long reads, segments_dev.hpp): n_reads counts views, and out_begin / out_count / out_flags /
+    // over_list / list_counters / cursor and the row arrays are the views' own; the join kernels put the reads together
+    const SegView *views;
+    unsigned long long *view_cx;  // per view: its words' share of the read's complexity sum
+    uint32_t seg_tiles;           // tiles of a segment ("scan_segment_bases" / 2048)
 };
 
 // squeeze the 2-bit fields of x whose flag bit (bit 2i of d) is set down to the low end
@@ -831,7 +837,12 @@ template <int PFW> struct FastGeometry {
 };
 static_assert(FastGeometry<16>::PF_LDS + 28672 <= 163840, "16 waves fit beside the 28 KB the benchmark's other batch asks for");
 
-template <bool HPC, bool QUAL, bool APPROX, int PFW = 0>
+// SEG: the items are VIEWS of long reads (segments_dev.hpp; mdbg_scan, "scan_segments") instead of reads.  A view is scanned like a
+// read that begins at a tile of its read and ends one tile behind its segment, with four differences: the base in front of it is the
+// read's (no run start is made up, the complexity bound's boundary word is the read's), the end trim applies at the read's ends only,
+// it lists the windows it OWNS and no others, and its words enter the complexity sum with the weights of their place in the whole read --
+// the sum goes to view_cx and the decision is taken once per read, after the join.  Rows carry view positions; the join adds c_s.
+template <bool HPC, bool QUAL, bool APPROX, int PFW = 0, bool SEG = false>
 __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void scan_fast_kernel(ScanArgs a) {
     using Geo = FastGeometry<PFW>;          // this instantiation's workgroup, ring and stage
     constexpr bool PF = Geo::PF;
@@ -928,14 +939,26 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         return k < chunk_n ? (uint32_t)chunk0 + k : NO_READ;
     };
     for (uint32_t r = PF ? take_read() : wave_global; PF ? r != NO_READ : r < a.n_reads; r = PF ? take_read() : r + n_waves) {
-        if constexpr (PF) { if (a.pf_len_split && a.len[r] >= a.pf_len_split) continue; }      // the four-wave launch's read
-        if (a.skip && a.skip[r]) {          // a read with an N or a case flip: the host sends it through the general kernel
+        if constexpr (PF && !SEG) { if (a.pf_len_split && a.len[r] >= a.pf_len_split) continue; }      // the four-wave launch's read
+        if (!SEG && a.skip && a.skip[r]) {          // a read with an N or a case flip: the host sends it through the general kernel
             if (a.cursor && lane == 0) { a.out_begin[r] = 0; a.out_count[r] = 0; a.out_flags[r] = 0; }
             continue;
         }
-        const uint32_t L = a.len[r];
-        const uint64_t w_base = a.word_off[r];
+        SegView view{};
+        if constexpr (SEG) {
+            view = a.views[r];
+            if (view.flags & SEG_DEAD) {        // a view of an unsegmentable read: the read is scanned whole elsewhere
+                if (lane == 0) { a.out_begin[r] = 0; a.out_count[r] = 0; a.out_flags[r] = 0; a.view_cx[r] = 0ull; }
+                continue;
+            }
+        }
+        const uint32_t rd = SEG ? view.read : r;                       // the read whose words, qualities and length these are
+        const bool seg_inner = SEG && !(view.flags & SEG_FIRST);       // a view with the read's own bases in front of it
+        const uint32_t L = SEG ? view.raw_len : a.len[r];
+        const uint64_t w_base = a.word_off[rd] + (SEG ? (uint64_t)view.tile0 * TILE_WORDS : 0ull);
         const uint64_t *rw = a.words + w_base;
+        // the end trim in front (Kmer.hpp:1395) is the read's: its first view's
+        const uint32_t trim_first = seg_inner ? 0u : a.trim;
         const uint32_t nwords = (L + 31u) / 32u;
         const uint32_t ntiles = (nwords + TILE_WORDS - 1) / TILE_WORDS;
         const bool bump = a.cursor != nullptr;
@@ -966,7 +989,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             uint32_t k = rel - o[lo];
             const uint32_t wi = tt * TILE_WORDS + lo;
             const uint64_t x = rw[wi];
-            const uint32_t pl = wi ? (uint32_t)(rw[wi - 1] >> 62) : (((uint32_t)x & 3u) ^ 1u);   // the first base of the read starts a run
+            const uint32_t pl = (wi || seg_inner) ? (uint32_t)(rw[(int64_t)wi - 1] >> 62) : (((uint32_t)x & 3u) ^ 1u);   // the first base of the read starts a run
             const int rem = (int)L - (int)(wi * 32u);
             const unsigned nvalid = rem >= 32 ? 32u : (unsigned)rem;
             const uint64_t vspread = nvalid == 32 ? M5 : (((1ull << (2 * nvalid)) - 1ull) & M5);
@@ -980,7 +1003,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             }
             return wi * 32u + (pos >> 1);
         };
-        const uint8_t *qq = QUAL ? a.qual + a.qual_off[r] : nullptr;
+        const uint8_t *qq = QUAL ? a.qual + a.qual_off[rd] + (SEG ? (uint64_t)view.tile0 * SEG_TILE_BASES : 0ull) : nullptr;
         // minimum quality of the minimizer at compressed position j; unknown = false when a run start has left the history
         auto min_quality = [&](uint32_t j, bool &known) -> uint8_t {
             uint32_t os = j, oe = j + K;
@@ -1015,7 +1038,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         uint32_t flushed = 0;      // ... of which already written to the output slot
         uint32_t n_mat = 0;        // ... of which materialised (rows [n_mat, nout) of the stage hold a position only)
         uint32_t zero_from = 0;    // ring position from which bases are still kept (<= done): the oldest block with listed positions
-        uint32_t prev_last = 0;
+        uint32_t prev_last = seg_inner ? (uint32_t)(rw[-1] >> 62) : 0u;
         // complexity bound: sum of weight x Q over the read's words (complexity_dev.hpp).  Q <= CX_Q_MAX = 3840 and the weights of a
         // read sum to 2 nW <= L / 16, so below 2^24 bases the whole sum is under 240 * 2^24 < 2^32: a lane adds its words up in 32
         // bits and the wave sum is taken once per read, in 32 bits.  A longer read (wave-uniform test on L) folds the lanes' sums
@@ -1024,8 +1047,11 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         uint32_t cx_acc = 0;       // per lane
         uint64_t cx_total = 0;     // wave-uniform: what the tiles of a long read have folded so far
         const bool cx_long = L >= (1u << 24);
-        uint64_t prev_word = 0;
-        const uint32_t cx_nW = complexity_windows(L);      // number of complexity windows (ReadSelection.hpp:1171-1228)
+        uint64_t prev_word = seg_inner ? rw[-1] : 0ull;     // (a view: the boundary word is counted here, in the view behind the cut)
+        const uint32_t cx_nW = complexity_windows(SEG ? a.len[rd] : L);      // number of complexity windows (ReadSelection.hpp:1171-1228)
+        // a view adds the words of its own tiles (the halo's are the next view's), at their place in the read
+        const uint32_t cx_tiles = SEG ? ((view.flags & SEG_LAST) ? ntiles : a.seg_tiles) : ntiles;
+        const uint32_t cx_t0 = SEG ? view.tile0 : 0u;
 
         // ---- materialisation of the listed positions, one per lane: window, canonical form, direction and, with qualities, the
         // look-ups behind min_quality.  Deferred over up to Geo::DEFER blocks (a block lists about ten positions: materialised
@@ -1062,7 +1088,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 const uint32_t first_j = lane * P;                 // span-relative index of this lane's first position
                 if (first_j >= npos_limit) bits = 0;
                 else if (first_j + P > npos_limit) bits &= ~((1u << (first_j + P - npos_limit)) - 1u);
-                if (done == 0u && lane == 0u && a.trim) bits &= ~(1u << (P - 1u));      // Kmer.hpp:1395
+                if (done == 0u && lane == 0u && trim_first) bits &= ~(1u << (P - 1u));      // Kmer.hpp:1395
             }
             if (__ballot(bits != 0u) == 0ull) return;
             if (a.n_rep) {          // Kmer.hpp:1437: repetitive minimizers are not selected
@@ -1161,7 +1187,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 const uint32_t first_j = lane * P;
                 if (first_j >= npos_limit) bits = 0;
                 else if (first_j + P > npos_limit) bits &= ~((1u << (first_j + P - npos_limit)) - 1u);
-                if (done == 0u && lane == 0u && a.trim) bits &= ~(1u << (P - 1u));
+                if (done == 0u && lane == 0u && trim_first) bits &= ~(1u << (P - 1u));
             }
             uint32_t kept = 0u;
             for (;;) {
@@ -1287,16 +1313,17 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             const unsigned nvalid = rem <= 0 ? 0u : (rem >= 32 ? 32u : (unsigned)rem);
 
             // ---- complexity: upper bound from per-word 2-mer counts (as in scan_kernel; the word below comes over DPP) ----
-            if (a.apply_filters) {
+            if (a.apply_filters && (!SEG || t < cx_tiles)) {
                 const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
                 const uint32_t pl32 = lane_below(xl, (uint32_t)prev_word), ph32 = lane_below(xh, (uint32_t)(prev_word >> 32));
                 prev_word = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)xh, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)xl, 63);
                 // word wq = wi - 1 enters window wq (if wq < nW) and window wq - 1 (if 1 <= wq <= nW): weight 1 at wq = 0 and nW, 2 between
                 const uint32_t q = word_pair_q(((uint64_t)ph32 << 32) | pl32, xl);
-                if (t != 0u && t * TILE_WORDS + (TILE_WORDS - 1u) <= cx_nW) {
+                const uint32_t tg = t + cx_t0;                    // the tile's place in the read
+                if (tg != 0u && tg * TILE_WORDS + (TILE_WORDS - 1u) <= cx_nW) {
                     cx_acc += q + q;                              // a tile in the middle of the read (wave-uniform test): words 1 .. nW - 1 only
                 } else {
-                    const uint32_t wq = wi - 1u;                  // lane 0 of tile 0: wraps around, weight 0
+                    const uint32_t wq = cx_t0 * TILE_WORDS + wi - 1u;      // lane 0 of tile 0: wraps around, weight 0
                     const uint32_t w2 = wq < cx_nW ? q : 0u, w1 = (wq - 1u) < cx_nW ? q : 0u;
                     cx_acc += w2 + w1;
                 }
@@ -1308,7 +1335,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             unsigned c;
             if (HPC) {
                 uint32_t pl = lane_below((uint32_t)(x >> 62), prev_last);
-                if (wi == 0) pl = ((uint32_t)x & 3u) ^ 1u;      // the first base of the read starts a run whatever precedes it
+                if (wi == 0 && !seg_inner) pl = ((uint32_t)x & 3u) ^ 1u;      // the first base of the read starts a run whatever precedes it
                 unsigned nbits;
                 y = compress_pairs_lut(HpcLut{lds_lut_b, lds_lut_n}, x, pl, &nbits);
                 c = nbits >> 1;
@@ -1350,7 +1377,8 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             // ---- full blocks: 2048 positions, every one followed by a known base ----
             // (with _trimBps == 0 the last l-mer is a position too: a block also runs at exactly 2048 + K bases, or the tail would
             // be left with 2049 positions -- 36 per lane, four more than a lane's verdict vector holds)
-            while (fill - done >= BLOCK_POS + K + a.trim) aligned_block(std::integral_constant<int, (int)SPAN>());
+            // (a view: whole blocks of OWNED positions only; what it owns beyond them is the tail's)
+            while (fill - done >= BLOCK_POS + K + a.trim && (!SEG || view.n_own - done >= BLOCK_POS)) aligned_block(std::integral_constant<int, (int)SPAN>());
         }
         // (a last half block of 1024 positions, 16 per lane, in front of the group-of-four, one-chain tail of rounds 2 - 6 was measured:
         // 11.73 against 11.76 ms, not kept.  What that tail cost was its padding -- spans of 4 ceil(npos / 256) positions, 1536 hashed
@@ -1364,6 +1392,9 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             const uint32_t live = fill - done;
             uint32_t npos = live > K ? live - K : 0u;
             if (a.trim == 0u && live >= K) npos = live - K + 1u;
+            // a view stops at the last window it owns: the halo behind it has completed every one of them (segments_dev.hpp), and the
+            // block loop has left fewer than 2048 of them or fewer than 2048 + l + trim bases
+            if (SEG && npos > view.n_own - done) npos = view.n_own - done;
             // (the same in every lane, but derived from loads the compiler takes for per-lane values: as a scalar, so that the walk
             // below is counted and branched on by the scalar unit)
             npos = (uint32_t)__builtin_amdgcn_readfirstlane((int)npos);
@@ -1455,7 +1486,10 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         if (((QUAL && HPC) || APPROX) && __ballot(lost) != 0ull) outgrown = true;      // a run start had left the history, or a false candidate:
                                                                                         // the general kernel redoes the read
         uint8_t flags = 0;
-        if (a.apply_filters && L >= 66) {
+        if constexpr (SEG) {          // the read's decision is the join's, over the sums of all its views
+            const uint64_t cx_view = a.apply_filters ? cx_total + wave_sum_u32(cx_acc) : 0ull;
+            if (lane == 0) a.view_cx[r] = cx_view;
+        } else if (a.apply_filters && L >= 66) {
             if (complexity_suspect(cx_total + wave_sum_u32(cx_acc), cx_nW)) flags |= READ_SUSPECT;
         }
         // ---- the staged minimizers leave in rows ----
@@ -1524,6 +1558,143 @@ __global__ __launch_bounds__(256) void split_skip_kernel(const uint32_t *len, co
     }
     sum = wave_sum_u64(sum);
     if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(long_bases, (unsigned long long)sum);
+}
+
+// ---- long reads as views (segments_dev.hpp; mdbg_scan, "scan_segments") ------------------------------------------------------------
+// The pre-pass: which reads are cut (plain reads of more than one segment), their tiles and views counted ...
+__global__ __launch_bounds__(256) void seg_count_kernel(const uint32_t *len, const uint8_t *masked, uint32_t n_reads, uint32_t G,
+                                                        uint32_t *tiles_per_read, uint32_t *views_per_read, uint8_t *skip) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * 256u) {
+        const uint32_t L = len[i];
+        const bool plain = !(masked && masked[i]);
+        const bool cut = plain && L > G;
+        tiles_per_read[i] = cut ? seg_tiles(L) : 0u;
+        views_per_read[i] = cut ? seg_count(L, G) : 0u;
+        skip[i] = (uint8_t)(plain ? 0u : 1u);            // (seg_plan_kernel adds the reads it cuts)
+    }
+}
+
+// ... the run starts of every tile of those reads, one wave a tile (homopolymer compression only) ...
+__global__ __launch_bounds__(256) void seg_tile_runs_kernel(const uint64_t *words, const uint64_t *word_off, const uint32_t *len, uint32_t n_reads,
+                                                            const uint64_t *tile_off /* n_reads + 1 */, uint32_t *tile_runs) {
+    const unsigned lane = threadIdx.x & 63u;
+    const uint64_t n_tiles = tile_off[n_reads];
+    for (uint64_t gt = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6; gt < n_tiles; gt += ((uint64_t)gridDim.x * 256u) >> 6) {
+        uint32_t lo = 0, hi = n_reads;                   // the read of tile gt: the last r with tile_off[r] <= gt
+        while (hi - lo > 1u) { const uint32_t mid = lo + (hi - lo) / 2u; if (tile_off[mid] <= gt) lo = mid; else hi = mid; }
+        const uint32_t r = lo, L = len[r], t = (uint32_t)(gt - tile_off[r]);
+        const uint64_t *rw = words + word_off[r];
+        const uint32_t nwords = (uint32_t)(((uint64_t)L + 31u) / 32u), wi = t * 64u + lane;
+        uint32_t c = 0;
+        if (wi < nwords) {
+            const uint32_t prev = wi ? (uint32_t)(rw[wi - 1u] >> 62) : seg_first_prev(rw[0]);
+            c = seg_word_run_starts(rw[wi], prev, seg_word_valid(L, wi));
+        }
+        c = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_sum_dpp(c), 63);
+        if (lane == 0) tile_runs[gt] = c;
+    }
+}
+
+// ... and, one wave a read, the exclusive scan of its tiles' run starts (in place), the verdict on its cuts and its views.
+// totals: [0] reads cut, [1] their views.  The reads it cuts are flagged in `skip` beside the masked ones.
+__global__ __launch_bounds__(256) void seg_plan_kernel(const uint32_t *len, uint32_t n_reads, uint32_t G, uint32_t K, int hpc, const uint64_t *tile_off,
+                                                       const uint64_t *view_off, const uint32_t *tile_runs, uint32_t *tile_excl /* exclusive sums of tile_runs inside a read */,
+                                                       SegView *views, uint8_t *skip, uint8_t *read_cut, unsigned long long *totals) {
+    const unsigned lane = threadIdx.x & 63u;
+    for (uint64_t r = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6; r < n_reads; r += ((uint64_t)gridDim.x * 256u) >> 6) {
+        const uint32_t nS = (uint32_t)(view_off[r + 1] - view_off[r]);
+        if (nS == 0u) { if (lane == 0) read_cut[r] = 0; continue; }
+        const uint32_t L = len[r], nT = (uint32_t)(tile_off[r + 1] - tile_off[r]), per = G / SEG_TILE_BASES;
+        const uint32_t *tr = tile_runs + tile_off[r];
+        uint32_t *te = tile_excl + tile_off[r];
+        bool bad = false;
+        uint32_t C = L;
+        if (hpc) {
+            for (uint32_t s = 1u + lane; s < nS; s += 64u) bad = bad || !seg_cut_ok(L, s * G, tr[(uint64_t)s * per], K);
+            uint32_t carry = 0;
+            for (uint32_t t0 = 0; t0 < nT; t0 += 64u) {
+                const uint32_t t = t0 + lane, c = t < nT ? tr[t] : 0u;
+                const uint32_t inc = wave_inclusive_sum_dpp(c);
+                if (t < nT) te[t] = carry + inc - c;
+                carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            }
+            C = carry;
+            __threadfence();          // the lanes read each other's sums below
+        } else {
+            for (uint32_t s = 1u + lane; s < nS; s += 64u) {
+                const uint64_t b = (uint64_t)s * G;
+                bad = bad || !seg_cut_ok(L, (uint32_t)b, (uint32_t)(L - b < SEG_TILE_BASES ? L - b : SEG_TILE_BASES), K);
+            }
+        }
+        const bool live = __ballot(bad) == 0ull;
+        const uint32_t *excl = hpc ? te : nullptr;
+        for (uint32_t s = lane; s < nS; s += 64u)
+            views[view_off[r] + s] = seg_view_make((uint32_t)r, s, nS, L, G, seg_offset(excl, s, nS, L, G, C), seg_offset(excl, s + 1u, nS, L, G, C), live);
+        if (lane == 0) {
+            read_cut[r] = (uint8_t)(live ? 1u : 0u);
+            if (live) { skip[r] = 1; atomicAdd(&totals[0], 1ull); atomicAdd(&totals[1], (unsigned long long)nS); }
+        }
+    }
+}
+
+// The join.  Views that outgrew their stage or met a false candidate are on the views' own list: flagged per view ...
+__global__ __launch_bounds__(256) void seg_mark_views_kernel(const uint32_t *view_over_list, const uint32_t *n_over, uint32_t n_views, uint8_t *view_bad) {
+    const uint32_t n = *n_over < n_views ? *n_over : n_views;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) view_bad[view_over_list[i]] = 1;
+}
+
+// ... then, one wave a cut read: its views' counts and complexity sums added up, its rows placed behind the regions where the
+// exclusive scan over ALL views' counts (row_off) puts its first view -- so a read's rows are contiguous, in view order -- its
+// count, flags and begin set.  A read with a flagged view goes whole the way outgrown reads go (a.over_list), with its exact count.
+// totals: [2] rows joined, [3] reads joined, [4] = 1 when the joined rows did not fit `join_cap`
+__global__ __launch_bounds__(256) void seg_join_reads_kernel(ScanArgs a /* the batch's: out_*, lists, len */, uint32_t n_reads, const uint64_t *view_off,
+                                                             const uint64_t *row_off, const uint8_t *view_bad,
+                                                             const unsigned long long *view_cx, uint8_t *read_cut, uint64_t join_base, uint64_t join_cap,
+                                                             unsigned long long *totals) {
+    const unsigned lane = threadIdx.x & 63u;
+    for (uint64_t r = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6; r < n_reads; r += ((uint64_t)gridDim.x * 256u) >> 6) {
+        if (!read_cut[r]) continue;
+        const uint64_t v0 = view_off[r], v1 = view_off[r + 1];
+        uint64_t cx = 0;
+        bool bad = false;
+        for (uint64_t v = v0 + lane; v < v1; v += 64u) { cx += view_cx[v]; bad = bad || view_bad[v]; }
+        cx = wave_sum_u64(cx);
+        const bool fell_back = __ballot(bad) != 0ull;
+        const uint64_t first = row_off[v0], rows = row_off[v1] - first;
+        const bool fits = first + rows <= join_cap;
+        if (lane == 0) {
+            const uint32_t L = a.len[r];
+            const uint8_t flags = (a.apply_filters && L >= 66u && complexity_suspect(cx, complexity_windows(L))) ? READ_SUSPECT : (uint8_t)0;
+            a.out_count[r] = (uint32_t)rows;
+            a.out_flags[r] = flags;
+            a.out_begin[r] = fell_back || !fits ? 0ull : join_base + first;
+            if (flags & READ_SUSPECT) a.suspect_list[atomicAdd(&a.list_counters[1], 1u)] = (uint32_t)r;
+            if (fell_back) { a.over_list[atomicAdd(&a.list_counters[0], 1u)] = (uint32_t)r; read_cut[r] = 2; }
+            else if (!fits) { totals[4] = 1ull; read_cut[r] = 2; }
+            else { atomicAdd(&totals[2], (unsigned long long)rows); atomicAdd(&totals[3], 1ull); }
+        }
+    }
+}
+
+// ... and, one wave a view, its rows copied to their place in the read's, c_s added to the positions.
+__global__ __launch_bounds__(256) void seg_join_rows_kernel(const SegView *views, uint32_t n_views, const uint8_t *read_cut, const uint64_t *row_off,
+                                                            const uint64_t *view_begin, const uint32_t *view_cnt, uint64_t view_rows_extent,
+                                                            const uint32_t *vmin, const uint32_t *vpos, const uint8_t *vdir, const uint8_t *vmq, int has_q,
+                                                            uint32_t *omin, uint32_t *opos, uint8_t *odir, uint8_t *omq, uint64_t join_base, uint64_t join_cap) {
+    const unsigned lane = threadIdx.x & 63u;
+    for (uint64_t v = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6; v < n_views; v += ((uint64_t)gridDim.x * 256u) >> 6) {
+        const SegView vw = views[v];
+        if ((vw.flags & SEG_DEAD) || read_cut[vw.read] != 1) continue;
+        const uint64_t src = view_begin[v], dst = row_off[v];
+        const uint32_t n = view_cnt[v];
+        if (dst + n > join_cap || src + n > view_rows_extent) continue;       // (never: seg_join_reads_kernel placed the read inside, the view wrote inside)
+        for (uint32_t i = lane; i < n; i += 64u) {
+            omin[join_base + dst + i] = vmin[src + i];
+            opos[join_base + dst + i] = vpos[src + i] + vw.c_s;
+            odir[join_base + dst + i] = vdir[src + i];
+            if (has_q) omq[join_base + dst + i] = vmq[src + i];
+        }
+    }
 }
 
 // ---- padded -> dense CSR (+ per-minimizer minimum quality) -------------------------------------
@@ -1806,8 +1977,9 @@ static size_t kernel_static_lds(const void *kernel) {
 
 // pf_len_limit > 0: the batch may take the pre-filtered variant, whose stage a read shorter than that is expected to fit; pf_split:
 // the batch also holds longer reads -- a launch of the four-wave kernel in front of it scans those (ScanArgs::pf_len_split)
+// seg: the items are views of long reads (ScanArgs::views): the SEG instantiations of the block-structured kernels, chosen as for reads
 static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool has_n, uint32_t n_items, uint32_t pf_len_limit = 0, bool pf_split = false,
-                       uint64_t batch_bases = 0) {
+                       uint64_t batch_bases = 0, bool seg = false) {
     a.n_reads = n_items;
     const unsigned max_blocks = (unsigned)ctx->n_cu * 8u;
     static const bool no_fast = getenv("MDBG_SCAN_NO_FAST") != nullptr;      // A/B: the general kernel for everything
@@ -1816,6 +1988,7 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
     using FastKernel = void (*)(ScanArgs);
     // (not when the candidate limit would saturate -- a threshold within a few 2^32 of 2^64, density 1.0f: the full verdict then)
     const bool approx = fast && a.cursor && !no_approx && (a.threshold >> 32) + 3ull + (uint64_t)a.cand_slack < 0xFFFFFFFFull;
+    if (seg && !approx) return set_error(ctx, MDBG_EINVAL, "scan: views are scanned by the candidate-hash kernels only");
     // The pre-filtered variant ("scan_prefilter", MDBG_SCAN_PREFILTER): compressed reads at l = 15 without qualities, the candidate
     // test as it is by default, a batch most of whose reads fit its smaller stage (mdbg_scan), a bitmap sparse enough (prefilter_ensure) -- and as many
     // waves a workgroup as leave "scan_lds_reserve" free: 16, else 8, else the four-wave kernels with their padding.  Decided, and
@@ -1826,8 +1999,10 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
         ctx->scan_prefilter && !ctx->scan_lds_pad) {
         const size_t total = ctx->lds_per_cu ? ctx->lds_per_cu : 163840u;
         const size_t room = total > ctx->scan_lds_reserve ? total - ctx->scan_lds_reserve : 0;
-        const FastKernel pf16 = scan_fast_kernel<true, false, true, 16>, pf8 = scan_fast_kernel<true, false, true, 8>;
-        static const size_t lds16 = kernel_static_lds(reinterpret_cast<const void *>(pf16)), lds8 = kernel_static_lds(reinterpret_cast<const void *>(pf8));
+        const FastKernel pf16 = seg ? scan_fast_kernel<true, false, true, 16, true> : scan_fast_kernel<true, false, true, 16>;
+        const FastKernel pf8 = seg ? scan_fast_kernel<true, false, true, 8, true> : scan_fast_kernel<true, false, true, 8>;
+        static const size_t lds16 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 16>)),
+                            lds8 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 8>));      // (the same with SEG)
         if (!lds16 || !lds8) return set_error(ctx, MDBG_EHIP, "hipFuncGetAttributes of the pre-filtered scan kernels failed");
         if (lds16 <= room) { pf_kernel = pf16; pf_waves = 16; }
         else if (lds8 <= room) { pf_kernel = pf8; pf_waves = 8; }
@@ -1880,7 +2055,9 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             // bump mode: candidates by the upper half of the hash (span_step<APPROX>); the host's re-run of a read covers a false one
             const dim3 g((unsigned)blocks), b(FAST_BLOCK);
             ctx->scan_info[1]++;
-            const FastKernel fk = approx ? (hpc ? (has_q ? scan_fast_kernel<true, true, true> : scan_fast_kernel<true, false, true>)
+            const FastKernel fk = seg ? (hpc ? (has_q ? scan_fast_kernel<true, true, true, 0, true> : scan_fast_kernel<true, false, true, 0, true>)
+                                             : (has_q ? scan_fast_kernel<false, true, true, 0, true> : scan_fast_kernel<false, false, true, 0, true>))
+                                : approx ? (hpc ? (has_q ? scan_fast_kernel<true, true, true> : scan_fast_kernel<true, false, true>)
                                                 : (has_q ? scan_fast_kernel<false, true, true> : scan_fast_kernel<false, false, true>))
                                          : (hpc ? (has_q ? scan_fast_kernel<true, true, false> : scan_fast_kernel<true, false, false>)
                                                 : (has_q ? scan_fast_kernel<false, true, false> : scan_fast_kernel<false, false, false>));
@@ -1937,6 +2114,50 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
     return MDBG_OK;
 }
 
+// The plan of a batch whose long reads are cut into views (segments_dev.hpp): built on the device by the pre-pass, of which the host
+// learns the totals only
+struct SegPlan {
+    DevBuf<uint32_t> tiles_per_read, views_per_read, tile_runs, tile_excl;
+    DevBuf<uint64_t> tile_off, view_off;
+    DevBuf<SegView> views;
+    DevBuf<uint8_t> skip, read_cut;      // per read: left out of the batch's own launch (masked or cut); 1 = cut, 2 = cut but fallen back
+    DevBuf<unsigned long long> totals;   // [0] reads cut, [1] their views, [2] rows joined, [3] reads joined, [4] the joined rows did not fit
+    uint64_t n_cut = 0, n_views = 0, n_tiles = 0;       // reads cut; views and tiles of the reads long enough to be (those of unsegmentable reads are dead)
+};
+
+static int seg_prepass(mdbg_ctx *ctx, const mdbg_reads *reads, const uint8_t *masked, uint32_t G, uint32_t K, bool hpc, SegPlan &sp) {
+    const uint32_t n = reads->n_reads;
+    const uint64_t max_tiles = reads->n_bases / SEG_TILE_BASES + n, max_views = reads->n_bases / G + n;
+    MDBG_TRY(sp.tiles_per_read.alloc(ctx, n)); MDBG_TRY(sp.views_per_read.alloc(ctx, n));
+    MDBG_TRY(sp.tile_off.alloc(ctx, (size_t)n + 1)); MDBG_TRY(sp.view_off.alloc(ctx, (size_t)n + 1));
+    MDBG_TRY(sp.tile_runs.alloc(ctx, hpc ? max_tiles : 1)); MDBG_TRY(sp.tile_excl.alloc(ctx, hpc ? max_tiles : 1));
+    MDBG_TRY(sp.views.alloc(ctx, max_views)); MDBG_TRY(sp.skip.alloc(ctx, n)); MDBG_TRY(sp.read_cut.alloc(ctx, n)); MDBG_TRY(sp.totals.alloc(ctx, 8));
+    MDBG_HIP_CHECK(ctx, hipMemsetAsync(sp.totals.p, 0, 64, ctx->stream));
+    const unsigned cap = (unsigned)ctx->n_cu * 16u;
+    {
+        LaunchTimer timer(ctx, "scan_segments");
+        hipLaunchKernelGGL(seg_count_kernel, dim3(grid_for(n, 256, cap)), dim3(256), 0, ctx->stream, reads->d_len.p, masked, n, G, sp.tiles_per_read.p,
+                           sp.views_per_read.p, sp.skip.p);
+        MDBG_TRY(exclusive_scan_u32(ctx, sp.tiles_per_read.p, sp.tile_off.p, n));
+        MDBG_TRY(exclusive_scan_u32(ctx, sp.views_per_read.p, sp.view_off.p, n));
+        if (hpc) hipLaunchKernelGGL(seg_tile_runs_kernel, dim3(grid_for(max_tiles * 64u, 256, cap)), dim3(256), 0, ctx->stream, reads->d_words.p,
+                                    reads->d_word_off.p, reads->d_len.p, n, sp.tile_off.p, sp.tile_runs.p);
+        hipLaunchKernelGGL(seg_plan_kernel, dim3(grid_for((uint64_t)n * 64u, 256, cap)), dim3(256), 0, ctx->stream, reads->d_len.p, n, G, K, hpc ? 1 : 0,
+                           sp.tile_off.p, sp.view_off.p, sp.tile_runs.p, sp.tile_excl.p, sp.views.p, sp.skip.p, sp.read_cut.p, sp.totals.p);
+    }
+    MDBG_HIP_CHECK(ctx, hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    hipError_t e;
+    if ((e = hipMemcpyAsync(&h[0], sp.totals.p, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&h[1], sp.view_off.p + n, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(&h[2], sp.tile_off.p + n, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess)
+        return set_error(ctx, MDBG_EHIP, "scan: the plan of the long reads' segments failed: %s", hipGetErrorString(e));
+    sp.n_cut = h[0]; sp.n_views = h[1]; sp.n_tiles = h[2];
+    if (sp.n_views > max_views || sp.n_tiles > max_tiles || sp.n_views > 0xFFFFFFFFull) return set_error(ctx, MDBG_EHIP, "scan: inconsistent segment plan");
+    return MDBG_OK;
+}
+
 extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan_params *p, mdbg_minimizers **out) try {
     if (!ctx || !reads || !p || !out) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: null argument");
     if (p->quality_window != 0 && p->quality_window != 1) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: quality_window must be 0 or 1");
@@ -1946,6 +2167,7 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
     MDBG_HIP_CHECK(ctx, reads_ready_on(ctx, reads));        // an upload still in flight (mdbg_reads_from_packed_async): ordered on the device
     const uint32_t n = reads->n_reads;
     const bool hpc = p->hpc != 0, has_q = reads->has_qual && !p->ignore_qualities, has_n = reads->has_invalid;
+    ctx->scan_info[7] = 0;
     mdbg_minimizers *m = new mdbg_minimizers();
     m->n_reads = n;
     m->from_scan = true;
@@ -2074,15 +2296,39 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
     // kernel skips those reads (ScanArgs::skip) and they alone are counted, placed and scanned by the general kernel below.
     const uint32_t n_masked = has_n ? reads->n_masked : 0u;
     const bool route_masked = has_n && reads->d_masked.p && (uint64_t)n_masked * 8ull <= (uint64_t)n + 128ull;
-    if (n && (!has_n || route_masked) && !no_bump && p->density < 0.2f && reads->max_len < (1u << 31) &&
-        (double)reads->n_bases / (double)n * (double)p->density * (hpc ? 0.8 : 1.0) * 1.4 + 24.0 < (double)STAGE_CAP) {
+    const bool block_path_but_length = n && (!has_n || route_masked) && !no_bump && p->density < 0.2f && reads->max_len < (1u << 31);
+    const double rows_per_base = (double)p->density * (hpc ? 0.8 : 1.0) * 1.4;
+    const bool avg_fits_stage = n && (double)reads->n_bases / (double)n * rows_per_base + 24.0 < (double)STAGE_CAP;
+    // "scan_segments": the plain reads of more than one segment are cut into views (segments_dev.hpp) -- 1: in a batch that would leave
+    // this path for its reads' length alone, and which stays if any read can be cut; 2: there and in every batch that takes this path.  Views are
+    // scanned by the candidate-hash kernels (as reads in bump mode are, but for MDBG_SCAN_NO_APPROX and thresholds near 2^64)
+    SegPlan seg;
+    const uint32_t seg_G = ctx->scan_segment_bases;
+    {
+        static const bool no_approx = getenv("MDBG_SCAN_NO_APPROX") != nullptr || getenv("MDBG_SCAN_NO_FAST") != nullptr;      // (launch_scan's own A/B switches)
+        const uint64_t thr = density_threshold(p->density);
+        const bool wanted = ctx->scan_segments == 2u || (ctx->scan_segments == 1u && !avg_fits_stage);        // (2 includes what 1 does)
+        if (block_path_but_length && wanted && reads->max_len > seg_G && (double)seg_G * rows_per_base + 24.0 < (double)STAGE_CAP && !no_approx &&
+            (thr >> 32) + 3ull + (uint64_t)ctx->scan_cand_slack < 0xFFFFFFFFull) {
+            if ((rc = seg_prepass(ctx, reads, route_masked ? reads->d_masked.p : nullptr, seg_G, p->minimizer_size, hpc, seg))) return fail(rc);
+        }
+    }
+    if (block_path_but_length && (avg_fits_stage || seg.n_cut)) {
         // the output arrays are cut into regions, each with its own cursor (reads are dealt to the waves round-robin, so the regions
         // fill evenly); small batches use one
         uint32_t n_regions = 1;
         while (n_regions < 64u && (uint64_t)n_regions * 8192ull <= n) n_regions <<= 1;
         const uint64_t region_cap = ((uint64_t)((double)reads->n_bases * (double)p->density * 1.3) + 64ull * n) / n_regions + 4096ull;
         const uint64_t capacity = region_cap * n_regions;
-        const uint64_t reserve = capacity / 16 + 65536;       // rows behind the regions for reads that outgrow the stage
+        // views write their rows to arrays of their own, cut into regions like the batch's; the join copies them behind the batch's regions,
+        // in front of the reads that outgrow a stage.  (The batch's regions above are still sized from all its bases, the cut reads' included,
+        // which no longer write there: a batch of contigs holds about three times the rows it needs -- 10 bytes a row, 0.0065 rows a base.)
+        const uint64_t seg_bases = std::min<uint64_t>(seg.n_tiles * SEG_TILE_BASES, reads->n_bases);
+        const uint64_t seg_rows = seg.n_cut ? (uint64_t)((double)seg_bases * (double)p->density * 1.3) + 64ull * seg.n_views + 4096ull : 0ull;
+        uint32_t seg_regions = 1;
+        while (seg_regions < 64u && (uint64_t)seg_regions * 8192ull <= seg.n_views) seg_regions <<= 1;
+        const uint64_t seg_region_cap = seg_rows / seg_regions + 4096ull;
+        const uint64_t reserve = capacity / 16 + 65536 + seg_rows;       // rows behind the regions for reads that outgrow the stage (and the joined reads)
         constexpr uint32_t CTL_OVER = 64, CTL_DROPPED = 65, CTL_WORDS = 66;     // u64 words: cursors, {n_over, n_suspect}, rows dropped
         DevBuf<uint32_t> d_over, d_susp;
         DevBuf<unsigned long long> d_ctl;
@@ -2115,19 +2361,71 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
         const double pf_limit_bases = ((double)PF_STAGE_CAP - 24.0) / ((double)p->density * 0.8 * 1.4);
         const uint32_t pf_len_limit = hpc && (double)reads->n_bases / (double)n < pf_limit_bases ? (uint32_t)std::min(pf_limit_bases, 4294967295.0) : 0u;
         const bool pf_split = pf_len_limit && reads->max_len >= pf_len_limit;
-        a.skip = route_masked ? reads->d_masked.p : nullptr;
-        unsigned long long h_ctl[CTL_WORDS];
+        a.skip = seg.n_cut ? seg.skip.p : (route_masked ? reads->d_masked.p : nullptr);       // (the plan's flags: masked or cut)
+        DevBuf<uint32_t> sv_min, sv_pos, sv_cnt, sv_over;
+        DevBuf<uint8_t> sv_dir, sv_mq, sv_flags, sv_bad;
+        DevBuf<uint64_t> sv_begin, sv_row_off;
+        DevBuf<unsigned long long> sv_cx, sv_ctl;
+        constexpr uint32_t SCTL_WORDS = 66;          // the views' cursors and [64] = {views listed, -}
+        const uint32_t nv = (uint32_t)seg.n_views;
+        if (seg.n_cut) {
+            const uint64_t ext = seg_region_cap * seg_regions;
+            if ((rc = sv_min.alloc(ctx, ext)) || (rc = sv_pos.alloc(ctx, ext)) || (rc = sv_dir.alloc(ctx, ext)) || (rc = sv_mq.alloc(ctx, has_q ? ext : 1)) ||
+                (rc = sv_cnt.alloc(ctx, nv)) || (rc = sv_over.alloc(ctx, nv)) || (rc = sv_flags.alloc(ctx, nv)) || (rc = sv_bad.alloc(ctx, nv)) ||
+                (rc = sv_begin.alloc(ctx, nv)) || (rc = sv_row_off.alloc(ctx, (size_t)nv + 1)) || (rc = sv_cx.alloc(ctx, nv)) || (rc = sv_ctl.alloc(ctx, SCTL_WORDS)))
+                return fail(rc);
+            if ((e = hipMemsetAsync(sv_ctl.p, 0, SCTL_WORDS * 8, ctx->stream)) != hipSuccess || (e = hipMemsetAsync(sv_bad.p, 0, nv, ctx->stream)) != hipSuccess)
+                return fail(set_error(ctx, MDBG_EHIP, "scan: clearing the views' counters failed: %s", hipGetErrorString(e)));
+        }
+        unsigned long long h_ctl[CTL_WORDS], h_sctl[SCTL_WORDS] = {0}, h_seg[8] = {0}, h_join_rows = 0;
         {
             ScanTurn scan_turn(ctx->device);      // one scan kernel at a time per device (see below)
             if (!scans_may_interleave()) scan_turn.lock();
-            if ((rc = launch_scan(ctx, a, hpc, has_q, false, n, pf_len_limit, pf_split, reads->n_bases))) return fail(rc);
+            // (a batch all of whose reads are cut or masked -- contigs -- has nothing for its own launch: the join and the masked pass below
+            // set those reads' begin, count and flags)
+            const bool nothing_left = seg.n_cut && seg.n_cut + (route_masked ? (uint64_t)n_masked : 0ull) >= n;
+            if (!nothing_left && (rc = launch_scan(ctx, a, hpc, has_q, false, n, pf_len_limit, pf_split, reads->n_bases))) return fail(rc);
+            if (seg.n_cut) {
+                // the views, in one launch of the variant a batch of reads of segment length would take; then the join
+                ScanArgs v = a;
+                v.views = seg.views.p; v.view_cx = sv_cx.p; v.seg_tiles = seg_G / SEG_TILE_BASES;
+                v.out_min = sv_min.p; v.out_pos = sv_pos.p; v.out_dir = sv_dir.p; v.out_mqual = sv_mq.p;
+                v.out_count = sv_cnt.p; v.out_flags = sv_flags.p; v.out_begin = sv_begin.p;
+                v.cursor = sv_ctl.p; v.n_regions = seg_regions; v.out_capacity = seg_region_cap;
+                v.over_list = sv_over.p; v.suspect_list = nullptr; v.list_counters = (uint32_t *)(sv_ctl.p + 64);
+                v.skip = nullptr;
+                const uint32_t seg_pf_limit = hpc && (double)seg_G < pf_limit_bases ? (uint32_t)std::min(pf_limit_bases, 4294967295.0) : 0u;
+                if ((rc = launch_scan(ctx, v, hpc, has_q, false, nv, seg_pf_limit, false, 0, true))) return fail(rc);
+                if ((rc = exclusive_scan_u32(ctx, sv_cnt.p, sv_row_off.p, nv))) return fail(rc);
+                {
+                    LaunchTimer timer(ctx, "scan_segments");
+                    const unsigned cap_blocks = (unsigned)ctx->n_cu * 16u;
+                    hipLaunchKernelGGL(seg_mark_views_kernel, dim3(grid_for(nv, 256, cap_blocks)), dim3(256), 0, ctx->stream, sv_over.p, (const uint32_t *)(sv_ctl.p + 64), nv, sv_bad.p);
+                    hipLaunchKernelGGL(seg_join_reads_kernel, dim3(grid_for((uint64_t)n * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, a, n, seg.view_off.p,
+                                       sv_row_off.p, sv_bad.p, sv_cx.p, seg.read_cut.p, capacity, seg_rows, seg.totals.p);
+                    hipLaunchKernelGGL(seg_join_rows_kernel, dim3(grid_for((uint64_t)nv * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, seg.views.p, nv, seg.read_cut.p,
+                                       sv_row_off.p, sv_begin.p, sv_cnt.p, seg_region_cap * seg_regions, sv_min.p, sv_pos.p, sv_dir.p, sv_mq.p, has_q ? 1 : 0,
+                                       m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p, capacity, seg_rows);
+                }
+                if ((e = hipGetLastError()) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan: the join of the views failed: %s", hipGetErrorString(e)));
+            }
             if ((rc = quality_finish())) return fail(rc);          // host work while the kernel runs
             e = memcpy_sync(ctx, h_ctl, d_ctl.p, CTL_WORDS * 8, hipMemcpyDeviceToHost);
+            if (e == hipSuccess && seg.n_cut) {
+                if ((e = memcpy_sync(ctx, h_sctl, sv_ctl.p, SCTL_WORDS * 8, hipMemcpyDeviceToHost)) == hipSuccess &&
+                    (e = memcpy_sync(ctx, h_seg, seg.totals.p, 64, hipMemcpyDeviceToHost)) == hipSuccess)
+                    e = memcpy_sync(ctx, &h_join_rows, sv_row_off.p + nv, 8, hipMemcpyDeviceToHost);
+            }
         }
         if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan counters copy failed: %s", hipGetErrorString(e)));
         uint64_t rows = 0;
         bool fits = true;
         for (uint32_t g = 0; g < n_regions; g++) { rows += h_ctl[g]; fits = fits && h_ctl[g] <= region_cap; }
+        if (seg.n_cut) {          // the views' rows fitted their regions and the joined reads their room; the rows of the reads joined
+            for (uint32_t g = 0; g < seg_regions; g++) fits = fits && h_sctl[g] <= seg_region_cap;
+            fits = fits && h_seg[4] == 0ull && h_join_rows <= seg_rows;
+            rows += h_seg[2];
+        }
         const uint32_t n_over = (uint32_t)h_ctl[CTL_OVER];
         uint32_t n_suspect = (uint32_t)(h_ctl[CTL_OVER] >> 32);
         // ---- reads the block kernel did not finish: those that outgrew its stage (long reads; listed with their exact counts) and
@@ -2183,7 +2481,7 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
             std::sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.read < y.read; });
             std::vector<uint32_t> slist[2], scnt[2];
             std::vector<uint64_t> sstart[2];
-            uint64_t at = capacity;
+            uint64_t at = capacity + h_join_rows;       // (behind the joined reads)
             for (const Item &it : items) { slist[it.kind].push_back(it.read); scnt[it.kind].push_back(it.cnt); sstart[it.kind].push_back(at); at += it.cnt; }
             if (at - capacity <= reserve) {
                 DevBuf<uint32_t> scratch_count;
@@ -2215,7 +2513,7 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
                     if ((rc = launch_scan(ctx, b, hpc, has_q, kind == 1, nk))) return fail(rc);
                 }
                 if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "overflow re-run failed: %s", hipGetErrorString(e)));
-                rows += at - capacity;
+                rows += at - capacity - h_join_rows;
                 placed = true;
             }
         }
@@ -2245,6 +2543,7 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
             m->n_rows = capacity + reserve;        // extent of the row arrays (regions are not filled to the brim)
             m->n_min = rows - dropped;
             if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan failed: %s", hipGetErrorString(e)));
+            ctx->scan_info[7] = h_seg[3];
             *out = m;
             return MDBG_OK;
         }
