@@ -70,7 +70,8 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *   "pool_cache_percent"    the context keeps freed device blocks for reuse up to this share of the device memory (default 55:
  *                           several contexts share a device; a context that has the device to itself may take 90)
  *   "pool_trim"             any value: the blocks kept for reuse are given back to the device now
- *   "scan_reads_per_wave"   reads a scan wave processes before it retires (default 2)
+ *   "scan_reads_per_wave"   reads a scan wave processes before it retires; 0 (the default) = each kernel's own: 2, and for the pre-filtered
+ *                           variant up to 32 by the batch's size (a workgroup's set-up is paid once per chunk of 16 x that many reads)
  *   "scan_candidate_slack"  tests only: the block-structured scan records candidate positions by the upper half of the
  *                           hash and confirms each with the full hash; a read with a false candidate is re-run.  False
  *                           candidates occur about once in 2^31 positions; this widens the test (units of 2^32 of the
@@ -337,8 +338,23 @@ int  mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]);
  * scan (a block only runs beside a scan if it fits what the scan's blocks leave of a CU) "partition_tile" 2048,
  * "partition_slot_list" 0 and "partition_lds_slots" 1024 select the kernels' 24 KB forms and "scan_lds_reserve" (bytes) makes
  * the scan leave that much of every CU's LDS free; for tests "partition_bits", "partition_lds_slots" (256 / 1024 / 2048),
- * "partition_max_records" (instances per group).  mdbg_shard_begin counts a rank's share the same way. */
+ * "partition_max_records" (instances per group).  mdbg_shard_begin counts a rank's share the same way.
+ * "partition_threads" (MDBG_PARTITION_THREADS sets the default of new contexts) chooses the threads per block of the radix split's
+ * kernels: 0 (the default) or 512 = eight waves, tiles of 4096 records (2048 under "partition_tile" 2048); 256 = four waves, one per
+ * SIMD, tiles of 1024 records, at most 72 vector registers and 15 KB of LDS -- within the 96 registers per lane that another context's
+ * 16-wave scan workgroup leaves of a SIMD, which the eight-wave forms are not.  Beside that scan the four-wave forms measured SLOWER and
+ * the scan no faster, so they are opt-in: for that comparison and for tests.  Results never depend on it.
+ * mdbg_first_pass_form tells which form the context's last split kernels took: form[0] = threads per block, [1] = records per tile,
+ * [2] and [3] = 0. */
 int  mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]);
+int  mdbg_first_pass_form(const mdbg_ctx *ctx, uint64_t form[4]);
+/* The kernels of the headline step (scan, purge, first pass) by name, and what the runtime knows of each in the loaded code object
+ * (hipFuncGetAttributes): what a kernel of one context needs of a compute unit -- registers, wave slots, LDS -- against what another
+ * context's scan workgroup leaves of it.  mdbg_step_kernel_name(i) = the i-th name, NULL past the last.  attr[0] = vector registers per lane, [1] = bytes
+ * of static LDS per block, [2] = the most threads a block may have, [3] = threads per block as the library launches it, [4] = 0 for the
+ * 16-wave scan itself / 1 for a kernel that a context sharing its device launches / 2 for a form such a context does not take by itself, [5] = bytes of scratch per thread, [6], [7] = 0.  MDBG_EINVAL for an unknown name. */
+const char *mdbg_step_kernel_name(uint32_t index);
+int  mdbg_kernel_attributes(mdbg_ctx *ctx, const char *kernel, uint64_t attr[8]);
 /* Which block-structured scan kernels the context has launched (mdbg_scan; "scan_prefilter" above): info[0] = launches of the pre-filtered
  * variant, [1] = launches of the four-wave block kernels, [2] = selected-key bitmaps built, [3] = bits set in the last one, [4] = log2 of
  * its size in bits, [5] = waves per workgroup of the last pre-filtered launch (16, or 8 under a large "scan_lds_reserve"), [6] = 1 when

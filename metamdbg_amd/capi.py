@@ -88,6 +88,9 @@ SIGNATURES = {
     "mdbg_table_stats": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_info": (C.c_int, [_P, _u64p]),
     "mdbg_scan_info": (C.c_int, [_P, _u64p]),
+    "mdbg_first_pass_form": (C.c_int, [_P, _u64p]),
+    "mdbg_step_kernel_name": (C.c_char_p, [C.c_uint32]),
+    "mdbg_kernel_attributes": (C.c_int, [_P, C.c_char_p, _u64p]),
     "mdbg_stream_spin": (C.c_int, [_P, C.c_uint32]),
     "mdbg_minimizers_slice": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "mdbg_shard_exchange_local": (C.c_int, [_P, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), _u64p, C.POINTER(C.c_void_p)]),
@@ -201,6 +204,28 @@ class Context:
         a = (C.c_uint64 * 8)()
         self.check(lib().mdbg_first_pass_info(self.h, a))
         names = ("path", "groups", "bucket_bits", "levels", "attempts", "lds_slots", "buckets", "instances")
+        return {k: int(v) for k, v in zip(names, a)}
+
+    def first_pass_form(self) -> dict:
+        """Which form the split kernels this context last launched took (mdbg_first_pass_form)."""
+        a = (C.c_uint64 * 4)()
+        self.check(lib().mdbg_first_pass_form(self.h, a))
+        return {"split_threads": int(a[0]), "split_tile": int(a[1])}
+
+    @staticmethod
+    def step_kernel_names() -> list[str]:
+        """The kernels of the headline step that mdbg_kernel_attributes knows (mdbg_step_kernel_name)."""
+        names, i = [], 0
+        while (name := lib().mdbg_step_kernel_name(i)) is not None:
+            names.append(name.decode())
+            i += 1
+        return names
+
+    def kernel_attributes(self, kernel: str) -> dict:
+        """Registers, LDS and threads of one kernel of the step in the loaded code object (mdbg_kernel_attributes)."""
+        a = (C.c_uint64 * 8)()
+        self.check(lib().mdbg_kernel_attributes(self.h, kernel.encode(), a))
+        names = ("registers", "static_lds", "max_threads", "threads", "role", "scratch")
         return {k: int(v) for k, v in zip(names, a)}
 
     def scan_info(self) -> dict:

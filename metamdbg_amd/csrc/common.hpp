@@ -140,7 +140,8 @@ struct mdbg_ctx {
     std::map<std::string, std::pair<double, uint64_t>> timers;  // name -> (ms, launches)
     unsigned table_grid_blocks = 0;                        // > 0: the absolute grid of those kernels (fewer blocks than CUs: beside a scan, mdbg_set_option)
     unsigned table_blocks_per_cu = 1024;                   // resident blocks per CU of the kernels that walk every k-min-mer instance (mdbg_set_option)
-    unsigned scan_reads_per_wave = 2;                      // reads a scan wave processes before it retires (mdbg_set_option)
+    unsigned scan_reads_per_wave = 0;                      // reads a scan wave processes before it retires (mdbg_set_option); 0 = each kernel's own: 2 for the
+                                                           // four-wave and the general kernels, up to 32 by the batch's size for the pre-filtered variant (scan.hip)
     uint32_t scan_wave_priority = 0;        // s_setprio level of the block-structured scan's waves (mdbg_set_option)
     int test_exchange_fail_phase = 0;       // tests: this rank fails in phase 1 (before the counts) / 2 (buffers) / 3 (reduction) of the next exchange
     bool test_corrupt_replies = false;      // tests: the next exchange hands back one reply with a wrong count (the job's self-check must see it)
@@ -172,6 +173,9 @@ struct mdbg_ctx {
     uint32_t part_lds_slots = 0;            // 0: 1024 or 2048 by the key hint; 256 / 1024 / 2048: forced (tests)
     uint64_t part_max_records = 0;          // > 0: instances per group of keys (tests; default: a quarter of the HBM)
     uint32_t part_tile = 0;                 // 2048: the scatter regroups tiles of 2048 records (24 KB of LDS instead of 43), else 4096
+    uint32_t part_threads = 0;              // threads per block of the split kernels: 0 or 512 = eight waves; 256 = four waves, tiles of 1024 records (fits beside a
+                                            // 16-wave scan workgroup by registers, measured slower there: DESIGN.md 4.4; for that comparison and for tests)
+    uint64_t part_form[4] = {0};            // mdbg_first_pass_form: [0] threads per block, [1] records per tile of the split kernels last launched
     uint32_t part_slot_list = 1;            // 0: bucket_count keeps no slot list (24 KB of LDS per 1024-slot bucket instead of 40)
     uint32_t scan_lds_pad = 0;              // bytes of unused dynamic LDS per block of the block-structured scan: caps its blocks per CU and so
                                             // leaves LDS, registers and wave slots to other contexts' kernels (mdbg_set_option)
@@ -194,6 +198,15 @@ struct mdbg_ctx {
 };
 
 namespace mdbg {
+
+// A kernel of the headline step by name (mdbg_kernel_attributes): every source file lists its own.  role 0: the 16-wave scan the others
+// run beside; 1: launched by a context that shares its device, beside that scan (what each needs of a compute unit against what the scan
+// leaves: DESIGN.md 4.4); 2: a form such a context does not take by itself.
+struct StepKernel { const char *name; const void *fn; uint32_t threads, role; };
+const StepKernel *partition_step_kernels(uint32_t *n);
+const StepKernel *minimizers_step_kernels(uint32_t *n);
+const StepKernel *prims_step_kernels(uint32_t *n);
+const StepKernel *scan_step_kernels(uint32_t *n);
 
 int set_error(mdbg_ctx *ctx, int code, const char *fmt, ...);
 extern thread_local std::string g_last_error;  // for failures before a context exists (per calling thread)

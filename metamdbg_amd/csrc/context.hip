@@ -70,6 +70,7 @@ extern "C" int mdbg_create(int device, mdbg_ctx **out) try {
     if (const char *e = getenv("MDBG_SCAN_SEGMENTS")) ctx->scan_segments = atoi(e) == 0 ? 0u : (atoi(e) == 2 ? 2u : 1u);
     if (const char *e = getenv("MDBG_SCAN_LDS_PAD")) ctx->scan_lds_pad = (uint32_t)std::max(0, std::min(32768, atoi(e)));
     if (const char *e = getenv("MDBG_PARTITION_TILE")) ctx->part_tile = atoi(e) == 2048 ? 2048u : 0u;
+    if (const char *e = getenv("MDBG_PARTITION_THREADS")) ctx->part_threads = atoi(e) == 256 ? 256u : (atoi(e) == 512 ? 512u : 0u);
     if (const char *e = getenv("MDBG_PARTITION_SLOT_LIST")) ctx->part_slot_list = atoi(e) != 0;
     if (const char *e = getenv("MDBG_FIRST_PASS_MODE")) ctx->first_pass_mode = std::max(0, std::min(2, atoi(e)));
     ctx->hbm_bytes = prop.totalGlobalMem;
@@ -199,7 +200,7 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
         if (value != 0 && (value < 10 || value > 19)) return set_error(ctx, MDBG_EINVAL, "scan_prefilter_log2_bits: 0 (the kernel's own) or 10 .. 19");
         ctx->scan_prefilter_log2_bits = (uint32_t)value; return MDBG_OK;
     }
-    if (n == "scan_reads_per_wave") { ctx->scan_reads_per_wave = value > 0 ? (unsigned)std::min<int64_t>(value, 1 << 20) : 2u; return MDBG_OK; }
+    if (n == "scan_reads_per_wave") { ctx->scan_reads_per_wave = value > 0 ? (unsigned)std::min<int64_t>(value, 1 << 20) : 0u; return MDBG_OK; }
     if (n == "first_pass_mode") { ctx->first_pass_mode = (int)std::max<int64_t>(0, std::min<int64_t>(2, value)); return MDBG_OK; }
     if (n == "partition_auto_min") { ctx->part_auto_min = value > 0 ? (uint64_t)value : (1ull << 17); return MDBG_OK; }
     if (n == "partition_bits") { ctx->part_bits = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(24, value)); return MDBG_OK; }
@@ -208,6 +209,10 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
         ctx->part_lds_slots = (uint32_t)value; return MDBG_OK;
     }
     if (n == "partition_tile") { ctx->part_tile = value == 2048 ? 2048u : 0u; return MDBG_OK; }
+    if (n == "partition_threads") {
+        if (value != 0 && value != 256 && value != 512) return set_error(ctx, MDBG_EINVAL, "partition_threads: 0 (the default: 512), 256 or 512");
+        ctx->part_threads = (uint32_t)value; return MDBG_OK;
+    }
     if (n == "partition_slot_list") { ctx->part_slot_list = value != 0; return MDBG_OK; }
     if (n == "scan_lds_reserve") { ctx->scan_lds_reserve = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(131072, value)); return MDBG_OK; }
     if (n == "scan_lds_pad") { ctx->scan_lds_pad = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(32768, value)); return MDBG_OK; }

@@ -825,3 +825,16 @@ extern "C" int mdbg_repetitive_minimizers(mdbg_ctx *ctx, const mdbg_minimizers *
     MDBG_TRY(mdbg_census_add(ctx, &c, m));
     return mdbg_census_top(ctx, &c, out, n_out);
 } MDBG_API_CATCH(ctx)
+
+namespace mdbg {
+const StepKernel *minimizers_step_kernels(uint32_t *n) {
+    static const StepKernel k[] = {
+        {"purge_detect", reinterpret_cast<const void *>(purge_detect_kernel), 256, 1},
+        {"purge_fix", reinterpret_cast<const void *>(purge_fix_kernel), PURGE_FIX_THREADS, 1},
+        {"gather_prefix", reinterpret_cast<const void *>(gather_prefix_kernel), 256, 1},
+        {"gather_rows", reinterpret_cast<const void *>(gather_rows_kernel), 256, 1},
+    };
+    *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
+    return k;
+}
+}  // namespace mdbg

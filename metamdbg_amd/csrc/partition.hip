@@ -45,6 +45,15 @@ constexpr uint32_t PART_NT = MDBG_PART_NT;             // threads per block of t
 constexpr uint32_t PART_E = MDBG_PART_E;               // records per thread and tile
 constexpr uint32_t PART_TILE = PART_NT * PART_E;       // 4096 records regrouped in LDS at a time
 constexpr uint32_t PART_MAXW = 256;                    // ways per level
+// The small forms ("partition_threads" 256, opt-in): four waves a block, one per SIMD, and 4 records per thread -- at most 72 vector
+// registers and 15 KB of LDS, which is within what the 16-wave scan of another context leaves of a compute unit by every count (416 of a
+// SIMD's 512 registers per lane are the scan's; a 512-thread block needs two waves per SIMD).  Measured beside that scan they LOSE to the
+// eight-wave forms -- the scatter 7.0 against 6.0 ms a call, the step 1 % slower, the scan's launch no shorter (DESIGN.md 4.4,
+// profiles/split_residency_bench_alternating.txt) -- so no context takes them by itself; they stay for that comparison.
+constexpr uint32_t PART_NT_SMALL = 256;
+constexpr uint32_t PART_E_SMALL = 4;
+constexpr uint32_t PART_TILE_SMALL = PART_NT_SMALL * PART_E_SMALL;
+static_assert(PART_NT_SMALL >= PART_MAXW && PART_NT >= PART_MAXW, "the scatter scans a tile's histogram with one thread per way");
 // bucket_count remembers the LDS slot of a bucket's first records between its two passes: 8000 of them beside 1024 slots (not 8192:
 // four such buckets then fit a CU's 160 KB), 4096 beside 2048 (the 64 KB of static LDS), none when the kernel is to fit beside a scan
 constexpr uint32_t PART_MAX_K = 32;                    // window validity is one 64-bit extract of the start bits
@@ -135,23 +144,23 @@ __device__ __forceinline__ void split_range(const SplitArgs &a, uint32_t &seg, u
 
 // hist[(seg * ways + digit) * blocks_per_seg + j]: scanned in this order the table is every (block, digit)'s first output place,
 // and entry (seg * ways + digit) * blocks_per_seg the start of bucket seg * ways + digit
-template <bool FROM_MINS>
-__global__ __launch_bounds__(PART_NT) void split_hist_kernel(SplitArgs a, uint32_t *hist) {
+template <bool FROM_MINS, uint32_t NT>
+__global__ __launch_bounds__(NT) void split_hist_kernel(SplitArgs a, uint32_t *hist) {
     __shared__ uint32_t h[PART_MAXW];
     __shared__ uint32_t sketch[FROM_MINS ? HLL_M : 1];
     const bool sketching = FROM_MINS && a.hll != nullptr;
-    for (uint32_t t = threadIdx.x; t < a.ways; t += PART_NT) h[t] = 0;
-    if (sketching) for (uint32_t t = threadIdx.x; t < HLL_M; t += PART_NT) sketch[t] = 0;
+    for (uint32_t t = threadIdx.x; t < a.ways; t += NT) h[t] = 0;
+    if (sketching) for (uint32_t t = threadIdx.x; t < HLL_M; t += NT) sketch[t] = 0;
     __syncthreads();
     uint32_t seg, j; uint64_t b, e;
     split_range(a, seg, j, b, e);
     // PART_E records of a thread in flight at a time: one position per trip left the loads of its window (or of its record) waiting
     // for each other, 1.7 ms for a pass whose hashing is 0.7 ms of vector instructions
-    for (uint64_t t0 = b; t0 < e; t0 += PART_TILE) {
+    for (uint64_t t0 = b; t0 < e; t0 += NT * PART_E) {
         uint32_t digit[PART_E];
 #pragma unroll
         for (uint32_t q = 0; q < PART_E; q++) {
-            const uint64_t i = t0 + (uint64_t)q * PART_NT + threadIdx.x;
+            const uint64_t i = t0 + (uint64_t)q * NT + threadIdx.x;
             digit[q] = 0xFFFFFFFFu;
             if (i < e) {
                 uint64_t lo, hi;
@@ -175,8 +184,8 @@ __global__ __launch_bounds__(PART_NT) void split_hist_kernel(SplitArgs a, uint32
         for (uint32_t q = 0; q < PART_E; q++) if (digit[q] != 0xFFFFFFFFu) atomicAdd(&h[digit[q]], 1u);
     }
     __syncthreads();
-    for (uint32_t t = threadIdx.x; t < a.ways; t += PART_NT) hist[((uint64_t)seg * a.ways + t) * a.blocks_per_seg + j] = h[t];
-    if (sketching) for (uint32_t t = threadIdx.x; t < HLL_M; t += PART_NT) a.hll[(uint64_t)blockIdx.x * HLL_M + t] = (uint8_t)sketch[t];
+    for (uint32_t t = threadIdx.x; t < a.ways; t += NT) hist[((uint64_t)seg * a.ways + t) * a.blocks_per_seg + j] = h[t];
+    if (sketching) for (uint32_t t = threadIdx.x; t < HLL_M; t += NT) a.hll[(uint64_t)blockIdx.x * HLL_M + t] = (uint8_t)sketch[t];
 }
 
 // (64 slices of the blocks per register, merged by atomic max: one thread per register walking all 2048 blocks took 0.8 ms)
@@ -190,9 +199,9 @@ __global__ __launch_bounds__(256) void hll_merge_kernel(const uint8_t *per_block
 
 // E records per thread and tile: 8 (tiles of 4096: runs of 16 records per digit and tile at 256 ways) when the kernel has the device to
 // itself, 4 (24 KB of LDS instead of 43) when it is to fit beside another context's scan blocks (mdbg_set_option "partition_tile")
-template <bool FROM_MINS, uint32_t E>
-__global__ __launch_bounds__(PART_NT) void split_scatter_kernel(SplitArgs a, const uint64_t *place, RecView out) {
-    constexpr uint32_t TILE = PART_NT * E;
+template <bool FROM_MINS, uint32_t E, uint32_t NT>
+__global__ __launch_bounds__(NT) void split_scatter_kernel(SplitArgs a, const uint64_t *place, RecView out) {
+    constexpr uint32_t TILE = NT * E;
     __shared__ unsigned long long stage[TILE];         // one field of the tile's records at a time, grouped by digit
     __shared__ uint8_t stage_digit[TILE];
     __shared__ uint32_t h[PART_MAXW], wsum[4];
@@ -201,7 +210,7 @@ __global__ __launch_bounds__(PART_NT) void split_scatter_kernel(SplitArgs a, con
     uint32_t seg, j; uint64_t b, e;
     split_range(a, seg, j, b, e);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t t = tid; t < PART_MAXW; t += PART_NT) {
+    for (uint32_t t = tid; t < PART_MAXW; t += NT) {
         h[t] = 0;
         cur[t] = t < a.ways ? place[((uint64_t)seg * a.ways + t) * a.blocks_per_seg + j] : 0ull;
     }
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(PART_NT) void split_scatter_kernel(SplitArgs a, con
         uint32_t rep[E], meta[E];            // digit | rank << 8 | valid << 31
 #pragma unroll
         for (uint32_t q = 0; q < E; q++) {
-            const uint64_t i = t0 + (uint64_t)q * PART_NT + tid;
+            const uint64_t i = t0 + (uint64_t)q * NT + tid;
             bool valid = i < e;
             if (valid) {
                 if (FROM_MINS) { valid = window_at(a, i, hi[q], lo[q]) && in_group(a, lo[q]); rep[q] = (uint32_t)i; }
@@ -253,22 +262,22 @@ __global__ __launch_bounds__(PART_NT) void split_scatter_kernel(SplitArgs a, con
         }
         __syncthreads();
 #if !defined(MDBG_PART_ABLATE)
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.lo[gbase[stage_digit[s]] + s] = stage[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) out.lo[gbase[stage_digit[s]] + s] = stage[s];
 #elif MDBG_PART_ABLATE == 1
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) if (stage[s] == 0x123456789ull) out.lo[gbase[stage_digit[s]] + s] = stage[s];   // ablation: LDS work, no stores
+        for (uint32_t s = tid; s < n_tile; s += NT) if (stage[s] == 0x123456789ull) out.lo[gbase[stage_digit[s]] + s] = stage[s];   // ablation: LDS work, no stores
 #elif MDBG_PART_ABLATE == 3
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.lo[t0 - b + (place[0] & 1) + s] = stage[s];                                // ablation: stores in input order
+        for (uint32_t s = tid; s < n_tile; s += NT) out.lo[t0 - b + (place[0] & 1) + s] = stage[s];                                // ablation: stores in input order
 #endif
         __syncthreads();
 #pragma unroll
         for (uint32_t q = 0; q < E; q++) if (dst[q] != 0xFFFFFFFFu) stage[dst[q]] = hi[q];
         __syncthreads();
 #if !defined(MDBG_PART_ABLATE)
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.hi[gbase[stage_digit[s]] + s] = stage[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) out.hi[gbase[stage_digit[s]] + s] = stage[s];
 #elif MDBG_PART_ABLATE == 1
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) if (stage[s] == 0x123456789ull) out.hi[gbase[stage_digit[s]] + s] = stage[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) if (stage[s] == 0x123456789ull) out.hi[gbase[stage_digit[s]] + s] = stage[s];
 #elif MDBG_PART_ABLATE == 3
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.hi[t0 - b + (place[0] & 1) + s] = stage[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) out.hi[t0 - b + (place[0] & 1) + s] = stage[s];
 #endif
         __syncthreads();
         uint32_t *stage32 = reinterpret_cast<uint32_t *>(stage);
@@ -276,11 +285,11 @@ __global__ __launch_bounds__(PART_NT) void split_scatter_kernel(SplitArgs a, con
         for (uint32_t q = 0; q < E; q++) if (dst[q] != 0xFFFFFFFFu) stage32[dst[q]] = rep[q];
         __syncthreads();
 #if !defined(MDBG_PART_ABLATE)
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.rep[gbase[stage_digit[s]] + s] = stage32[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) out.rep[gbase[stage_digit[s]] + s] = stage32[s];
 #elif MDBG_PART_ABLATE == 1
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) if (stage32[s] == 0x12345678u) out.rep[gbase[stage_digit[s]] + s] = stage32[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) if (stage32[s] == 0x12345678u) out.rep[gbase[stage_digit[s]] + s] = stage32[s];
 #elif MDBG_PART_ABLATE == 3
-        for (uint32_t s = tid; s < n_tile; s += PART_NT) out.rep[t0 - b + (place[0] & 1) + s] = stage32[s];
+        for (uint32_t s = tid; s < n_tile; s += NT) out.rep[t0 - b + (place[0] & 1) + s] = stage32[s];
 #endif
         __syncthreads();
     }
@@ -659,6 +668,40 @@ struct RecBufs {
     RecView view() { return RecView{lo.p, hi.p, rep.p}; }
 };
 
+// Which form of the split kernels a context takes: threads per block and records per tile.  "partition_threads" 256 takes the four-wave
+// forms; 0 and 512 the eight-wave ones, whose tile "partition_tile" chooses as before.
+struct SplitForm { uint32_t threads, tile; };
+
+static SplitForm split_form(const mdbg_ctx *ctx) {
+    if (ctx->part_threads == PART_NT_SMALL) return SplitForm{PART_NT_SMALL, PART_TILE_SMALL};
+    return SplitForm{PART_NT, ctx->part_tile == 2048 ? PART_TILE / 2 : PART_TILE};
+}
+
+static void launch_split_hist(mdbg_ctx *ctx, bool from_mins, SplitForm f, unsigned grid, const SplitArgs &a, uint32_t *hist) {
+    if (f.threads == PART_NT_SMALL && PART_NT_SMALL != PART_NT) {
+        if (from_mins) hipLaunchKernelGGL((split_hist_kernel<true, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, hist);
+        else hipLaunchKernelGGL((split_hist_kernel<false, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, hist);
+    } else {
+        if (from_mins) hipLaunchKernelGGL((split_hist_kernel<true, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, hist);
+        else hipLaunchKernelGGL((split_hist_kernel<false, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, hist);
+    }
+    ctx->part_form[0] = f.threads; ctx->part_form[1] = f.tile;
+}
+
+static void launch_split_scatter(mdbg_ctx *ctx, bool from_mins, SplitForm f, unsigned grid, const SplitArgs &a, const uint64_t *place, RecView out) {
+    if (f.tile == PART_TILE_SMALL && f.threads == PART_NT_SMALL) {
+        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E_SMALL, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, place, out);
+        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E_SMALL, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, place, out);
+    } else if (f.tile != PART_TILE) {
+        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E / 2, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
+        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E / 2, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
+    } else {
+        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
+        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
+    }
+    ctx->part_form[0] = f.threads; ctx->part_form[1] = f.tile;
+}
+
 struct LevelPlan { uint32_t bits, shift, ways, blocks_per_seg; uint64_t n_seg; };
 
 template <uint32_t C, uint32_t LIST>
@@ -702,6 +745,7 @@ struct PartRun {
     // for small inputs: from 2^8 buckets up level 1 always takes 8 bits, so the histogram is not run twice.
     uint64_t I_est = 0, n_groups = 1;
     uint32_t group_bits = 0, lds_slots = 0, bucket_bits = 0, n_levels = 1, extra_bits = 0, tile = PART_TILE;
+    SplitForm form{PART_NT, PART_TILE};
     double keys_est = 1.0;
     bool sketched = false;
     LevelPlan lv[3];
@@ -763,7 +807,8 @@ struct PartRun {
         n_groups = 1ull << group_bits;
         keys_est = std::max(1.0, (double)I_est * ctx->key_ratio_hint[0]);
         sketched = ctx->part_bits != 0;                 // a forced plan needs no estimate
-        tile = ctx->part_tile == 2048 ? PART_TILE / 2 : PART_TILE;
+        form = split_form(ctx);
+        tile = form.tile;
         MDBG_TRY(overflow.alloc(ctx, 1));
         plan();
         return MDBG_OK;
@@ -800,7 +845,7 @@ struct PartRun {
             }
             {
                 LaunchTimer timer(ctx, "kminmer_split");
-                hipLaunchKernelGGL(split_hist_kernel<true>, dim3(lv[0].blocks_per_seg), dim3(PART_NT), 0, ctx->stream, a, hist.p);
+                launch_split_hist(ctx, true, form, lv[0].blocks_per_seg, a, hist.p);
                 if (a.hll) hipLaunchKernelGGL(hll_merge_kernel, dim3(HLL_M / 256, 64), dim3(256), 0, ctx->stream, hll_blocks.p, lv[0].blocks_per_seg, hll_merged.p);
             }
             MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[0].p, entries));
@@ -826,8 +871,7 @@ struct PartRun {
         if (kcnt.n < I || !kcnt.p) MDBG_TRY(kcnt.alloc(ctx, I));
         {
             LaunchTimer timer(ctx, "kminmer_split");
-            if (tile != PART_TILE) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E / 2>), dim3(lv[0].blocks_per_seg), dim3(PART_NT), 0, ctx->stream, a, place[0].p, buf[0].view());
-            else hipLaunchKernelGGL((split_scatter_kernel<true, PART_E>), dim3(lv[0].blocks_per_seg), dim3(PART_NT), 0, ctx->stream, a, place[0].p, buf[0].view());
+            launch_split_scatter(ctx, true, form, lv[0].blocks_per_seg, a, place[0].p, buf[0].view());
         }
         // deeper levels
         cur = 0;
@@ -845,13 +889,12 @@ struct PartRun {
             const unsigned grid = (unsigned)(n_seg * lv[l].blocks_per_seg);
             {
                 LaunchTimer timer(ctx, "kminmer_split");
-                hipLaunchKernelGGL(split_hist_kernel<false>, dim3(grid), dim3(PART_NT), 0, ctx->stream, d, hist.p);
+                launch_split_hist(ctx, false, form, grid, d, hist.p);
             }
             MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[l].p, entries));
             {
                 LaunchTimer timer(ctx, "kminmer_split");
-                if (tile != PART_TILE) hipLaunchKernelGGL((split_scatter_kernel<false, PART_E / 2>), dim3(grid), dim3(PART_NT), 0, ctx->stream, d, place[l].p, buf[cur ^ 1].view());
-                else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E>), dim3(grid), dim3(PART_NT), 0, ctx->stream, d, place[l].p, buf[cur ^ 1].view());
+                launch_split_scatter(ctx, false, form, grid, d, place[l].p, buf[cur ^ 1].view());
             }
             cur ^= 1;
         }
@@ -1158,7 +1201,8 @@ int part_owner_reduce(mdbg_ctx *ctx, const uint64_t *d_rows, uint64_t n_recv, ui
     while ((double)(1ull << bits) < (double)n_recv / (0.78 * lds_slots) && bits <= PART_MAX_BITS) bits++;
     if (bits > PART_MAX_BITS) return MDBG_OK;
     const uint32_t n_levels = bits <= 8 ? 1u : (bits + 7u) / 8u;
-    const uint32_t tile = ctx->part_tile == 2048 ? PART_TILE / 2 : PART_TILE;
+    const SplitForm form = split_form(ctx);
+    const uint32_t tile = form.tile;
     RecBufs buf[2];
     MDBG_TRY(buf[0].ensure(ctx, n_recv));
     MDBG_TRY(buf[1].ensure(ctx, n_recv));
@@ -1183,10 +1227,9 @@ int part_owner_reduce(mdbg_ctx *ctx, const uint64_t *d_rows, uint64_t n_recv, ui
         MDBG_TRY(hist.alloc(ctx, entries));
         MDBG_TRY(place[l].alloc(ctx, entries + 1));
         const unsigned grid = (unsigned)(n_seg * d.blocks_per_seg);
-        hipLaunchKernelGGL(split_hist_kernel<false>, dim3(grid), dim3(PART_NT), 0, ctx->stream, d, hist.p);
+        launch_split_hist(ctx, false, form, grid, d, hist.p);
         MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[l].p, entries));
-        if (tile != PART_TILE) hipLaunchKernelGGL((split_scatter_kernel<false, PART_E / 2>), dim3(grid), dim3(PART_NT), 0, ctx->stream, d, place[l].p, buf[cur ^ 1].view());
-        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E>), dim3(grid), dim3(PART_NT), 0, ctx->stream, d, place[l].p, buf[cur ^ 1].view());
+        launch_split_scatter(ctx, false, form, grid, d, place[l].p, buf[cur ^ 1].view());
         cur ^= 1; used += b; left -= b; n_seg <<= b; prev_bps = d.blocks_per_seg;
     }
     const uint64_t n_buckets = 1ull << bits;
@@ -1198,6 +1241,33 @@ int part_owner_reduce(mdbg_ctx *ctx, const uint64_t *d_rows, uint64_t n_recv, ui
     MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, overflow.p, 4, hipMemcpyDeviceToHost));
     *done = ov == 0;                                               // a key with a zero word, or a bucket of more keys than slots: the one-table pass takes it
     return MDBG_OK;
+}
+
+// ---- mdbg_kernel_attributes: the first pass's kernels as a context that shares its device launches them (role 1), and the other forms ----
+const StepKernel *partition_step_kernels(uint32_t *n) {
+#define MDBG_K(f) reinterpret_cast<const void *>(f)
+    static const StepKernel k[] = {
+        {"mark_starts", MDBG_K(mark_starts_kernel), 256, 1},
+        {"split_hist_mins_512", MDBG_K((split_hist_kernel<true, PART_NT>)), PART_NT, 1},
+        {"split_hist_records_512", MDBG_K((split_hist_kernel<false, PART_NT>)), PART_NT, 1},
+        {"split_scatter_mins_512_tile2048", MDBG_K((split_scatter_kernel<true, PART_E / 2, PART_NT>)), PART_NT, 1},
+        {"split_scatter_records_512_tile2048", MDBG_K((split_scatter_kernel<false, PART_E / 2, PART_NT>)), PART_NT, 1},
+        {"hll_merge", MDBG_K(hll_merge_kernel), 256, 1},
+        {"bucket_count_1024", MDBG_K((bucket_count_kernel<1024, 0>)), BC_NT, 1},
+        {"rescue_count", MDBG_K(rescue_count_p_kernel), 256, 1},
+        {"emit_bucket_rows", MDBG_K(emit_bucket_rows_kernel), 256, 1},
+        {"emit_rescued", MDBG_K(emit_rescued_p_kernel), 256, 1},
+        {"split_hist_mins_256", MDBG_K((split_hist_kernel<true, PART_NT_SMALL>)), PART_NT_SMALL, 2},
+        {"split_hist_records_256", MDBG_K((split_hist_kernel<false, PART_NT_SMALL>)), PART_NT_SMALL, 2},
+        {"split_scatter_mins_256", MDBG_K((split_scatter_kernel<true, PART_E_SMALL, PART_NT_SMALL>)), PART_NT_SMALL, 2},
+        {"split_scatter_records_256", MDBG_K((split_scatter_kernel<false, PART_E_SMALL, PART_NT_SMALL>)), PART_NT_SMALL, 2},
+        {"split_scatter_mins_512", MDBG_K((split_scatter_kernel<true, PART_E, PART_NT>)), PART_NT, 2},
+        {"split_scatter_records_512", MDBG_K((split_scatter_kernel<false, PART_E, PART_NT>)), PART_NT, 2},
+        {"bucket_count_1024_list", MDBG_K((bucket_count_kernel<1024, 8000>)), BC_NT, 2},
+    };
+#undef MDBG_K
+    *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
+    return k;
 }
 
 }  // namespace mdbg

@@ -141,4 +141,14 @@ int exclusive_scan_u32(mdbg_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, uin
     return exclusive_scan_impl<uint32_t>(ctx, d_in, d_out, n);
 }
 
+const StepKernel *prims_step_kernels(uint32_t *n) {
+    static const StepKernel k[] = {
+        {"prefix_reduce", reinterpret_cast<const void *>(scan_reduce_kernel<uint32_t>), SCAN_THREADS, 1},
+        {"prefix_small", reinterpret_cast<const void *>(scan_small_kernel), SCAN_THREADS, 1},
+        {"prefix_apply", reinterpret_cast<const void *>(scan_apply_kernel<uint32_t>), SCAN_THREADS, 1},
+    };
+    *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
+    return k;
+}
+
 }  // namespace mdbg

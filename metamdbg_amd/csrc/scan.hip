@@ -1951,6 +1951,25 @@ static int prefilter_ensure(mdbg_ctx *ctx, uint64_t threshold, unsigned log2_bit
     return MDBG_OK;
 }
 
+// "scan_reads_per_wave" left at 0: what a wave takes before its workgroup retires.  The four-wave and the general kernels keep 2 (see
+// launch_variant).  A workgroup of the pre-filtered variant copies the 64 KB bitmap, clears its rings and passes two barriers before its
+// first read, with nothing else of the scan on its CU meanwhile: at 2 reads a wave that is paid 312 500 times for 10 M reads.  Measured
+// (profiles/split_residency_reads_per_wave.txt), 10 M x 10 kb alone: 71.1 / 67.7 / 65.3 / 64.6 / 63.7 / 64.0 / 65.4 ms at 2 / 4 / 8 / 16 /
+// 32 / 64 / 128; 500 000 reads of 1 .. 25 kb: 3.94 / 3.27 / 3.00 / 2.85 / 2.79 / 2.74 / 2.71 ms.  With two batches in flight the step
+// gains more than the scan alone and keeps gaining up to 128 -- but from 64 on because the other batch's first pass is held back (its
+// kernels' time follows the life of a scan workgroup, DESIGN.md 4.4: 27 / 41 / 57 / 66 ms of first pass a step at 16 / 32 / 64 / 128 under a
+// scan launch of 82 / 80 / 78 / 77 ms), and a first pass as long as a scan launch is what the pipeline would wait for next.  32 is the
+// largest value at which it stays at half a launch.  The batch must also leave every CU PREFILTER_MIN_GROUPS_PER_CU workgroups (the 500 000
+// reads above are 1.9 a CU at 64): a small batch would otherwise leave CUs idle for the length of a workgroup.
+constexpr unsigned SCAN_READS_PER_WAVE = 2, PREFILTER_READS_PER_WAVE = 32, PREFILTER_MIN_GROUPS_PER_CU = 2;
+
+static unsigned prefilter_reads_per_wave(const mdbg_ctx *ctx, uint32_t n_items, unsigned waves) {
+    unsigned per_wave = PREFILTER_READS_PER_WAVE;
+    const uint64_t want = (uint64_t)PREFILTER_MIN_GROUPS_PER_CU * (uint64_t)std::max(ctx->n_cu, 1);
+    while (per_wave > SCAN_READS_PER_WAVE && (uint64_t)n_items / ((uint64_t)waves * per_wave) < want) per_wave /= 2;
+    return per_wave;
+}
+
 template <bool HPC, bool Q, bool N>
 static void launch_variant(mdbg_ctx *ctx, const ScanArgs &a, unsigned max_blocks, uint32_t n_items) {
     // A few reads per wave, then the wave retires.  One resident generation of persistent waves (the first design)
@@ -1961,7 +1980,7 @@ static void launch_variant(mdbg_ctx *ctx, const ScanArgs &a, unsigned max_blocks
     // to a 10 kb read.  2 reads per wave measured best with two batches in flight: a waiting kernel of the other batch gets
     // a slot within ~0.2 ms (MDBG_SCAN_READS_PER_WAVE to tune).
     (void)max_blocks;
-    const uint64_t per_wave = ctx->scan_reads_per_wave;
+    const uint64_t per_wave = ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : SCAN_READS_PER_WAVE;
     uint64_t blocks = ((uint64_t)n_items + SCAN_WAVES * per_wave - 1) / (SCAN_WAVES * per_wave);
     if (blocks < 1) blocks = 1;
     if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;
@@ -2048,7 +2067,7 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
         if (pf_split) a.skip = d_split.p;           // first the long reads, by the four-wave kernel below
         if (fast && (!pf_kernel || pf_split)) {
             // plain ACGT without qualities: the block-structured kernel; a few reads per wave, then the wave retires
-            const uint64_t per_wave = ctx->scan_reads_per_wave;
+            const uint64_t per_wave = ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : SCAN_READS_PER_WAVE;
             uint64_t blocks = ((uint64_t)n_items + FAST_WAVES * per_wave - 1) / (FAST_WAVES * per_wave);
             if (blocks < 1) blocks = 1;
             if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;
@@ -2096,7 +2115,7 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             // one workgroup of pf_waves waves per CU; it deals its chunk of reads out to its waves
             a.pf_bits = ctx->prefilter_bits;
             a.pf_shift = 32u - ctx->prefilter_log2;
-            const uint64_t chunk = std::min<uint64_t>((uint64_t)pf_waves * ctx->scan_reads_per_wave, 1u << 24);
+            const uint64_t chunk = std::min<uint64_t>((uint64_t)pf_waves * (ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : prefilter_reads_per_wave(ctx, n_items, pf_waves)), 1u << 24);
             a.pf_chunk = (uint32_t)chunk;
             const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, ((uint64_t)n_items + chunk - 1) / chunk), 0x7FFFFFFFull);
             a.pf_len_split = pf_split ? pf_len_limit : 0u;
@@ -2671,3 +2690,13 @@ extern "C" int mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]) {
     for (int i = 0; i < 8; i++) info[i] = ctx->scan_info[i];
     return MDBG_OK;
 }
+
+namespace mdbg {
+const StepKernel *scan_step_kernels(uint32_t *n) {
+    static const StepKernel k[] = {
+        {"scan_prefiltered_16", reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 16>), 1024, 0},
+    };
+    *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
+    return k;
+}
+}  // namespace mdbg
