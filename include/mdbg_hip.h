@@ -415,6 +415,30 @@ int  mdbg_minimizers_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records,
                                        uint8_t *circular, mdbg_minimizers **out);
 int  mdbg_prev_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records, uint64_t n_records, mdbg_table **out);
 
+/* ---- record files SERIALISED on the device ---------------------------------------------------------------------------------------
+ * The inverse of mdbg_minimizers_from_record_bytes: a minimizer set goes in, the exact bytes of its record file come out in an
+ * mdbg_bytes on the device, ready for mdbg_bytes_download and a plain write().  Replaces the field-by-field write loops of
+ * ReadSelection (readSelection/ReadSelection.hpp:415-467 for read_data_init.txt, :1420-1426 for read_data_corrected.txt) and the
+ * caller's own serialiser.  Little-endian, no padding; with o = offsets[r] and n = offsets[r + 1] - o, in 64-bit arithmetic:
+ *
+ *   MDBG_RECORDS_PLAIN  `u32 n; u8 circular; u32 m[n]` (read_data_corrected.txt, unitig_data.txt).  Record r starts at byte
+ *                       5 r + 4 o: count at +0, circular (always 0) at +4, values at +5.  5 n_reads + 4 n_minimizers bytes in all.
+ *   MDBG_RECORDS_INIT   `u32 n; u8 circular; u32 m[n]; u32 pos[n]; u8 dir[n]; u8 qual[n]; f32 meanQ; u32 len` (read_data_init.txt).
+ *                       Record r starts at byte 13 r + 10 o: count +0, circular (0) +4, m +5, pos +5 + 4 n, dir +5 + 8 n,
+ *                       qual +5 + 9 n, meanQ +5 + 10 n, len +9 + 10 n.  13 n_reads + 10 n_minimizers bytes in all.  Only an mdbg_scan
+ *                       output (or mdbg_minimizers_concat / mdbg_apply_density_threshold of such) has these fields: MDBG_EINVAL otherwise.  The mean
+ *                       quality comes out with the bits mdbg_minimizers_to_host hands back, NaN included.
+ *
+ * *out is a new buffer of exactly that many bytes (release with mdbg_bytes_free); *n_bytes (optional) is its size.  Zero reads give a
+ * buffer of 0 bytes.  An unknown `form` or a null argument is MDBG_EINVAL.  A fresh scan output is brought into read order first, as
+ * by mdbg_minimizers_to_host.  The kernel is queued on the context's stream and the call does NOT wait for it: what the same context
+ * is asked next -- mdbg_bytes_download, mdbg_minimizers_from_record_bytes, mdbg_reads_from_fastx_bytes -- is ordered behind it by the
+ * stream.  Another context, or anything else that reads the buffer, calls mdbg_synchronize(ctx) first.
+ * Timer name: "records_write". */
+#define MDBG_RECORDS_PLAIN 0   /* read_data_corrected.txt, unitig_data.txt */
+#define MDBG_RECORDS_INIT  1   /* read_data_init.txt: mdbg_scan output only */
+int  mdbg_minimizers_to_record_bytes(mdbg_ctx *ctx, const mdbg_minimizers *m, int form, mdbg_bytes **out, uint64_t *n_bytes /* optional */);
+
 /* ---- FASTA / FASTQ text taken apart on the device -----------------------------------------------------------------------------------
  * Replaces the host side of ReadParserParallel for a plain file: the kseq loop (KSEQ_INIT(gzFile, gzread), Commons.hpp:82) that
  * ReadParser::parse / ReadParserParallel::parse run over every character (Commons.hpp:5827-5922).  The file's bytes travel as they are

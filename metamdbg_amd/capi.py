@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MDBG_LIB") or os.path.join(_HERE, "libmdbg_hip.so")  
 
 MDBG_READ_LOW_COMPLEXITY = 1
 MDBG_READ_LOW_QUALITY = 2
+RECORDS_PLAIN, RECORDS_INIT = 0, 1      # MDBG_RECORDS_*: the forms of mdbg_minimizers_to_record_bytes
 
 
 class MdbgError(RuntimeError):
@@ -126,6 +127,7 @@ SIGNATURES = {
     "mdbg_bytes_free": (None, [_P]),
     "mdbg_minimizers_from_record_bytes": (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.POINTER(_P)]),
     "mdbg_prev_from_record_bytes": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
+    "mdbg_minimizers_to_record_bytes": (C.c_int, [_P, _P, C.c_int, C.POINTER(_P), _u64p]),
     "mdbg_reads_from_fastx_bytes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
     "mdbg_bytes_inflate_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _u64p]),
     "mdbg_bytes_download": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
@@ -401,6 +403,15 @@ class Context:
         self.check(lib().mdbg_minimizers_from_record_bytes(self.h, b.h, _ptr(offs), n, _ptr(circ), C.byref(h)))
         m = Minimizers(self, h)
         return (m, circ) if want_circular else m
+
+    def minimizers_to_record_bytes(self, m: "Minimizers", form: int = RECORDS_PLAIN) -> "DeviceBytes":
+        """The bytes of the set's record file, composed on the device (mdbg_minimizers_to_record_bytes): RECORDS_PLAIN is
+        read_data_corrected.txt / unitig_data.txt (formats.write_minimizer_reads), RECORDS_INIT is read_data_init.txt
+        (formats.build_read_data_init; scan output only).  The kernel is queued, not waited for: ``download`` on this context is ordered behind it."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        self.check(lib().mdbg_minimizers_to_record_bytes(self.h, m.h, form, C.byref(h), C.byref(n)))
+        return DeviceBytes(self, h, int(n.value))
 
     def prev_from_record_bytes(self, b: "DeviceBytes", n_records: int) -> "Table":
         h = C.c_void_p()

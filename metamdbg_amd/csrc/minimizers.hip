@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "objects.hpp"
 #include "murmur.hpp"
+#include "records_dev.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -478,6 +479,79 @@ extern "C" int mdbg_minimizers_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes
     if (circular && n_reads) MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, circular, d_circ.p, n_reads, hipMemcpyDeviceToHost));
     if (bad) return set_error(ctx, MDBG_EINVAL, "mdbg_minimizers_from_record_bytes: a record's count does not agree with the offsets (not this file's bytes?)");
     *out = m.release();
+    return MDBG_OK;
+} MDBG_API_CATCH(ctx)
+
+// The inverse: the bytes of a record file composed from a set's arrays (records_dev.hpp has the layout and the rule under which the
+// stores of different lanes and records never meet).  16 lanes a record, as in the gather.  The output is written, never read.
+namespace mdbg {
+struct RecGlobalSink {
+    uint8_t *out;
+    __device__ __forceinline__ void word(uint64_t at, uint32_t v) { *reinterpret_cast<uint32_t *>(out + at) = v; }
+    __device__ __forceinline__ void byte(uint64_t at, uint8_t v) { out[at] = v; }
+};
+}
+__global__ __launch_bounds__(256) void records_write_kernel(int form, const uint64_t *off, uint32_t n_reads, RecSource src, uint8_t *out, uint64_t n_bytes) {
+    const unsigned sub = threadIdx.x & 15u;
+    const uint64_t group = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) >> 4;
+    RecGlobalSink sink{out};
+    for (uint64_t r = group; r < n_reads; r += ngroups) {
+        const uint64_t o = off[r], n = off[r + 1] - o;
+        if (off[r + 1] < o || rec_start(form, r, o) + rec_bytes(form, n) > n_bytes) continue;     // (offsets that are not this set's: nothing outside the buffer)
+        rec_emit(form, src, r, o, n, sub, 16u, sink);
+    }
+}
+
+extern "C" int mdbg_minimizers_to_record_bytes(mdbg_ctx *ctx, const mdbg_minimizers *m, int form, mdbg_bytes **out, uint64_t *n_bytes) try {
+    if (!ctx || !m || !out) return set_error(ctx, MDBG_EINVAL, "mdbg_minimizers_to_record_bytes: null argument");
+    if (form != MDBG_RECORDS_PLAIN && form != MDBG_RECORDS_INIT)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_minimizers_to_record_bytes: form %d is neither MDBG_RECORDS_PLAIN nor MDBG_RECORDS_INIT", form);
+    if (form == MDBG_RECORDS_INIT && !m->from_scan)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_minimizers_to_record_bytes: positions, directions, qualities and read lengths (MDBG_RECORDS_INIT) exist only for mdbg_scan output");
+    static_assert(MDBG_RECORDS_PLAIN == REC_PLAIN && MDBG_RECORDS_INIT == REC_INIT, "the header's forms are the composition's");
+    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    MDBG_TRY(ensure_canonical(ctx, m));
+    if (form == MDBG_RECORDS_INIT && (!m->d_pos.p || !m->d_dir.p || !m->d_mqual.p || !m->d_len.p))
+        return set_error(ctx, MDBG_EINVAL, "mdbg_minimizers_to_record_bytes: the set has lost its positions, directions, qualities or read lengths (MDBG_RECORDS_INIT)");
+    const uint32_t n = m->n_reads;
+    const uint64_t total = rec_start(form, n, m->n_min);
+    std::unique_ptr<mdbg_bytes> b(new mdbg_bytes());
+    b->n = total;
+    b->owner = ctx;
+    MDBG_TRY(b->d.alloc(ctx, total + 16));
+    if (!ctx->upload_stream) MDBG_HIP_CHECK(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));     // (as mdbg_bytes_create leaves a buffer)
+    if (n) {
+        RecSource src{m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p, nullptr, 0u, m->d_len.p};
+        // (made first: what can still fail once something is queued waits for the stream before the staged bytes go)
+        hipEvent_t ev = nullptr;
+        MDBG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        {
+            std::lock_guard<std::mutex> g(b->mu);
+            b->events.push_back(ev);
+        }
+        if (form == MDBG_RECORDS_INIT) {
+            // the mean quality was finished on the host (mdbg_scan): its bits travel, no float is touched (a NaN comes out as it went in)
+            if (m->h_mean_quality.size() == n) {
+                b->h_keep.resize(n);
+                memcpy(b->h_keep.data(), m->h_mean_quality.data(), (size_t)n * 4);
+                MDBG_TRY(b->d_keep.alloc(ctx, n));
+                MDBG_HIP_CHECK(ctx, hipMemcpyAsync(b->d_keep.p, b->h_keep.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+                src.meanq_bits = b->d_keep.p;
+            } else memcpy(&src.meanq_all, &m->mean_quality_all, 4);
+        }
+        {
+            LaunchTimer timer(ctx, "records_write");
+            hipLaunchKernelGGL(records_write_kernel, dim3(grid_for((uint64_t)n * 16, 256, (unsigned)ctx->n_cu * 16)), dim3(256), 0, ctx->stream, form, m->d_off.p, n, src,
+                               b->d.p, total);
+        }
+        // the event behind the kernel: the buffer and the staged mean qualities are not let go before it has run (~mdbg_bytes waits for it)
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ev, ctx->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return set_error(ctx, MDBG_EHIP, "mdbg_minimizers_to_record_bytes: %s", hipGetErrorString(e)); }
+    }
+    if (n_bytes) *n_bytes = total;
+    *out = b.release();
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
 

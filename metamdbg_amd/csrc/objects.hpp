@@ -64,6 +64,10 @@ struct mdbg_bytes {
     std::vector<hipEvent_t> events;     // events[t - 1] behind piece t
     uint64_t done_upto = 0;             // tickets <= done_upto are known complete
     mdbg_ctx *owner = nullptr;
+    // mdbg_minimizers_to_record_bytes: the per-read mean qualities its kernel reads, as staged on the host and as uploaded; the event
+    // behind that kernel is the last of `events`
+    std::vector<uint32_t> h_keep;
+    mdbg::DevBuf<uint32_t> d_keep;
     mdbg_bytes() = default;
     mdbg_bytes(const mdbg_bytes &) = delete;
     mdbg_bytes &operator=(const mdbg_bytes &) = delete;

@@ -313,6 +313,11 @@ extern "C" int mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, co
 extern "C" int mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n) __attribute__((weak));
 extern "C" int mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format) __attribute__((weak));
 
+// ---- MDBG_TOOL_DEVICE_RECORDS=1: the record bytes of read_data_init.txt and read_data_corrected.txt are composed on the device --------
+// (mdbg_minimizers_to_record_bytes) and come back ready to be written; without it, or with a library that lacks the symbol (the CPU
+// tests' double), builder threads put them together from the eight arrays of a batch.
+extern "C" int mdbg_minimizers_to_record_bytes(mdbg_ctx *ctx, const mdbg_minimizers *m, int form, mdbg_bytes **out, uint64_t *n_bytes) __attribute__((weak));
+
 struct DeviceParsePlan {
     // a BGZF file: its mapping, its block table (BgzfReader::index) and the text offset of every block
     struct Bgzf {
@@ -511,8 +516,37 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         uint32_t n = 0; uint64_t t = 0;
         char *slab = nullptr; size_t cap = 0;
         uint64_t *off = nullptr; uint32_t *m = nullptr, *pos = nullptr, *len = nullptr; uint8_t *dir = nullptr, *qual = nullptr, *flags = nullptr; float *meanQ = nullptr;
-        void shape(uint32_t n_, uint64_t t_) {
+        char *rec = nullptr;                     // device records: the batch's (the group's) record bytes as they go to the file; m, pos, dir, qual are absent then
+        void room(size_t need) {
+            if (need <= cap) return;
+            if (slab) mdbg_host_free(g_ctx, slab);
+            cap = need + need / 4;
+            void *p = nullptr;
+            check(mdbg_host_alloc(g_ctx, cap, &p), "mdbg_host_alloc");
+            slab = (char *)p;
+        }
+        // device records, main pass: the per-read arrays the statistics need and `bytes` of records
+        void shape_init_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
             n = n_; t = t_;
+            room(((size_t)n + 1) * 8 + (size_t)n * 8 + (((size_t)n + 7) & ~(size_t)7) + bytes + 64);
+            char *q = slab;
+            off = (uint64_t *)q; q += ((size_t)n + 1) * 8;
+            len = (uint32_t *)q; q += (size_t)n * 4;
+            meanQ = (float *)q; q += (size_t)n * 4;
+            flags = (uint8_t *)q; q += ((size_t)n + 7) & ~(size_t)7;
+            rec = q;
+            m = pos = nullptr; dir = qual = nullptr;
+        }
+        // device records, purge pass: offsets and `bytes` of records
+        void shape_plain_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
+            n = n_; t = t_;
+            room(((size_t)n + 1) * 8 + bytes + 64);
+            off = (uint64_t *)slab;
+            rec = slab + ((size_t)n + 1) * 8;
+            m = pos = len = nullptr; dir = qual = flags = nullptr; meanQ = nullptr;
+        }
+        void shape(uint32_t n_, uint64_t t_) {
+            n = n_; t = t_; rec = nullptr;
             const size_t need = ((size_t)n + 1) * 8 + t * 8 + (size_t)n * 8 + ((t + 7) & ~(size_t)7) * 2 + (((size_t)n + 7) & ~(size_t)7) + 64;
             if (need > cap) {
                 if (slab) mdbg_host_free(g_ctx, slab);
@@ -533,7 +567,7 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         }
         // offsets and values only (the purge pass)
         void shape_values(uint32_t n_, uint64_t t_) {
-            n = n_; t = t_;
+            n = n_; t = t_; rec = nullptr;
             const size_t need = ((size_t)n + 1) * 8 + t * 4 + 64;
             if (need > cap) {
                 if (slab) mdbg_host_free(g_ctx, slab);
@@ -575,6 +609,14 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         const uint64_t groups = inputBytes / ((uint64_t)std::max<size_t>(1, a.batchBases) * GROUP);
         groupSlabsWanted = (size_t)std::min<uint64_t>(7 * (uint64_t)nConsumers + 2, groups * (uint64_t)nConsumers / 3);
     }
+    bool deviceRecords = false;
+    if (const char *e = getenv("MDBG_TOOL_DEVICE_RECORDS")) {
+        if (atoi(e) != 0) {
+            deviceRecords = mdbg_minimizers_to_record_bytes && mdbg_bytes_download;
+            g_trace.mark(deviceRecords ? "device records: the records of read_data_init.txt and read_data_corrected.txt are composed on the device (mdbg_minimizers_to_record_bytes)"
+                                       : "device records: falling back to the host builders: the library has no mdbg_minimizers_to_record_bytes or mdbg_bytes_download");
+        }
+    }
     std::vector<mdbg_ctx *> ctxs{g_ctx};
     for (int i = 1; i < nConsumers; i++) {
         mdbg_ctx *c = nullptr;
@@ -592,6 +634,8 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
     // built by a few builder threads and written where they belong in the file (pwrite: the size of every earlier batch is known as
     // soon as it has been scanned); one thread writing 1.9 GB of a 50 Gbp read set alone finished 0.45 s behind the consumers.  The
     // statistics (long-double sums: order matters) are accumulated by one thread in read order behind the builders.
+    // With MDBG_TOOL_DEVICE_RECORDS=1 the consumers bring the bytes back ready-made (mdbg_minimizers_to_record_bytes) and a builder only
+    // writes them; placement, the window of batches in flight and the order of the statistics are the same.
     std::map<uint64_t, HostBatch *> buildQ;             // by batch number: a builder takes the lowest one whose place in the file is known
     std::map<uint64_t, uint64_t> sizeOf, offOf;         // batch -> record bytes / file offset
     uint64_t prefSeq = 0, prefOff = 0;
@@ -628,20 +672,24 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                 at = offOf[hb->seq];
                 offOf.erase(hb->seq);
             }
-            rec.resize(hb->t * 10 + (size_t)hb->n * 13);
-            char *dst = rec.data();
-            for (uint32_t r = 0; r < hb->n; r++) {
-                const uint64_t s0 = hb->off[r];
-                const uint32_t k = (uint32_t)(hb->off[r + 1] - s0);
-                memcpy(dst, &k, 4); dst[4] = 0; dst += 5;
-                memcpy(dst, hb->m + s0, (size_t)k * 4); dst += (size_t)k * 4;
-                memcpy(dst, hb->pos + s0, (size_t)k * 4); dst += (size_t)k * 4;
-                memcpy(dst, hb->dir + s0, k); dst += k;
-                memcpy(dst, hb->qual + s0, k); dst += k;
-                memcpy(dst, &hb->meanQ[r], 4); memcpy(dst + 4, &hb->len[r], 4); dst += 8;
+            const size_t recBytes = hb->t * 10 + (size_t)hb->n * 13;
+            if (!hb->rec) {
+                rec.resize(recBytes);
+                char *dst = rec.data();
+                for (uint32_t r = 0; r < hb->n; r++) {
+                    const uint64_t s0 = hb->off[r];
+                    const uint32_t k = (uint32_t)(hb->off[r + 1] - s0);
+                    memcpy(dst, &k, 4); dst[4] = 0; dst += 5;
+                    memcpy(dst, hb->m + s0, (size_t)k * 4); dst += (size_t)k * 4;
+                    memcpy(dst, hb->pos + s0, (size_t)k * 4); dst += (size_t)k * 4;
+                    memcpy(dst, hb->dir + s0, k); dst += k;
+                    memcpy(dst, hb->qual + s0, k); dst += k;
+                    memcpy(dst, &hb->meanQ[r], 4); memcpy(dst + 4, &hb->len[r], 4); dst += 8;
+                }
             }
-            for (size_t done = 0; done < rec.size();) {
-                const ssize_t w = pwrite(outFd, rec.data() + done, rec.size() - done, (off_t)(at + done));
+            const char *from = hb->rec ? hb->rec : rec.data();       // (device records: the slab holds the bytes as they came off the device)
+            for (size_t done = 0; done < recBytes;) {
+                const ssize_t w = pwrite(outFd, from + done, recBytes - done, (off_t)(at + done));
                 if (w < 0) { if (errno == EINTR) continue; die("write to " + outFile + " failed"); }
                 done += (size_t)w;
             }
@@ -908,7 +956,8 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                 {
                     uint32_t bn; uint64_t bt;
                     mdbg_minimizers_info(mins, &bn, &bt);
-                    hb->shape(bn, bt);
+                    if (deviceRecords) hb->shape_init_records(bn, bt, bt * 10 + (uint64_t)bn * 13);
+                    else hb->shape(bn, bt);
                     if (needCorrected && groupSlabsWanted && !getenv("MDBG_TOOL_NO_GROUP_SLABS"))       // (the variable: A/B of the helper)
                         std::call_once(groupSlabOnce, [&, bn, bt] {
                             // a consumer's share of a group (batches are handed out as consumers come free: a little more than GROUP / consumers)
@@ -917,14 +966,26 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                             groupSlabHelper = std::thread([&, rn, rt] {
                                 for (size_t i = 0; i < groupSlabsWanted && !groupSlabsStop.load(); i++) {
                                     HostBatch *g = new HostBatch();
-                                    g->shape_values((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt);
+                                    if (deviceRecords) g->shape_plain_records((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt, 5 * std::min<uint64_t>(rn, 0xFFFFFFFFu) + 4 * rt);
+                                    else g->shape_values((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt);
                                     std::lock_guard<std::mutex> lk(fifoMu);
                                     groupSlabs.push_back(g);
                                 }
                             });
                         });
                 }
-                check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, hb->m, hb->pos, hb->dir, hb->qual, hb->len, hb->meanQ, hb->flags), "to_host");
+                if (deviceRecords) {
+                    // the serialisation is queued, the per-read arrays the statistics thread reads come back behind it, then the record bytes
+                    mdbg_bytes *rb = nullptr;
+                    uint64_t nb_rec = 0;
+                    check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, mins, MDBG_RECORDS_INIT, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
+                    if (nb_rec != hb->t * 10 + (uint64_t)hb->n * 13) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a batch");
+                    check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, nullptr, nullptr, nullptr, nullptr, hb->len, hb->meanQ, hb->flags), "to_host");
+                    check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
+                    mdbg_bytes_free(rb);
+                } else {
+                    check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, hb->m, hb->pos, hb->dir, hb->qual, hb->len, hb->meanQ, hb->flags), "to_host");
+                }
                 const double t3 = g_trace.now();
                 {
                     std::unique_lock<std::mutex> lk(fifoMu);
@@ -1035,16 +1096,21 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                 }
                 const HostBatch *hb = pc.hb;
                 const uint64_t r0 = pc.firstRead, r1 = r0 + pc.nReads;
-                rec.resize((size_t)pc.bytes);
-                char *dst = &rec[0];
-                for (uint64_t r = r0; r < r1; r++) {
-                    const uint32_t k = (uint32_t)(hb->off[r + 1] - hb->off[r]);
-                    memcpy(dst, &k, 4); dst[4] = 0;
-                    memcpy(dst + 5, hb->m + hb->off[r], (size_t)k * 4);
-                    dst += 5 + (size_t)k * 4;
+                // (device records: piece j is the bytes [5 f + 4 off[f], 5 (f + c) + 4 off[f + c]) of the group's slab, f its first read, c its reads)
+                const char *from = hb->rec ? hb->rec + 5 * r0 + 4 * hb->off[r0] : nullptr;
+                if (!from) {
+                    rec.resize((size_t)pc.bytes);
+                    char *dst = &rec[0];
+                    for (uint64_t r = r0; r < r1; r++) {
+                        const uint32_t k = (uint32_t)(hb->off[r + 1] - hb->off[r]);
+                        memcpy(dst, &k, 4); dst[4] = 0;
+                        memcpy(dst + 5, hb->m + hb->off[r], (size_t)k * 4);
+                        dst += 5 + (size_t)k * 4;
+                    }
+                    from = rec.data();
                 }
-                for (size_t done = 0; done < rec.size();) {
-                    const ssize_t w = pwrite(corrFd, rec.data() + done, rec.size() - done, (off_t)(at + done));
+                for (size_t done = 0; done < (size_t)pc.bytes;) {
+                    const ssize_t w = pwrite(corrFd, from + done, (size_t)pc.bytes - done, (off_t)(at + done));
                     if (w < 0) { if (errno == EINTR) continue; die("write to " + tmpDir + "/read_data_corrected.txt failed"); }
                     done += (size_t)w;
                 }
@@ -1101,9 +1167,20 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                 if (!hb) hb = new HostBatch();
                 uint32_t bn; uint64_t bt;
                 mdbg_minimizers_info(pur, &bn, &bt);
-                hb->shape_values(bn, bt);
+                if (deviceRecords) hb->shape_plain_records(bn, bt, 5 * (uint64_t)bn + 4 * bt);
+                else hb->shape_values(bn, bt);
                 const double t4 = g_trace.now();
-                check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, hb->m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
+                if (deviceRecords) {
+                    mdbg_bytes *rb = nullptr;
+                    uint64_t nb_rec = 0;
+                    check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, pur, MDBG_RECORDS_PLAIN, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
+                    if (nb_rec != 5 * (uint64_t)bn + 4 * bt) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a group");
+                    check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
+                    check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
+                    mdbg_bytes_free(rb);
+                } else {
+                    check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, hb->m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
+                }
                 if (a.thenGraph) { std::lock_guard<std::mutex> lk(fifoMu); purgedResident.emplace_back(idx[0], pur); }
                 else mdbg_minimizers_free(pur);
                 const double t5 = g_trace.now();

@@ -130,6 +130,8 @@ def run_tool(tmp_parent, inputs, threads, P, trace=True, rs_args=(), graph_args=
                          "--min-read-quality", "0.000000", *rs_args], capture_output=True, text=True, env=env, timeout=240)
     t1 = time.perf_counter()
     assert r1.returncode == 0, r1.stderr[-1000:]
+    import struct
+    rs_cpu_s, rs_rss_gb = struct.unpack("<dd", open(os.path.join(tmp, "perf.bin"), "rb").read(16))     # readSelection's own (Tool::end); graph overwrites it
     r2 = subprocess.run([TOOL, "graph", tmp, "--threads", str(threads), *graph_args], capture_output=True, text=True, env=env, timeout=240)
     t2 = time.perf_counter()
     assert r2.returncode == 0, r2.stderr[-1000:]
@@ -152,7 +154,7 @@ def run_tool(tmp_parent, inputs, threads, P, trace=True, rs_args=(), graph_args=
         one = {"asm_step_s": t4 - t3, "output_sizes_equal_and_first_16_MB_of_read_data_init_equal": bool(same),
                "trace": [ln.strip() for ln in r3.stderr.splitlines() if "[mdbg_tool]" in ln]}
         shutil.rmtree(os.path.join(tmp_parent, "one"), ignore_errors=True)
-    return {"read_selection_s": t1 - t0, "graph_s": t2 - t1, "total_s": t2 - t0, "asm_step": one,
+    return {"read_selection_s": t1 - t0, "graph_s": t2 - t1, "total_s": t2 - t0, "asm_step": one, "read_selection_cpu_s": rs_cpu_s, "read_selection_rss_gb": rs_rss_gb,
             "trace_read_selection": [ln.strip() for ln in r1.stderr.splitlines() if "[mdbg_tool]" in ln],
             "trace_graph": [ln.strip() for ln in r2.stderr.splitlines() if "[mdbg_tool]" in ln], "output_bytes": sizes}
 
@@ -173,6 +175,8 @@ def main():
     ap.add_argument("--no-gzip", action="store_true", help="of the compressed legs, BGZF only")
     ap.add_argument("--bgzf-modes", default="", help="comma list of extra BGZF runs: copy (the round-2 path: MDBG_HOST_BGZF_COPY=1), t<N> (MDBG_HOST_BGZF_THREADS=N)")
     ap.add_argument("--batch-bases", default="", help="comma list: readSelection --batch-bases values to compare on the FASTA set (tool flag, not a reference flag)")
+    ap.add_argument("--ab-env", default="", help="NAME=VALUE: the plain FASTA and the ONT legs run --reps times WITHOUT and WITH this environment setting, alternating "
+                                                 "(same binary, same files, one session), e.g. MDBG_TOOL_DEVICE_RECORDS=1; every run is listed under <leg>_ab")
     a = ap.parse_args()
     from metamdbg_amd import capi, formats, synth
     work = tempfile.mkdtemp(prefix="mdbg_e2e_", dir=a.dir)
@@ -207,7 +211,20 @@ def main():
                 print(label, t, "threads: readSelection", sorted(b["all_read_selection_s"]), file=sys.stderr)
                 print(label, t, "threads: %.2f s total (readSelection %.2f, graph %.2f) = %.1f Gbp/s" % (b["total_s"], b["read_selection_s"], b["graph_s"], b["gbps"]), file=sys.stderr, flush=True)
             return out
-        if a.reads:
+        def alternating(inputs, PP, label, rs_args=()):
+            """--ab-env: off, on, off, on, ... on the first thread count; every run's times and trace"""
+            name, _, value = a.ab_env.partition("=")
+            out = {"env": a.ab_env, "off": [], "on": []}
+            for _ in range(a.reps):
+                for side, env in (("off", None), ("on", {name: value})):
+                    r = run_tool(os.path.join(work, "run"), inputs, threads[0], PP, rs_args=rs_args, extra_env=env)
+                    out[side].append(r)
+                    print(label, a.ab_env, side, "%.3f s total (readSelection %.3f with %.2f CPU-s, graph %.3f, asmStep %.3f)" % (r["total_s"], r["read_selection_s"],
+                          r["read_selection_cpu_s"], r["graph_s"], r["asm_step"]["asm_step_s"] if r["asm_step"] else float("nan")), file=sys.stderr, flush=True)
+            return out
+        if a.reads and a.ab_env:
+            res["fasta_ab"] = alternating([fasta], P, "fasta")
+        elif a.reads:
             res["fasta"] = best_of([fasta], a.reads, "fasta")
             for bb in [x for x in a.batch_bases.split(",") if x]:
                 runs = [run_tool(os.path.join(work, "run"), [fasta], threads[0], P, rs_args=("--batch-bases", bb)) for _ in range(2)]
@@ -221,14 +238,17 @@ def main():
         if a.ont_reads:
             PO = formats.Parameters(minimizer_size=15, kminmer_size=4, density=0.005, first_k=4, prev_k=4, hpc=False, data_type=1, correction_density=0.025)
             out = {}
-            for t in threads:
+            if a.ab_env:
+                res["ont_ab"] = alternating([ont_fastq], PO, "ont", rs_args=("--skip-correction",))
+            for t in ([] if a.ab_env else threads):
                 runs = [run_tool(os.path.join(work, "run"), [ont_fastq], t, PO, rs_args=("--skip-correction",)) for _ in range(2)]
                 b = min(runs, key=lambda r: r["total_s"])
                 gbp = a.ont_reads * 20_000 / 1e9
                 b.update(gbp=gbp, gbps=gbp / b["total_s"], read_selection_gbps=gbp / b["read_selection_s"], all_total_s=[round(r["total_s"], 3) for r in runs])
                 out[f"threads_{t}"] = b
                 print("ont", t, "threads: %.2f s total (readSelection %.2f, graph %.2f) = %.1f Gbp/s" % (b["total_s"], b["read_selection_s"], b["graph_s"], b["gbps"]), file=sys.stderr, flush=True)
-            res["ont"] = out
+            if not a.ab_env:
+                res["ont"] = out
         if a.gz_reads and a.reads:
             import multiprocessing as mp
             n = min(a.gz_reads, a.reads)
