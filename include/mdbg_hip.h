@@ -497,6 +497,45 @@ int  mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, const mdbg_b
 int  mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n);
 int  mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format);
 
+/* ---- ordinary gzip inflated on the device ---------------------------------------------------------------------------------------------
+ * Replaces gzread under the same kseq loop for gzip input that is not BGZF -- what gzip, pigz and zlib write: one deflate stream per
+ * member, no index, every block free to refer to the 32 KB in front of it.  The scheme is the two-pass one of host/gzip_parallel.hpp:
+ * the caller cuts the compressed file into CHUNKS that start at deflate block headers (finding them stays on the host:
+ * mdbg_host::gzip_find_block); the device decodes every chunk without its window into 16-bit symbols, resolves the windows in order,
+ * translates the symbols to text and checks every member that ended against its trailer.
+ *
+ * mdbg_gzip_stream   what one gzip FILE carries from call to call: the last 32 KB of text, the open member's CRC register and length.
+ *                    It advances only when a call succeeds.
+ * mdbg_gzip_chunk    bits [start_bit, stop_bit) counted from the start of `comp`.  chunks[i].stop_bit == chunks[i + 1].start_bit.  A
+ *                    chunk is decoded from start_bit and must end exactly on stop_bit, at a block boundary; behind a member's last block
+ *                    that boundary is the next member's first block header (trailer and header are read by the chunk the member ends
+ *                    in), or, for the last chunk of a call, the byte behind the trailer.  The last chunk's stop_bit is the next call's
+ *                    first start or MDBG_GZIP_TO_END: through the end of the last member -- what follows it and is no gzip member header
+ *                    is ignored, as gzread does.  On a fresh stream (and after a call that ended behind a trailer) chunks[0].start_bit is
+ *                    the byte-aligned position of a gzip member header, which the device reads (magic, CM = 8, FEXTRA / FNAME / FCOMMENT /
+ *                    FHCRC by its flags); every other start is a deflate block header inside a member.  A chunk spans at most 2 MB.
+ * mdbg_bytes_inflate_gzip
+ *     The text is contiguous at text[text_at ...), *n_text its length; info (optional) = {n_text, members that ended in this call, 1 if
+ *     the file's last member ended, the bit just behind the last bit consumed}.  `comp` may be re-based from call to call (the bits
+ *     count from its start).  Uploads still in flight on `comp` (and `text`) are waited for on the device; the call returns after the
+ *     verdicts have been read back.
+ *     MDBG_EINVAL: a null argument, a chunk outside `comp`, or a chunk that does not decode -- the message names the first such chunk and
+ *     the reason: those of mdbg_bytes_inflate_bgzf, or: ran past the next chunk's start (that start was not a block header) / reference
+ *     before the member's start / bad member header / length does not match ISIZE / CRC-32 mismatch / the stream ended in front of the
+ *     chunk's stop.  MDBG_ERANGE: the text does not fit behind text_at; *n_text then holds the room needed and nothing of the stream has
+ *     changed.  Bytes of `text` outside [text_at, text_at + n_text) are never written.
+ * mdbg_bytes_copy
+ *     a device copy of src[src_at, +n) to dst[dst_at, +n), ordered on the context's stream behind the uploads of both; MDBG_EINVAL when a
+ *     range lies outside its buffer or the two overlap in one buffer. */
+typedef struct mdbg_gzip_stream mdbg_gzip_stream;
+typedef struct { uint64_t start_bit, stop_bit; } mdbg_gzip_chunk;
+#define MDBG_GZIP_TO_END (~0ull)
+int  mdbg_gzip_stream_create(mdbg_ctx *ctx, mdbg_gzip_stream **out);
+void mdbg_gzip_stream_free(mdbg_gzip_stream *s);
+int  mdbg_bytes_inflate_gzip(mdbg_ctx *ctx, mdbg_gzip_stream *s, const mdbg_bytes *comp, const mdbg_gzip_chunk *chunks, uint64_t n_chunks,
+                             mdbg_bytes *text, uint64_t text_at, uint64_t *n_text, uint64_t info[4]);
+int  mdbg_bytes_copy(mdbg_ctx *ctx, mdbg_bytes *dst, uint64_t dst_at, const mdbg_bytes *src, uint64_t src_at, uint64_t n);
+
 /* Page-locked host memory for read batches handed to mdbg_reads_from_ascii / _from_packed: uploads from it
  * run at PCIe rate instead of through the driver's staging copies.  Release with mdbg_host_free. */
 int  mdbg_host_alloc(mdbg_ctx *ctx, size_t bytes, void **out);

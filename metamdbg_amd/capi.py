@@ -131,11 +131,17 @@ SIGNATURES = {
     "mdbg_reads_from_fastx_bytes": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.POINTER(_P), _u64p]),
     "mdbg_bytes_inflate_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _u64p]),
     "mdbg_bytes_download": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
+    "mdbg_gzip_stream_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_gzip_stream_free": (None, [_P]),
+    "mdbg_bytes_inflate_gzip": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _u64p, _u64p]),
+    "mdbg_bytes_copy": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64]),
     "mdbg_fastx_whole_records": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _u64p, C.POINTER(C.c_int)]),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
 BGZF_BLOCK = np.dtype([("src", "<u8"), ("csize", "<u4"), ("isize", "<u4"), ("crc", "<u4"), ("reserved", "<u4")])
+
+GZIP_TO_END = (1 << 64) - 1
 
 _lib = None
 
@@ -447,6 +453,33 @@ class Context:
         self.check(lib().mdbg_bytes_inflate_bgzf(self.h, comp.h, _ptr(table) if len(table) else None, len(table), text.h, text_at, C.byref(n_text)))
         return int(n_text.value)
 
+    # -- ordinary gzip inflated on the device --------------------------------------------------------
+    def gzip_stream(self) -> "GzipStream":
+        """What one gzip file carries from call to call of ``inflate_gzip`` (mdbg_gzip_stream_create)."""
+        h = C.c_void_p()
+        self.check(lib().mdbg_gzip_stream_create(self.h, C.byref(h)))
+        return GzipStream(self, h)
+
+    def inflate_gzip(self, stream: "GzipStream", comp: "DeviceBytes", chunks, text: "DeviceBytes", text_at: int = 0) -> dict:
+        """``chunks`` -- (start_bit, stop_bit) counted from the start of ``comp``, the last stop possibly GZIP_TO_END -- inflated to
+        ``text[text_at ...)`` (mdbg_bytes_inflate_gzip); returns dict(n_text, members, ended, end_bit).  When the text does not fit,
+        the MdbgError (code -5) carries the room needed as ``needed``."""
+        table = np.zeros((len(chunks), 2), dtype=np.uint64)
+        for i, (start, stop) in enumerate(chunks):
+            table[i] = (start, stop)
+        n_text = C.c_uint64(0)
+        info = (C.c_uint64 * 4)()
+        rc = lib().mdbg_bytes_inflate_gzip(self.h, stream.h, comp.h, _ptr(table) if len(table) else None, len(table), text.h, text_at, C.byref(n_text), info)
+        if rc:
+            e = MdbgError(rc, (lib().mdbg_last_error(self.h) or b"").decode())
+            e.needed = int(n_text.value)
+            raise e
+        return dict(n_text=int(n_text.value), members=int(info[1]), ended=int(info[2]), end_bit=int(info[3]))
+
+    def bytes_copy(self, dst: "DeviceBytes", dst_at: int, src: "DeviceBytes", src_at: int, n: int) -> None:
+        """src[src_at, +n) to dst[dst_at, +n) on the device, in stream order (mdbg_bytes_copy)."""
+        self.check(lib().mdbg_bytes_copy(self.h, dst.h, dst_at, src.h, src_at, n))
+
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
         cut, fmt = C.c_uint64(0), C.c_int(0)
@@ -708,6 +741,22 @@ class DeviceBytes:
     def free(self) -> None:
         if self.h:
             lib().mdbg_bytes_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class GzipStream:
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+
+    def free(self) -> None:
+        if self.h:
+            lib().mdbg_gzip_stream_free(self.h)
             self.h = None
 
     def __del__(self):

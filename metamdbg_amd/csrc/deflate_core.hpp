@@ -12,6 +12,9 @@
 // (DFL_E_INPUT); a window index is checked against DFL_WIN, a table index against the table's size; a token is only emitted when its
 // output lies inside [0, isize) and its distance inside the text produced so far.  No loop runs longer than a constant or a
 // count read from a checked header.
+//
+// A chunk of an ordinary gzip file (gzip.hip; tests/host/test_gzip_core.cpp) is decoded by the same parts behind another step function:
+// gz_step, further down.
 #pragma once
 #include <cstdint>
 
@@ -31,7 +34,9 @@ constexpr uint32_t DFL_LENS = 352;        // scratch: 288 + 32 code lengths, the
 constexpr uint32_t DFL_MAX_ISIZE = 65536, DFL_MAX_CSIZE = 65536;      // a BGZF member is at most 64 KB, headers included
 constexpr uint32_t DFL_TOK_MATCH = 0x80000000u;               // token: a literal's byte, or this | length << 16 | distance
 
-enum { DFL_OK = 0, DFL_E_TYPE = 1, DFL_E_STORED = 2, DFL_E_CODE = 3, DFL_E_SYMBOL = 4, DFL_E_DIST = 5, DFL_E_INPUT = 6, DFL_E_SIZE = 7, DFL_E_CRC = 8 };
+enum { DFL_OK = 0, DFL_E_TYPE = 1, DFL_E_STORED = 2, DFL_E_CODE = 3, DFL_E_SYMBOL = 4, DFL_E_DIST = 5, DFL_E_INPUT = 6, DFL_E_SIZE = 7, DFL_E_CRC = 8,
+       // a chunk of an ordinary gzip file (gz_step)
+       GZ_E_PAST = 9, GZ_E_BACKREF = 10, GZ_E_HEADER = 11, GZ_E_ISIZE = 12, GZ_E_OVERFLOW = 13, GZ_E_STOP = 14, GZ_E_BORDERS = 15 };
 enum { DFL_ACT_NONE = 0, DFL_ACT_TOKENS = 1, DFL_ACT_STORED = 2 };
 
 inline const char *dfl_reason(uint32_t e) {
@@ -44,6 +49,13 @@ inline const char *dfl_reason(uint32_t e) {
         case DFL_E_INPUT: return "input exhausted";
         case DFL_E_SIZE: return "output not equal to isize";
         case DFL_E_CRC: return "CRC-32 mismatch";
+        case GZ_E_PAST: return "ran past the next chunk's start";
+        case GZ_E_BACKREF: return "reference before the member's start";
+        case GZ_E_HEADER: return "bad member header";
+        case GZ_E_ISIZE: return "length does not match ISIZE";
+        case GZ_E_OVERFLOW: return "more symbols than the format allows";
+        case GZ_E_STOP: return "the stream ended in front of the chunk's stop";
+        case GZ_E_BORDERS: return "more members than the chunk's bytes can hold";
         default: return "unknown status";
     }
 }
@@ -256,6 +268,41 @@ DFL_HD uint32_t dfl_dynamic_tables(dfl_bits &b, const dfl_mem &m) {
     return DFL_OK;
 }
 
+// Up to DFL_TOKENS tokens of the open block into m.tok.  `pos` is the output position (advanced), `limit` the output's bound
+// (beyond it: DFL_E_SIZE); a distance may be at most `maxd` (DFL_E_DIST) and may reach back to position `lo` at the lowest (`e_lo`).
+// The end-of-block code clears in_block.
+DFL_HD uint32_t dfl_tokens(dfl_bits &b, const dfl_mem &m, uint32_t &pos, uint32_t limit, uint32_t maxd, int64_t lo, uint32_t e_lo, uint32_t &n,
+                           uint32_t &in_block) {
+    const dfl_code lit = dfl_lit_code(m), dist = dfl_dist_code(m);
+    while (n < DFL_TOKENS) {
+        const int s = dfl_sym(b, lit);
+        if (s < 0 || s > 285) return DFL_E_SYMBOL;
+        if (s < 256) {
+            if (pos >= limit) return DFL_E_SIZE;
+            m.tok[n++] = (uint32_t)s;
+            pos++;
+            continue;
+        }
+        if (s == 256) { in_block = 0; break; }
+        const uint32_t i = (uint32_t)s - 257u;                 // 0 .. 28
+        uint32_t len;
+        if (i < 8) len = 3 + i;
+        else if (i == 28) len = 258;
+        else { const uint32_t x = (i >> 2) - 1; len = 3 + ((4 + (i & 3u)) << x) + dfl_take(b, x); }
+        const int d = dfl_sym(b, dist);
+        if (d < 0 || d > 29) return DFL_E_SYMBOL;
+        uint32_t off;
+        if (d < 4) off = 1 + (uint32_t)d;
+        else { const uint32_t x = ((uint32_t)d >> 1) - 1; off = 1 + ((2 + ((uint32_t)d & 1u)) << x) + dfl_take(b, x); }
+        if (off > maxd) return DFL_E_DIST;
+        if ((int64_t)pos - (int64_t)off < lo) return e_lo;
+        if ((uint64_t)pos + len > limit) return DFL_E_SIZE;
+        m.tok[n++] = DFL_TOK_MATCH | (len << 16) | off;
+        pos += len;
+    }
+    return DFL_OK;
+}
+
 // One step.  The window must hold the payload from (bitpos >> 3) on for DFL_NEED bytes or up to its end.
 DFL_HD void dfl_step(dfl_state &st, const dfl_mem &m) {
     dfl_bits b;
@@ -292,33 +339,8 @@ DFL_HD void dfl_step(dfl_state &st, const dfl_mem &m) {
             st.in_block = 1;
         } else err = DFL_E_TYPE;
     } else {
-        const dfl_code lit = dfl_lit_code(m), dist = dfl_dist_code(m);
         uint32_t pos = st.out, n = 0;
-        while (n < DFL_TOKENS) {
-            const int s = dfl_sym(b, lit);
-            if (s < 0 || s > 285) { err = DFL_E_SYMBOL; break; }
-            if (s < 256) {
-                if (pos >= st.isize) { err = DFL_E_SIZE; break; }
-                m.tok[n++] = (uint32_t)s;
-                pos++;
-                continue;
-            }
-            if (s == 256) { st.in_block = 0; break; }
-            const uint32_t i = (uint32_t)s - 257u;                 // 0 .. 28
-            uint32_t len;
-            if (i < 8) len = 3 + i;
-            else if (i == 28) len = 258;
-            else { const uint32_t x = (i >> 2) - 1; len = 3 + ((4 + (i & 3u)) << x) + dfl_take(b, x); }
-            const int d = dfl_sym(b, dist);
-            if (d < 0 || d > 29) { err = DFL_E_SYMBOL; break; }
-            uint32_t off;
-            if (d < 4) off = 1 + (uint32_t)d;
-            else { const uint32_t x = ((uint32_t)d >> 1) - 1; off = 1 + ((2 + ((uint32_t)d & 1u)) << x) + dfl_take(b, x); }
-            if (off > pos) { err = DFL_E_DIST; break; }
-            if (pos + len > st.isize) { err = DFL_E_SIZE; break; }
-            m.tok[n++] = DFL_TOK_MATCH | (len << 16) | off;
-            pos += len;
-        }
+        err = dfl_tokens(b, m, pos, st.isize, 0xFFFFFFFFu, 0, DFL_E_DIST, n, st.in_block);
         st.n_tok = n;
         st.out = pos;
         st.act = DFL_ACT_TOKENS;
@@ -327,6 +349,163 @@ DFL_HD void dfl_step(dfl_state &st, const dfl_mem &m) {
     if (!stored && (dfl_bitpos(b) > (uint64_t)st.csize * 8 || b.fault)) err = DFL_E_INPUT;
     if (err != DFL_OK) { st.err = err; st.act = DFL_ACT_NONE; st.n_tok = 0; return; }
     if (!stored) st.bitpos = dfl_bitpos(b);
+}
+
+// ---- a chunk of an ordinary gzip file ------------------------------------------------------------------------------------------------
+// The two-pass scheme of host/gzip_parallel.hpp: a chunk is bits [start, stop) of the file, it starts at a deflate block header (or at a
+// gzip member header) and is decoded WITHOUT the 32 KB in front of it into 16-bit symbols -- a byte, or GZ_MARK + p for "byte p of the
+// unknown 32 KB in front of the chunk".  The steps are those of a BGZF member plus three: a member header (RFC 1952: magic, CM = 8,
+// FEXTRA / FNAME / FCOMMENT / FHCRC by its flags), the rest of a long header, and a member trailer, after which the caller notes a
+// BORDER (symbol position, CRC-32, ISIZE) and the next member's header follows or the stream ends (what is no header is ignored, as
+// gzread does).  Behind a border no distance reaches in front of it.  After every block: the reader stands on `stop` (the chunk is
+// done), or beyond it (GZ_E_PAST: `stop`, the next chunk's start, was no block header).
+//
+// Bounds, as above: the payload is [0, csize) bytes and bits beyond it read as zeros and fail the step; an output position is checked
+// against `cap`; every step consumes at least one bit (a header step 80, a trailer step 64, a step of a long header at least 8), so
+// gz_max_steps bounds the loop.
+constexpr uint32_t GZ_MARK = 0x8000u, GZ_REACH = 32768u;
+constexpr uint64_t GZ_TO_END = ~0ull;
+constexpr uint32_t GZ_MAX_SPAN = 1u << 21;                     // bytes of a chunk: 1032 symbols a byte stay below 2^32
+enum { GZ_PH_HEADER = 0, GZ_PH_HEADER_REST = 1, GZ_PH_BLOCK = 2, GZ_PH_TRAILER = 3, GZ_PH_DONE = 4 };
+enum { GZ_ACT_BORDER = 3 };
+enum { GZ_END_STOP = 0, GZ_END_BORDER = 1, GZ_END_STREAM = 2 };     // how a chunk ended: on its stop inside a member, on its stop behind a trailer, with the file's last member
+struct gz_state {
+    uint64_t bitpos, stop;    // bits of the payload; stop: GZ_TO_END = through the end of the last member
+    int64_t lo;               // the lowest symbol position a distance may reach: -reach0 at first, the last border's position behind one
+    uint32_t csize, cap, out, wbase, filled, in_block, final, err;
+    uint32_t phase, hflags, skip, hcrc, ended, n_borders;
+    uint32_t act, out0, n_tok, stored_at, stored_len;
+    uint32_t border_crc, border_isize;    // GZ_ACT_BORDER: a member ended at symbol position out0 with this trailer
+};
+DFL_HD void gz_begin(gz_state &st, uint32_t start_bit /* < 8 */, uint64_t stop, uint32_t csize, uint32_t cap, uint32_t reach0, bool at_header) {
+    st.bitpos = start_bit; st.stop = stop; st.lo = -(int64_t)(reach0 < GZ_REACH ? reach0 : GZ_REACH); st.csize = csize; st.cap = cap; st.out = 0;
+    st.wbase = 0; st.filled = 0; st.in_block = 0; st.final = 0; st.err = DFL_OK; st.phase = at_header ? GZ_PH_HEADER : GZ_PH_BLOCK; st.hflags = 0; st.skip = 0; st.hcrc = 0;
+    st.ended = GZ_END_STOP; st.n_borders = 0; st.act = DFL_ACT_NONE; st.out0 = 0; st.n_tok = 0; st.stored_at = 0; st.stored_len = 0; st.border_crc = 0; st.border_isize = 0;
+}
+DFL_HD bool gz_finished(const gz_state &st) { return st.err != DFL_OK || st.phase == GZ_PH_DONE; }
+DFL_HD uint64_t gz_max_steps(uint32_t csize) { return (uint64_t)csize * 8 + 2; }
+// symbols a chunk of `csize` bytes holds at the most: a match of 258 costs two bits at the least (1032 a byte), and a last one may begin in the last bit
+DFL_HD uint64_t gz_max_symbols(uint32_t csize) { return (uint64_t)csize * 1032 + 258; }
+
+// the CRC-32 register over a header byte (no table: a header is a few bytes)
+DFL_HD uint32_t gz_hcrc(uint32_t reg, uint32_t byte) {
+    uint32_t c = (reg ^ byte) & 255u;
+    for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+    return c ^ (reg >> 8);
+}
+// a block ended at st.bitpos
+DFL_HD void gz_block_end(gz_state &st) {
+    if (st.final) { st.phase = GZ_PH_TRAILER; return; }
+    if (st.stop == GZ_TO_END || st.bitpos < st.stop) return;
+    if (st.bitpos == st.stop) st.phase = GZ_PH_DONE; else st.err = GZ_E_PAST;
+}
+
+DFL_HD void gz_step(gz_state &st, const dfl_mem &m) {
+    dfl_bits b;
+    dfl_seed(b, m.win, st.wbase, st.csize, st.bitpos);
+    st.act = DFL_ACT_NONE;
+    st.n_tok = 0;
+    st.out0 = st.out;
+    uint32_t err = DFL_OK;
+    bool jumped = false;      // the step set st.bitpos itself
+    bool boundary = false;    // the step ends where a block header is due
+    if (st.phase == GZ_PH_HEADER) {
+        uint32_t h[10];
+        st.hcrc = 0xFFFFFFFFu;
+        for (uint32_t i = 0; i < 10; i++) { h[i] = dfl_take(b, 8); st.hcrc = gz_hcrc(st.hcrc, h[i]); }
+        if ((st.bitpos & 7u) || h[0] != 0x1Fu || h[1] != 0x8Bu || h[2] != 8u || (h[3] & 0xE0u)) err = GZ_E_HEADER;
+        else {
+            st.hflags = h[3] & (4u | 8u | 16u | 2u);
+            st.skip = 0;
+            if (st.hflags & 4u) {
+                const uint32_t x0 = dfl_take(b, 8), x1 = dfl_take(b, 8);
+                st.hcrc = gz_hcrc(gz_hcrc(st.hcrc, x0), x1);
+                st.skip = x0 | x1 << 8;
+                if (!st.skip) st.hflags &= ~4u;
+            }
+            st.phase = st.hflags ? GZ_PH_HEADER_REST : GZ_PH_BLOCK;
+            st.final = 0; st.in_block = 0;
+            boundary = !st.hflags;
+        }
+    } else if (st.phase == GZ_PH_HEADER_REST) {                    // at most 256 bytes a step, at least one
+        if (st.hflags & 4u) {                                      // FEXTRA: st.skip bytes
+            for (uint32_t i = 0; i < 256 && st.skip; i++, st.skip--) st.hcrc = gz_hcrc(st.hcrc, dfl_take(b, 8));
+            if (!st.skip) st.hflags &= ~4u;
+        } else if (st.hflags & (8u | 16u)) {                       // FNAME, then FCOMMENT: up to their zero byte
+            const uint32_t flag = (st.hflags & 8u) ? 8u : 16u;
+            for (uint32_t i = 0; i < 256; i++) {
+                if ((dfl_bitpos(b) >> 3) >= st.csize) { err = DFL_E_INPUT; break; }
+                const uint32_t c = dfl_take(b, 8);
+                st.hcrc = gz_hcrc(st.hcrc, c);
+                if (c == 0) { st.hflags &= ~flag; break; }
+            }
+        } else if (st.hflags & 2u) {                               // FHCRC: the low half of the header's CRC-32
+            if (dfl_take(b, 16) != ((st.hcrc ^ 0xFFFFFFFFu) & 0xFFFFu)) err = GZ_E_HEADER;
+            st.hflags &= ~2u;
+        }
+        if (!st.hflags) { st.phase = GZ_PH_BLOCK; boundary = true; }
+    } else if (st.phase == GZ_PH_TRAILER) {
+        dfl_drop(b, b.cnt & 7u);
+        const uint32_t c0 = dfl_take(b, 16), c1 = dfl_take(b, 16), i0 = dfl_take(b, 16), i1 = dfl_take(b, 16);
+        const uint64_t at = dfl_bitpos(b) >> 3;
+        if (at > st.csize || b.fault) err = st.stop == GZ_TO_END ? DFL_E_INPUT : GZ_E_PAST;
+        else {
+            st.act = GZ_ACT_BORDER;
+            st.border_crc = c0 | c1 << 16; st.border_isize = i0 | i1 << 16;
+            st.n_borders++;
+            st.lo = st.out;
+            st.final = 0;
+            if (st.stop != GZ_TO_END && at * 8 >= st.stop) {
+                if (at * 8 == st.stop) { st.phase = GZ_PH_DONE; st.ended = GZ_END_BORDER; } else err = GZ_E_PAST;
+            } else if (at + 2 <= st.csize && dfl_peek(b, 16) == 0x8B1Fu) st.phase = GZ_PH_HEADER;
+            else if (st.stop != GZ_TO_END) err = GZ_E_STOP;
+            else { st.phase = GZ_PH_DONE; st.ended = GZ_END_STREAM; }
+            st.bitpos = at * 8; jumped = true;
+        }
+    } else if (st.phase == GZ_PH_BLOCK && !st.in_block) {
+        st.final = dfl_take(b, 1);
+        const uint32_t type = dfl_take(b, 2);
+        if (type == 0) {
+            dfl_drop(b, b.cnt & 7u);
+            const uint32_t len = dfl_take(b, 16), nlen = dfl_take(b, 16);
+            const uint64_t at = dfl_bitpos(b) >> 3;
+            if (at > st.csize || b.fault) err = st.stop == GZ_TO_END ? DFL_E_INPUT : GZ_E_PAST;
+            else if ((len ^ 0xFFFFu) != nlen) err = DFL_E_STORED;
+            else if (at + len > st.csize) err = st.stop == GZ_TO_END ? DFL_E_INPUT : GZ_E_PAST;
+            else if ((uint64_t)st.out + len > st.cap) err = GZ_E_OVERFLOW;
+            else {
+                jumped = true;
+                st.act = DFL_ACT_STORED;
+                st.stored_at = (uint32_t)at;
+                st.stored_len = len;
+                st.out += len;
+                st.bitpos = (at + len) * 8;
+                boundary = true;
+            }
+        } else if (type == 1) {
+            err = dfl_fixed_tables(m);
+            st.in_block = 1;
+        } else if (type == 2) {
+            err = dfl_dynamic_tables(b, m);
+            st.in_block = 1;
+        } else err = DFL_E_TYPE;
+    } else if (st.phase == GZ_PH_BLOCK) {
+        uint32_t pos = st.out, n = 0;
+        err = dfl_tokens(b, m, pos, st.cap, GZ_REACH, st.lo, GZ_E_BACKREF, n, st.in_block);
+        if (err == DFL_E_SIZE) err = GZ_E_OVERFLOW;
+        st.n_tok = n;
+        st.out = pos;
+        st.act = DFL_ACT_TOKENS;
+    } else err = DFL_E_INPUT;                                      // (no step is asked of a finished chunk)
+    // bits that do not exist were read as zeros: whatever they decoded to, the input ended first (a chunk's input ends with its stop)
+    if (!jumped && (dfl_bitpos(b) > (uint64_t)st.csize * 8 || b.fault)) err = st.stop == GZ_TO_END ? DFL_E_INPUT : GZ_E_PAST;
+    if (err != DFL_OK) { st.err = err; st.act = DFL_ACT_NONE; st.n_tok = 0; return; }
+    if (!jumped) st.bitpos = dfl_bitpos(b);
+    if (st.act == DFL_ACT_TOKENS && !st.in_block) boundary = true;
+    if (boundary) {
+        gz_block_end(st);
+        if (st.err != DFL_OK) { st.act = DFL_ACT_NONE; st.n_tok = 0; }
+    }
 }
 
 // ---- CRC-32 (gzip: polynomial 0xEDB88320 reflected) --------------------------------------------------------------------------------

@@ -348,3 +348,115 @@ def bgzf_compress(data: bytes, block: int = 0xFF00, level: int = 6, strategy: in
     if eof_marker:
         out.append(bgzf_member(b""))
     return b"".join(out)
+
+
+# ---- deflate block headers: the ground truth for the chunk starts of mdbg_bytes_inflate_gzip -------------------------------------------
+class _BitReader:
+    def __init__(self, raw: bytes, bit: int):
+        self.raw = raw + bytes(4)
+        self.n = len(raw) * 8
+        self.bit = bit
+
+    def peek(self, k: int) -> int:                             # k <= 16; zeros beyond the end
+        at = self.bit >> 3
+        return (int.from_bytes(self.raw[at:at + 4], "little") >> (self.bit & 7)) & ((1 << k) - 1)
+
+    def take(self, k: int) -> int:
+        if self.bit + k > self.n:
+            raise ValueError("deflate stream ends inside a block")
+        x = self.peek(k)
+        self.bit += k
+        return x
+
+
+def _huffman(lengths):
+    """{(length, code): symbol} of a canonical code; the code's bits are read most significant first."""
+    count = [0] * 16
+    for l in lengths:
+        count[l] += 1
+    count[0] = 0
+    code, nxt = 0, [0] * 16
+    for l in range(1, 16):
+        code = (code + count[l - 1]) << 1
+        nxt[l] = code
+    table = {}
+    for sym, l in enumerate(lengths):
+        if l:
+            table[(l, nxt[l])] = sym
+            nxt[l] += 1
+    return table
+
+
+def _symbol(r: _BitReader, table) -> int:
+    v, code = r.peek(15), 0
+    for l in range(1, 16):
+        code = (code << 1) | (v & 1)
+        v >>= 1
+        s = table.get((l, code))
+        if s is not None:
+            r.take(l)
+            return s
+    raise ValueError("no such Huffman code")
+
+
+_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+_DIST_EXTRA = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+_FIXED = None
+
+
+def deflate_block_starts(raw: bytes, start_bit: int = 0):
+    """A walk over the stored, fixed and dynamic blocks of the raw DEFLATE stream that begins at bit ``start_bit`` of ``raw``, through
+    its final block: ([(bit of the block's header, type, final flag, text bytes in front of it)], the bit behind the stream).  Pure
+    Python and slow (seconds a megabyte of text): for tests, which take their chunk starts from it."""
+    global _FIXED
+    r = _BitReader(raw, start_bit)
+    blocks, n_text = [], 0
+    while True:
+        at = r.bit
+        final, kind = r.take(1), r.take(2)
+        blocks.append((at, kind, final, n_text))
+        if kind == 0:
+            r.bit = (r.bit + 7) & ~7
+            ln, nln = r.take(16), r.take(16)
+            if ln ^ 0xFFFF != nln:
+                raise ValueError("stored LEN/NLEN mismatch")
+            if r.bit + 8 * ln > r.n:
+                raise ValueError("deflate stream ends inside a block")
+            r.bit += 8 * ln
+            n_text += ln
+        elif kind in (1, 2):
+            if kind == 1:
+                if _FIXED is None:
+                    _FIXED = (_huffman([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8), _huffman([5] * 30))
+                lit, dist = _FIXED
+            else:
+                hlit, hdist, hclen = r.take(5) + 257, r.take(5) + 1, r.take(4) + 4
+                cl = [0] * 19
+                for i in range(hclen):
+                    cl[(16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)[i]] = r.take(3)
+                clt, lens = _huffman(cl), []
+                while len(lens) < hlit + hdist:
+                    s = _symbol(r, clt)
+                    if s < 16:
+                        lens.append(s)
+                    elif s == 16:
+                        lens += [lens[-1]] * (3 + r.take(2))
+                    elif s == 17:
+                        lens += [0] * (3 + r.take(3))
+                    else:
+                        lens += [0] * (11 + r.take(7))
+                lit, dist = _huffman(lens[:hlit]), _huffman(lens[hlit:hlit + hdist])
+            while True:
+                s = _symbol(r, lit)
+                if s < 256:
+                    n_text += 1
+                elif s == 256:
+                    break
+                else:
+                    n_text += _LEN_BASE[s - 257] + r.take(_LEN_EXTRA[s - 257])
+                    r.take(_DIST_EXTRA[_symbol(r, dist)])
+        else:
+            raise ValueError("reserved block type")
+        if final:
+            return blocks, r.bit

@@ -44,6 +44,69 @@
 
 namespace mdbg_host {
 
+// ---- finding a block header --------------------------------------------------------------------------------------------
+// (callable from outside the reader: mdbg_tool's device path finds its chunk starts with the same search)
+constexpr size_t GZIP_WINDOW = 32768, GZIP_PROBE_ROOM = 1u << 18;
+constexpr uint64_t GZIP_NONE = ~0ull;
+
+inline bool gzip_plausible_text(const uint16_t *s, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        const uint16_t v = s[i];
+        // read files are text: no control characters (bytes >= 128 may be UTF-8 in a header line).  Bytes decoded from a
+        // wrong position are uniformly random: a few hundred of them already contain one.
+        if (v < 32 ? !(v == '\n' || v == '\r' || v == '\t') : v == 127) return false;
+    }
+    return true;
+}
+
+// first bit in [from, to) of `data` where a non-final dynamic block starts that decodes to text and is followed by
+// more valid data; GZIP_NONE if there is none
+inline uint64_t gzip_find_block(const uint8_t *data, const uint8_t *end, uint64_t from, uint64_t to, InflaterT<uint16_t> &probe, std::vector<uint16_t> &scratch) {
+    if (scratch.size() < GZIP_WINDOW + GZIP_PROBE_ROOM) {
+        scratch.resize(GZIP_WINDOW + GZIP_PROBE_ROOM);
+        for (size_t i = 0; i < GZIP_WINDOW; i++) scratch[i] = (uint16_t)(0x8000u + i);
+    }
+    const uint64_t last = (uint64_t)(end - data) * 8;
+    for (uint64_t bit = from; bit < to && bit + 128 < last; bit++) {
+        uint64_t w;
+        memcpy(&w, data + (bit >> 3), 8);
+        w >>= (bit & 7);
+        if ((w & 7) != 4) continue;                                        // BFINAL = 0, BTYPE = 2 (dynamic Huffman)
+        if (((w >> 3) & 31) > 29 || ((w >> 8) & 31) > 29) continue;        // HLIT, HDIST
+        // the code-length code must be complete: sum over its codes of 2^(7 - length) == 2^7
+        const unsigned hclen = (unsigned)((w >> 13) & 15) + 4;
+        uint64_t cl;
+        memcpy(&cl, data + ((bit + 17) >> 3), 8);
+        cl >>= ((bit + 17) & 7);                                           // 57 bits left: 19 lengths of 3 bits
+        unsigned kraft = 0;
+        for (unsigned i = 0; i < hclen; i++) {
+            const unsigned l = (unsigned)((cl >> (3 * i)) & 7);
+            if (l) kraft += 128u >> l;
+        }
+        if (kraft != 128) continue;
+        probe.reset_at_bit(data, bit, end);
+        size_t produced = 0;
+        const auto st = probe.run(scratch.data() + GZIP_WINDOW, scratch.data() + scratch.size(), GZIP_WINDOW, &produced);
+        if (st == InflaterT<uint16_t>::CORRUPT) continue;                  // NEED_ROOM: 256 K symbols decoded cleanly
+        if (st == InflaterT<uint16_t>::STREAM_END && probe.blocks_done() < 2) continue;
+        if (!gzip_plausible_text(scratch.data() + GZIP_WINDOW, produced)) continue;
+        return bit;
+    }
+    return GZIP_NONE;
+}
+// the same with a decoder and scratch of its own (a caller that searches often keeps both and calls the form above)
+inline uint64_t gzip_find_block(const uint8_t *data, size_t len, uint64_t from, uint64_t to) {
+    InflaterT<uint16_t> probe;
+    std::vector<uint16_t> scratch;
+    return gzip_find_block(data, data + len, from, to, probe, scratch);
+}
+// bit `bit` of `data` holds BFINAL = 0, BTYPE = 2: the kind of header the search looks for
+inline bool gzip_is_dynamic_nonfinal(const uint8_t *data, size_t len, uint64_t bit) {
+    if ((bit >> 3) + 1 >= len) return false;
+    const unsigned w = (unsigned)(data[bit >> 3] | data[(bit >> 3) + 1] << 8) >> (bit & 7);
+    return (w & 7) == 4;
+}
+
 class ParallelGzipReader {
 public:
     static constexpr size_t WINDOW = 32768;
@@ -198,51 +261,10 @@ private:
 
     std::string hint() const { return " (MDBG_HOST_GZIP_THREADS=1 decodes the stream on one thread)"; }
 
-    // ---- finding a block header ------------------------------------------------------------------------------------
-    static bool plausible_text(const uint16_t *s, size_t n) {
-        for (size_t i = 0; i < n; i++) {
-            const uint16_t v = s[i];
-            // read files are text: no control characters (bytes >= 128 may be UTF-8 in a header line).  Bytes decoded from a
-            // wrong position are uniformly random: a few hundred of them already contain one.
-            if (v < 32 ? !(v == '\n' || v == '\r' || v == '\t') : v == 127) return false;
-        }
-        return true;
-    }
-
-    // first bit in [from, to) of `data` where a non-final dynamic block starts that decodes to text and is followed by
-    // more valid data; NONE if there is none
+    // ---- finding a block header (gzip_find_block above) ------------------------------------------------------------
+    static bool plausible_text(const uint16_t *s, size_t n) { return gzip_plausible_text(s, n); }
     static uint64_t find_block(const uint8_t *data, const uint8_t *end, uint64_t from, uint64_t to, InflaterT<uint16_t> &probe, std::vector<uint16_t> &scratch) {
-        if (scratch.size() < WINDOW + PROBE_ROOM) {
-            scratch.resize(WINDOW + PROBE_ROOM);
-            for (size_t i = 0; i < WINDOW; i++) scratch[i] = (uint16_t)(0x8000u + i);
-        }
-        const uint64_t last = (uint64_t)(end - data) * 8;
-        for (uint64_t bit = from; bit < to && bit + 128 < last; bit++) {
-            uint64_t w;
-            memcpy(&w, data + (bit >> 3), 8);
-            w >>= (bit & 7);
-            if ((w & 7) != 4) continue;                                        // BFINAL = 0, BTYPE = 2 (dynamic Huffman)
-            if (((w >> 3) & 31) > 29 || ((w >> 8) & 31) > 29) continue;        // HLIT, HDIST
-            // the code-length code must be complete: sum over its codes of 2^(7 - length) == 2^7
-            const unsigned hclen = (unsigned)((w >> 13) & 15) + 4;
-            uint64_t cl;
-            memcpy(&cl, data + ((bit + 17) >> 3), 8);
-            cl >>= ((bit + 17) & 7);                                           // 57 bits left: 19 lengths of 3 bits
-            unsigned kraft = 0;
-            for (unsigned i = 0; i < hclen; i++) {
-                const unsigned l = (unsigned)((cl >> (3 * i)) & 7);
-                if (l) kraft += 128u >> l;
-            }
-            if (kraft != 128) continue;
-            probe.reset_at_bit(data, bit, end);
-            size_t produced = 0;
-            const auto st = probe.run(scratch.data() + WINDOW, scratch.data() + scratch.size(), WINDOW, &produced);
-            if (st == InflaterT<uint16_t>::CORRUPT) continue;                  // NEED_ROOM: 256 K symbols decoded cleanly
-            if (st == InflaterT<uint16_t>::STREAM_END && probe.blocks_done() < 2) continue;
-            if (!plausible_text(scratch.data() + WINDOW, produced)) continue;
-            return bit;
-        }
-        return NONE;
+        return gzip_find_block(data, end, from, to, probe, scratch);
     }
 
     // ---- the pool ------------------------------------------------------------------------------------------------------
@@ -495,7 +517,7 @@ private:
         p.reset();
     }
 
-    static constexpr size_t PROBE_ROOM = 1u << 18;
+    static constexpr size_t PROBE_ROOM = GZIP_PROBE_ROOM;
 
     const uint8_t *addr_;
     size_t len_;

@@ -312,6 +312,12 @@ extern "C" int mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, co
                                        uint64_t *n_text) __attribute__((weak));
 extern "C" int mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n) __attribute__((weak));
 extern "C" int mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format) __attribute__((weak));
+// gzip that is not BGZF: cut into chunks at deflate block headers found here (mdbg_host::gzip_find_block) and inflated on the device
+extern "C" int mdbg_gzip_stream_create(mdbg_ctx *ctx, mdbg_gzip_stream **out) __attribute__((weak));
+extern "C" void mdbg_gzip_stream_free(mdbg_gzip_stream *s) __attribute__((weak));
+extern "C" int mdbg_bytes_inflate_gzip(mdbg_ctx *ctx, mdbg_gzip_stream *s, const mdbg_bytes *comp, const mdbg_gzip_chunk *chunks, uint64_t n_chunks, mdbg_bytes *text,
+                                       uint64_t text_at, uint64_t *n_text, uint64_t info[4]) __attribute__((weak));
+extern "C" int mdbg_bytes_copy(mdbg_ctx *ctx, mdbg_bytes *dst, uint64_t dst_at, const mdbg_bytes *src, uint64_t src_at, uint64_t n) __attribute__((weak));
 
 // ---- MDBG_TOOL_DEVICE_RECORDS=1: the record bytes of read_data_init.txt and read_data_corrected.txt are composed on the device --------
 // (mdbg_minimizers_to_record_bytes) and come back ready to be written; without it, or with a library that lacks the symbol (the CPU
@@ -326,9 +332,65 @@ struct DeviceParsePlan {
         std::vector<mdbg_host::BgzfReader::Block> blocks;
         std::vector<uint64_t> cum;
     };
-    struct Slab { const char *p; size_t n; int file; int bgzf; };        // bgzf >= 0: the whole of bgzfs[bgzf], cut into slabs as it is inflated
+    // A gzip file that is not BGZF: worker threads look for one deflate block header per `chunk` bytes of the file (start[k]: the first
+    // header in chunk k, NONE: none found; start[0] is the file's first member header) and run ahead of the consumers, which inflate
+    // groups of chunks on the device (mdbg_bytes_inflate_gzip) and carry the unfinished record from slab to slab.
+    struct Gzip {
+        static constexpr uint64_t NONE = mdbg_host::GZIP_NONE;
+        std::string path;
+        const unsigned char *addr = nullptr;
+        size_t size = 0, chunk = 65536, nChunks = 0;
+        std::vector<uint64_t> start;
+        std::vector<char> known;
+        std::mutex mu;
+        std::condition_variable cv;
+        std::atomic<size_t> nextSearch{0};
+        std::vector<std::thread> workers;
+        // where the consumers stand (under the feed's lock)
+        mdbg_gzip_stream *stream = nullptr;
+        uint64_t atBit = 0;             // the next call's first start
+        size_t nextK = 1;               // the first chunk whose header may lie behind atBit
+        mdbg_bytes *rest = nullptr;     // the unfinished record behind the last slab's cut
+        uint64_t nRest = 0;
+        bool ended = false;
+        uint64_t nCalls = 0, nChunksInflated = 0;
+
+        void search(size_t k) {
+            mdbg_host::InflaterT<uint16_t> probe;
+            std::vector<uint16_t> scratch;
+            const uint64_t found = mdbg_host::gzip_find_block(addr, addr + size, (uint64_t)k * chunk * 8, (uint64_t)(k + 1) * chunk * 8, probe, scratch);
+            std::lock_guard<std::mutex> g(mu);
+            start[k] = found;
+            known[k] = 1;
+            cv.notify_all();
+        }
+        void run_workers(int threads) {
+            for (int t = 0; t < threads; t++)
+                workers.emplace_back([this] {
+                    mdbg_host::InflaterT<uint16_t> probe;
+                    std::vector<uint16_t> scratch;
+                    for (;;) {
+                        const size_t k = nextSearch.fetch_add(1);
+                        if (k >= nChunks) return;
+                        const uint64_t found = mdbg_host::gzip_find_block(addr, addr + size, (uint64_t)k * chunk * 8, (uint64_t)(k + 1) * chunk * 8, probe, scratch);
+                        std::lock_guard<std::mutex> g(mu);
+                        start[k] = found;
+                        known[k] = 1;
+                        cv.notify_all();
+                    }
+                });
+        }
+        uint64_t wait_start(size_t k) {
+            std::unique_lock<std::mutex> g(mu);
+            cv.wait(g, [&] { return known[k] != 0; });
+            return start[k];
+        }
+        void join() { for (auto &t : workers) t.join(); workers.clear(); }
+    };
+    struct Slab { const char *p; size_t n; int file; int bgzf; int gz; };        // bgzf >= 0: the whole of bgzfs[bgzf], gz >= 0: of gzips[gz], cut into slabs as it is inflated
     std::vector<Slab> slabs;            // whole records each, in read order
     std::vector<Bgzf> bgzfs;
+    std::vector<std::unique_ptr<Gzip>> gzips;
     size_t maxSlab = 0;
     std::vector<std::pair<void *, size_t>> maps;
 
@@ -352,10 +414,61 @@ struct DeviceParsePlan {
         return true;
     }
 
-    // true: every file of the list is plain text or pure BGZF that begins with '>' or '@' (FASTQ: four lines a record).  Plain files are
+    // The first member of a gzip file inflated on the host, until 1 MB of text: what the plain files' checks look at.  false: it does not inflate
+    static bool gzip_prefix(const unsigned char *addr, size_t size, std::string &text) {
+        const size_t h = mdbg_host::gzip_header_size(addr, size);
+        if (!h) return false;
+        mdbg_host::Inflater inf;
+        std::vector<uint8_t> buf(((size_t)1 << 20) + 512);
+        inf.reset(addr + h, addr + size);
+        size_t produced = 0;
+        if (inf.run(buf.data(), buf.data() + buf.size(), 0, &produced) == mdbg_host::Inflater::CORRUPT) return false;
+        text.assign((const char *)buf.data(), produced);
+        return true;
+    }
+    // a gzip file that is not BGZF joins the plan; false: `why` says what stands against it
+    bool add_gzip(const std::string &path, const unsigned char *addr, size_t size, int file, int threads, int gpus, std::string &why) {
+        if (!mdbg_bytes_inflate_gzip || !mdbg_gzip_stream_create || !mdbg_gzip_stream_free || !mdbg_bytes_copy) { why = path + " is gzip but not BGZF and the library has no mdbg_bytes_inflate_gzip"; return false; }
+        if (gpus > 1) { why = path + " is gzip but not BGZF: its chunks are inflated on one device, and --gpus is " + std::to_string(gpus); return false; }
+        std::string head;
+        if (!gzip_prefix(addr, size, head)) { why = path + " is gzip but not BGZF and its first member does not inflate"; return false; }
+        if (head.empty()) { why = path + " is gzip but not BGZF and begins with an empty member"; return false; }
+        const bool fastq = head[0] == '@';
+        if (!fastq && head[0] != '>') { why = path + " does not begin with '>' or '@'"; return false; }
+        if (fastq && !mdbg_host::ReadFeeder::fastq_is_four_line(head.data(), head.data() + head.size())) { why = path + " is not four-line FASTQ, which the device parse refuses"; return false; }
+        std::unique_ptr<Gzip> g(new Gzip());
+        g->path = path; g->addr = addr; g->size = size;
+        if (const char *e = getenv("MDBG_TOOL_GZIP_CHUNK_KB")) g->chunk = (size_t)std::max(16, atoi(e)) << 10;
+        g->nChunks = (size + g->chunk - 1) / g->chunk;
+        g->start.assign(g->nChunks, Gzip::NONE);
+        g->known.assign(g->nChunks, 0);
+        g->start[0] = 0; g->known[0] = 1;
+        // a stream of stored blocks has no header the search finds, and would decode on one wave: the host feed takes it
+        if (g->nChunks > 2) {
+            g->search(1); g->search(2);
+            if (g->start[1] == Gzip::NONE && g->start[2] == Gzip::NONE) {
+                why = path + " is gzip but not BGZF, and no deflate block header is to be found in its second and third chunk (stored blocks, or members of one block): it would inflate on one wave of the device";
+                return false;
+            }
+        }
+        // A call of few chunks occupies a fraction of the device's waves and still pays a whole chunk's latency on one lane (DESIGN.md
+        // 4.3c, 6): a file of fewer than 32 chunks is left to the host feed, which has it decoded before the first call would return.
+        if (g->nChunks < 32) {
+            why = path + " is gzip but not BGZF and holds " + std::to_string(g->nChunks) + " chunk(s) of " + std::to_string(g->chunk >> 10) +
+                  " KB: fewer than the 32 from which the device takes a gzip file";
+            return false;
+        }
+        g->nextSearch = g->nChunks > 2 ? 3 : 1;
+        g->run_workers(std::max(1, std::min(threads, 16)));
+        slabs.push_back(Slab{nullptr, 0, file, -1, (int)gzips.size()});
+        gzips.push_back(std::move(g));
+        return true;
+    }
+
+    // true: every file of the list is plain text, pure BGZF or ordinary gzip that begins with '>' or '@' (FASTQ: four lines a record).  Plain files are
     // mapped and cut at record starts by the feeder's own search into slabs of at most batchBases bytes; a BGZF file is one entry that
     // the consumers cut as its text appears on the device.  false: `why` says what stands against it
-    bool make(const std::vector<std::string> &files, size_t batchBases, std::string &why) {
+    bool make(const std::vector<std::string> &files, size_t batchBases, int threads, int gpus, std::string &why) {
         using mdbg_host::ReadFeeder;
         if (!mdbg_reads_from_fastx_bytes) { why = "the library has no mdbg_reads_from_fastx_bytes"; return false; }
         for (size_t f = 0; f < files.size(); f++) {
@@ -379,7 +492,10 @@ struct DeviceParsePlan {
                 Bgzf z;
                 z.path = path;
                 z.addr = (const unsigned char *)addr;
-                if (!mdbg_host::BgzfReader::index(z.addr, (size_t)st.st_size, z.blocks)) { why = path + " is gzip but not BGZF"; return false; }
+                if (!mdbg_host::BgzfReader::index(z.addr, (size_t)st.st_size, z.blocks)) {
+                    if (!add_gzip(path, z.addr, (size_t)st.st_size, (int)f, threads, gpus, why)) return false;
+                    continue;
+                }
                 z.cum.assign(z.blocks.size() + 1, 0);
                 for (size_t i = 0; i < z.blocks.size(); i++) z.cum[i + 1] = z.cum[i] + z.blocks[i].isize;
                 if (z.cum.back() == 0) continue;                        // nothing but empty blocks: no reads
@@ -391,7 +507,7 @@ struct DeviceParsePlan {
                     why = path + " is not four-line FASTQ, which the device parse refuses";
                     return false;
                 }
-                slabs.push_back(Slab{nullptr, 0, (int)f, (int)bgzfs.size()});
+                slabs.push_back(Slab{nullptr, 0, (int)f, (int)bgzfs.size(), -1});
                 bgzfs.push_back(std::move(z));
                 continue;
             }
@@ -405,14 +521,24 @@ struct DeviceParsePlan {
                     q = ReadFeeder::cut_at_record_start(p, p + batchBases, end, fastq);
                     if (q == p) die("a single read is larger than the batch size; raise --batch-bases");
                 }
-                slabs.push_back(Slab{p, (size_t)(q - p), (int)f, -1});
+                slabs.push_back(Slab{p, (size_t)(q - p), (int)f, -1, -1});
                 maxSlab = std::max(maxSlab, (size_t)(q - p));
                 p = q;
             }
         }
         return true;
     }
-    void unmap() { for (auto &m : maps) munmap(m.first, m.second); maps.clear(); }
+    void unmap() {
+        for (auto &g : gzips) {
+            g->nextSearch = g->nChunks;                 // (a plan given up: the searches end with the chunk they are in)
+            g->join();
+            if (g->rest) mdbg_bytes_free(g->rest);
+            if (g->stream) mdbg_gzip_stream_free(g->stream);
+            g->rest = nullptr; g->stream = nullptr;
+        }
+        for (auto &m : maps) munmap(m.first, m.second);
+        maps.clear();
+    }
 };
 
 mdbg_scan_params scan_params(const Parameters &P, float density, const std::vector<uint32_t> &rep, float minQ, bool filters) {
@@ -760,10 +886,15 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         DeviceParsePlan devParse;
         bool deviceParse = false;
         if (const char *e = getenv("MDBG_TOOL_DEVICE_PARSE")) {
-            if (atoi(e) != 0) {
+            if (atoi(e) != 0 && getenv("MDBG_TOOL_PARSE_ON_HOST")) g_trace.mark("device parse: MDBG_TOOL_PARSE_ON_HOST is set: the host feed");
+            else if (atoi(e) != 0) {
                 std::string why;
-                deviceParse = devParse.make(read_input_list(inputList), std::max<size_t>(1, a.batchBases), why);
-                if (deviceParse && devParse.bgzfs.empty())
+                deviceParse = devParse.make(read_input_list(inputList), std::max<size_t>(1, a.batchBases), a.threads, std::max(1, a.gpus), why);
+                if (deviceParse && !devParse.gzips.empty())
+                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size() - devParse.bgzfs.size() - devParse.gzips.size()) +
+                                  " slab(s) of plain text, " + std::to_string(devParse.bgzfs.size()) + " BGZF file(s) and " + std::to_string(devParse.gzips.size()) +
+                                  " gzip file(s) cut into chunks at deflate block headers, inflated there and cut into slabs").c_str());
+                else if (deviceParse && devParse.bgzfs.empty())
                     g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size()) + " slab(s)").c_str());
                 else if (deviceParse)
                     g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size() - devParse.bgzfs.size()) +
@@ -782,6 +913,9 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         size_t bgzfBlock = 0;
         uint64_t bgzfBegin = 0;
         uint64_t bgzfSlabs = 0, bgzfInflated = 0, bgzfBlocks = 0;
+        // gzip files are inflated by a context of their own (under feedMu): a stream belongs to one context, the consumers take turns
+        mdbg_ctx *gzCtx = nullptr;
+        uint64_t gzSlabs = 0, gzChunks = 0, gzCalls = 0;
         const size_t batchText = std::max<size_t>(1, a.batchBases);
         auto consume = [&](int ci) {
             mdbg_ctx *ctx = ctxs[(size_t)ci];
@@ -856,6 +990,98 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                     do sum += z.blocks[b1++].isize; while (b1 < nb && sum < upto && sum + z.blocks[b1].isize <= batchText);
                 }
             };
+            // The next slab of the gzip file `G` (feedMu held).  A group of chunks -- about a quarter of batchText in compressed bytes, one
+            // chunk at the least -- goes up from the mapping and is inflated behind the unfinished record the last slab left
+            // (mdbg_bytes_copy); all but the file's last slab end behind their last whole record (mdbg_fastx_whole_records).  The text
+            // buffer is sized by a guess; MDBG_ERANGE names the room needed and leaves the stream where it was.  A start the search
+            // guessed wrong ends the run with the device's message: nothing is guessed silently.
+            auto next_gzip_slab = [&](DeviceParsePlan::Gzip &G, mdbg_bytes **text, uint64_t *begin, uint64_t *end) -> bool {
+                using Gz = DeviceParsePlan::Gzip;
+                auto gz_die = [&](const std::string &what) {
+                    die(G.path + ": " + what + " -- set MDBG_TOOL_PARSE_ON_HOST=1 (or run without MDBG_TOOL_DEVICE_PARSE) for the host feed");
+                };
+                if (!gzCtx) {
+                    if (mdbg_create(0, &gzCtx) != MDBG_OK) die(std::string("mdbg_create (gzip inflation): ") + mdbg_last_error(nullptr));
+                    g_more_ctx.push_back(gzCtx);
+                }
+                if (!G.stream) check_on(gzCtx, mdbg_gzip_stream_create(gzCtx, &G.stream), "mdbg_gzip_stream_create");
+                for (;;) {
+                    if (G.ended) {
+                        if (G.rest) { mdbg_bytes_free(G.rest); G.rest = nullptr; }
+                        if (G.nRest) gz_die("the file ends inside a record");      // (the last slab is parsed whole: nothing is left behind it)
+                        return false;
+                    }
+                    const uint64_t target = std::max<uint64_t>(G.chunk, batchText / 4);
+                    std::vector<mdbg_gzip_chunk> table;
+                    uint64_t cur = G.atBit;
+                    size_t k = G.nextK;
+                    for (;;) {
+                        uint64_t s = Gz::NONE;
+                        while (k < G.nChunks && s == Gz::NONE) {
+                            const uint64_t f = G.wait_start(k++);
+                            if (f != Gz::NONE && f > cur) s = f;
+                        }
+                        if (s == Gz::NONE) { table.push_back(mdbg_gzip_chunk{cur, MDBG_GZIP_TO_END}); break; }
+                        table.push_back(mdbg_gzip_chunk{cur, s});
+                        cur = s;
+                        if ((s >> 3) - (G.atBit >> 3) >= target) break;
+                    }
+                    const uint64_t stop = table.back().stop_bit;
+                    const uint64_t base = G.atBit >> 3, top = stop == MDBG_GZIP_TO_END ? G.size : (stop + 7) / 8;
+                    for (mdbg_gzip_chunk &c : table) {
+                        if (((c.stop_bit == MDBG_GZIP_TO_END ? G.size : (c.stop_bit + 7) / 8) - (c.start_bit >> 3)) > ((uint64_t)1 << 21))
+                            gz_die("no deflate block header was found in 2 MB behind bit " + std::to_string(c.start_bit));
+                        c.start_bit -= base * 8;
+                        if (c.stop_bit != MDBG_GZIP_TO_END) c.stop_bit -= base * 8;
+                    }
+                    mdbg_bytes *comp = nullptr;
+                    check_on(gzCtx, mdbg_bytes_create(gzCtx, top - base, &comp), "mdbg_bytes_create");
+                    check_on(gzCtx, mdbg_bytes_upload_async(gzCtx, comp, 0, G.addr + base, top - base, nullptr), "mdbg_bytes_upload_async");
+                    uint64_t room = G.nRest + 5 * (top - base) + 65536, n_text = 0, info[4] = {0, 0, 0, 0};
+                    for (int attempt = 0;; attempt++) {
+                        check_on(gzCtx, mdbg_bytes_create(gzCtx, room, text), "mdbg_bytes_create");
+                        if (G.nRest) check_on(gzCtx, mdbg_bytes_copy(gzCtx, *text, 0, G.rest, 0, G.nRest), "mdbg_bytes_copy");
+                        const int rc = mdbg_bytes_inflate_gzip(gzCtx, G.stream, comp, table.data(), table.size(), *text, G.nRest, &n_text, info);
+                        if (rc == MDBG_OK) break;
+                        mdbg_bytes_free(*text);
+                        *text = nullptr;
+                        if (rc != MDBG_ERANGE || attempt) {
+                            mdbg_bytes_free(comp);
+                            gz_die(std::string(mdbg_last_error(gzCtx)) + " (the chunks of this call begin at bit " + std::to_string(G.atBit) + " of the file; a chunk start is a guess of the header search)");
+                        }
+                        room = G.nRest + n_text;
+                    }
+                    mdbg_bytes_free(comp);
+                    G.nCalls++; G.nChunksInflated += table.size();
+                    gzCalls++; gzChunks += table.size();
+                    const uint64_t n = G.nRest + n_text;
+                    if (G.rest) { mdbg_bytes_free(G.rest); G.rest = nullptr; }
+                    G.nRest = 0;
+                    G.atBit = base * 8 + info[3];
+                    G.nextK = k;
+                    *begin = 0;
+                    *end = n;
+                    if (info[2]) {                                               // the file's last slab is parsed whole
+                        G.ended = true;
+                        if (n == 0) { mdbg_bytes_free(*text); *text = nullptr; return false; }
+                        return true;
+                    }
+                    if (stop == MDBG_GZIP_TO_END) gz_die("the device stopped in front of the file's end");
+                    uint64_t cut = 0;
+                    int format = 0;
+                    if (n) check_on(gzCtx, mdbg_fastx_whole_records(gzCtx, *text, 0, n, &cut, &format), "mdbg_fastx_whole_records");
+                    if (cut < n) {                                               // the unfinished record goes in front of the next text
+                        check_on(gzCtx, mdbg_bytes_create(gzCtx, n - cut, &G.rest), "mdbg_bytes_create");
+                        check_on(gzCtx, mdbg_bytes_copy(gzCtx, G.rest, 0, *text, cut, n - cut), "mdbg_bytes_copy");
+                        G.nRest = n - cut;
+                    }
+                    if (cut > 0) { *end = cut; return true; }
+                    // not one whole record yet: more chunks
+                    mdbg_bytes_free(*text);
+                    *text = nullptr;
+                    if (n > batchText) die("a single read is larger than the batch size; raise --batch-bases");
+                }
+            };
             auto stage_text = [&]() -> Staged {
                 Staged st;
                 size_t idx;
@@ -866,7 +1092,15 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                     for (;;) {
                         idx = nextSlab;
                         if (idx >= devParse.slabs.size()) return st;
-                        const int zi = devParse.slabs[idx].bgzf;
+                        const int zi = devParse.slabs[idx].bgzf, gi = devParse.slabs[idx].gz;
+                        if (gi >= 0) {
+                            const double t0 = g_trace.now();
+                            const bool got = next_gzip_slab(*devParse.gzips[(size_t)gi], &text, &begin, &end);
+                            up += g_trace.now() - t0;
+                            if (got) { gzSlabs++; break; }
+                            nextSlab++;                          // this file is done
+                            continue;
+                        }
                         if (zi < 0) { nextSlab++; break; }
                         const double t0 = g_trace.now();
                         const bool got = next_bgzf_slab(devParse.bgzfs[(size_t)zi], &text, &begin, &end);
@@ -1017,6 +1251,9 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
         for (auto &t : consumers) t.join();
         g_trace.mark("last batch scanned and handed to the writer");
         devParse.unmap();                       // every slab has been copied and parsed
+        if (!devParse.gzips.empty() && getenv("MDBG_TRACE"))
+            fprintf(stderr, "[mdbg_tool] device parse: %llu chunk(s) of %zu gzip file(s) inflated on the device in %llu call(s), %llu slab(s)\n", (unsigned long long)gzChunks,
+                    devParse.gzips.size(), (unsigned long long)gzCalls, (unsigned long long)gzSlabs);
         if (!devParse.bgzfs.empty() && getenv("MDBG_TRACE"))
             fprintf(stderr, "[mdbg_tool] device parse: %llu BGZF block(s) of %zu file(s) inflated on the device in %llu slab(s) (%llu block inflations: a slab's first block may "
                             "be the one its predecessor ended in)\n", (unsigned long long)bgzfBlocks, devParse.bgzfs.size(), (unsigned long long)bgzfSlabs,
