@@ -93,6 +93,15 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *   "scan_prefilter_log2_bits"  tests only: the bitmap is built and probed with 2^value bits (10 .. 19; 0 = the kernel's own 2^19) and
  *                           used whatever its fill, so that nearly every position reaches the confirmation with the full hash and its
  *                           list overflows.  Results never depend on it
+ *   "scan_confirm_table"    1 = the pre-filtered variant takes the exact verdict of a position that passed its bitmap from a table of
+ *                           the selected keys in global memory (1 MB: 2^16 buckets of seven 16-bit tags, one 16-byte load a candidate; built
+ *                           on the device beside the bitmap, rebuilt and freed with it) instead of hashing the key; a key of a bucket that
+ *                           holds more than seven -- none at density 0.005, a handful at 0.01 -- is hashed as before.  0 (default) = every candidate
+ *                           is hashed: alone the kernel is 0.3 - 1.1 % faster with the table, beside another batch's table kernels it is not
+ *                           (DESIGN.md 4.1).  The environment variable MDBG_SCAN_CONFIRM_TABLE=0 / 1 sets the default of new contexts.  Results
+ *                           never depend on it; mdbg_scan_confirm_info tells which path ran
+ *   "scan_confirm_table_log2_buckets"  tests only: the table is built and probed with 2^value buckets (10 .. 16; 0 = the kernel's own 2^16), so
+ *                           that most buckets overflow and looked-up and hashed verdicts mix in one round.  Results never depend on it
  *   "scan_segments"         long reads, contigs and unitigs cut into segments that the block-structured scan takes one wave each: a plain read
  *                           (no N, no case flip) of more than one segment is scanned as several views -- each owns the windows that start
  *                           in its segment and reads one 2048-base tile on behind it -- and the views' rows are joined in read order.
@@ -361,6 +370,10 @@ int  mdbg_kernel_attributes(mdbg_ctx *ctx, const char *kernel, uint64_t attr[8])
  * the last block-kernel launch was the pre-filtered variant, [7] = reads the context's last mdbg_scan scanned as segments ("scan_segments";
  * reads that fell back whole are not counted).  No reference analogue: the reference hashes every position. */
 int  mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]);
+/* The selected-key table of the pre-filtered variant's confirmation ("scan_confirm_table" above): info[0] = tables built, [1] = buckets of
+ * the last one, [2] = buckets of it that ask the hash (more than seven keys; or, in a test geometry below 2^16 buckets, a tag shared with a
+ * key that is not selected), [3] = 1 when the last pre-filtered launch took its verdicts from the table, 0 when it hashed its candidates. */
+int  mdbg_scan_confirm_info(const mdbg_ctx *ctx, uint64_t info[4]);
 /* Order-independent sums over the rows, wrapping at 2^64, computed on the device (nothing but 32 bytes travels):
  *   sums[0] = sum abundance * hash_lo -- the "Checksum kminmer abundance" the reference logs when it loads the table again
  *             (CreateMdbg::loadRefinedAbundances, graph/CreateMdbg.cpp:3300-3321, :3397: `abundance * vecHash` truncated to u64),

@@ -89,6 +89,7 @@ SIGNATURES = {
     "mdbg_table_stats": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_info": (C.c_int, [_P, _u64p]),
     "mdbg_scan_info": (C.c_int, [_P, _u64p]),
+    "mdbg_scan_confirm_info": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_form": (C.c_int, [_P, _u64p]),
     "mdbg_step_kernel_name": (C.c_char_p, [C.c_uint32]),
     "mdbg_kernel_attributes": (C.c_int, [_P, C.c_char_p, _u64p]),
@@ -242,6 +243,13 @@ class Context:
         self.check(lib().mdbg_scan_info(self.h, a))
         names = ("prefiltered_launches", "block_launches", "bitmaps_built", "bitmap_bits_set", "bitmap_log2_bits", "prefilter_waves",
                  "last_prefiltered", "reads_segmented")
+        return {k: int(v) for k, v in zip(names, a)}
+
+    def scan_confirm_info(self) -> dict:
+        """The selected-key table of the pre-filtered scan's confirmation (mdbg_scan_confirm_info)."""
+        a = (C.c_uint64 * 4)()
+        self.check(lib().mdbg_scan_confirm_info(self.h, a))
+        names = ("tables_built", "table_buckets", "table_overflowed", "last_by_table")
         return {k: int(v) for k, v in zip(names, a)}
 
     # -- timing ---------------------------------------------------------------------------

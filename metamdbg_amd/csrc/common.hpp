@@ -155,6 +155,15 @@ struct mdbg_ctx {
     bool prefilter_valid = false;
     uint64_t prefilter_threshold = 0;
     uint32_t prefilter_log2 = 0, prefilter_set = 0;
+    // ... and the selected-key table its confirm step takes exact verdicts from (prefilter.hpp), built and freed with the bitmap
+    uint32_t scan_confirm_table = 0;        // "scan_confirm_table": 1 = candidates are looked up, 0 = hashed (default: DESIGN.md 4.1) (mdbg_set_option, MDBG_SCAN_CONFIRM_TABLE)
+    uint32_t scan_confirm_table_log2_buckets = 0;   // tests: a table of 2^10 .. 2^16 buckets, most of which overflow and ask the hash; 0 = 2^16
+    uint32_t *confirm_table = nullptr;      // device: 2^16 buckets of 16 bytes (whatever the geometry) + the count of overflowed buckets
+    bool confirm_valid = false;
+    uint64_t confirm_threshold = 0;
+    uint32_t confirm_log2 = 0;
+    uint64_t scan_confirm_info[4] = {0};    // mdbg_scan_confirm_info: [0] tables built, [1] buckets of the last, [2] its overflowed buckets, [3] 1 when the
+                                            // last pre-filtered launch took its verdicts from the table
     uint32_t scan_segments = 1;             // "scan_segments": plain reads of more than one segment are cut into views, one wave each (scan.hip, segments_dev.hpp) --
                                             // 1 = automatic (default): in a batch that would leave the block-structured kernels for its reads' length alone, 0 = never,
                                             // 2 = in every batch those kernels take (opt-in: its pre-pass costs more than it gains) (mdbg_set_option, MDBG_SCAN_SEGMENTS)

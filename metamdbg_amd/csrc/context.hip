@@ -67,6 +67,7 @@ extern "C" int mdbg_create(int device, mdbg_ctx **out) try {
     if (const char *e = getenv("MDBG_SCAN_READS_PER_WAVE")) if (atoi(e) > 0) ctx->scan_reads_per_wave = (unsigned)atoi(e);
     if (const char *e = getenv("MDBG_SCAN_LDS_RESERVE")) ctx->scan_lds_reserve = (uint32_t)std::max(0, std::min(131072, atoi(e)));
     if (const char *e = getenv("MDBG_SCAN_PREFILTER")) ctx->scan_prefilter = atoi(e) != 0;
+    if (const char *e = getenv("MDBG_SCAN_CONFIRM_TABLE")) ctx->scan_confirm_table = atoi(e) != 0;
     if (const char *e = getenv("MDBG_SCAN_SEGMENTS")) ctx->scan_segments = atoi(e) == 0 ? 0u : (atoi(e) == 2 ? 2u : 1u);
     if (const char *e = getenv("MDBG_SCAN_LDS_PAD")) ctx->scan_lds_pad = (uint32_t)std::max(0, std::min(32768, atoi(e)));
     if (const char *e = getenv("MDBG_PARTITION_TILE")) ctx->part_tile = atoi(e) == 2048 ? 2048u : 0u;
@@ -103,6 +104,7 @@ extern "C" void mdbg_destroy(mdbg_ctx *ctx) {
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->prefilter_bits) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->prefilter_bits); }
+    if (ctx->confirm_table) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->confirm_table); }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -188,6 +190,11 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
     if (n == "scan_candidate_slack") { ctx->scan_cand_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 1 << 24) : 0u; return MDBG_OK; }
     if (n == "scan_guard_slack") { ctx->scan_guard_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll - 68) : 0u; return MDBG_OK; }
     if (n == "scan_prefilter") { ctx->scan_prefilter = value != 0; return MDBG_OK; }
+    if (n == "scan_confirm_table") { ctx->scan_confirm_table = value != 0; return MDBG_OK; }
+    if (n == "scan_confirm_table_log2_buckets") {
+        if (value != 0 && (value < 10 || value > 16)) return set_error(ctx, MDBG_EINVAL, "scan_confirm_table_log2_buckets: 0 (the kernel's own) or 10 .. 16");
+        ctx->scan_confirm_table_log2_buckets = (uint32_t)value; return MDBG_OK;
+    }
     if (n == "scan_segments") {
         if (value > 2) return set_error(ctx, MDBG_EINVAL, "scan_segments: 0 (never), 1 (automatic, the default; negative too) or 2 (every eligible read)");
         ctx->scan_segments = value < 0 ? 1u : (uint32_t)value; return MDBG_OK;

@@ -100,6 +100,8 @@ struct ScanArgs {
     const uint32_t *pf_bits;
     uint32_t pf_shift;            // 32 - log2(bits of the bitmap): a key's bit is (v * 0x9E3779B1) >> pf_shift
     uint32_t pf_chunk;            // reads a workgroup deals out to its waves
+    const uint4 *pf_table;        // the selected-key table confirm looks its candidates up in (prefilter.hpp); null: confirm hashes them
+    uint32_t pf_table_shift;      // 32 - log2(buckets of the table)
     uint32_t pf_len_split;        // > 0: that variant passes over the reads of this many bases or more -- too long for its stage, they are
                                   // the four-wave kernel's, launched in front of it with the other reads flagged in `skip` (launch_scan)
     // scan_fast_kernel<.., SEG> (views of long reads, segments_dev.hpp): n_reads counts views, and out_begin / out_count / out_flags /
@@ -928,6 +930,8 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
     uint16_t *pf_list = PF ? pf_list_all + wv * PF_LIST_CAP : nullptr;
     uint32_t *pf_surv = PF ? pf_surv_all + wv * 64u : nullptr;
     const uint32_t pf_shift = a.pf_shift;
+    const uint4 *const pf_table = PF ? a.pf_table : nullptr;      // wave-uniform; null: confirm hashes its candidates
+    const uint32_t pf_table_shift = a.pf_table_shift;
     // PF: the workgroup's chunk of reads [chunk0, chunk0 + chunk_n) is dealt out read by read; NO_READ when it is used up
     constexpr uint32_t NO_READ = 0xFFFFFFFFu;               // no read has this index: n_reads is a 32-bit count
     const uint64_t chunk0 = (uint64_t)blockIdx.x * a.pf_chunk;
@@ -1083,8 +1087,9 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         // ---- emission: list the positions recorded in `bits` (span length P per lane, oldest position in bit P-1) ----
         auto emit = [&](uint32_t bits, unsigned P, uint32_t npos_limit) {
             // positions at or beyond npos_limit (tail lanes past the end) and the trimmed first position of the read
-            if (P < 32u) bits &= (1u << P) - 1u;
-            {
+            // (PF: confirm has masked them already and hands back a subset of what it kept)
+            if constexpr (!PF) {
+                if (P < 32u) bits &= (1u << P) - 1u;
                 const uint32_t first_j = lane * P;                 // span-relative index of this lane's first position
                 if (first_j >= npos_limit) bits = 0;
                 else if (first_j + P > npos_limit) bits &= ~((1u << (first_j + P - npos_limit)) - 1u);
@@ -1110,7 +1115,8 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             if (bump) {
                 if (outgrown || nout + total > (unsigned)Geo::STAGE) {
                     if (!outgrown) { materialise(); n_staged_at_outgrowth = nout; }
-                    if (APPROX) {          // the count the host places the read by must be exact: hash the candidates in full
+                    if (APPROX && !PF) {   // the count the host places the read by must be exact: hash the candidates in full (PF: confirm's
+                                           // verdicts are exact already)
                         uint32_t bad = 0;
                         while (bits) {
                             const unsigned bit = 31u - (unsigned)__clz((int)bits);
@@ -1190,11 +1196,10 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 if (done == 0u && lane == 0u && trim_first) bits &= ~(1u << (P - 1u));
             }
             uint32_t kept = 0u;
-            for (;;) {
-                const unsigned cnt = (unsigned)__popc(bits);
-                const unsigned incl = wave_inclusive_sum_dpp(cnt);
-                const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-                if (total == 0u) break;
+            unsigned cnt = (unsigned)__popc(bits);
+            unsigned incl = wave_inclusive_sum_dpp(cnt);
+            unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+            while (total != 0u) {
                 pf_surv[lane] = 0u;
                 unsigned at = incl - cnt;
                 while (bits && at < PF_LIST_CAP) {
@@ -1204,15 +1209,61 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 }
                 const unsigned n = total < PF_LIST_CAP ? total : PF_LIST_CAP;
                 wave_lds_sync();
-                for (unsigned i = lane; i < n; i += 64u) {
-                    const uint32_t q = pf_list[i], owner = q >> 5, bit = q & 31u;
-                    const uint32_t e = ring_window(S, done + owner * P + (P - 1u - bit), Geo::RING_WMASK) & kmask;
+                // the key of listed position q (6 bits of owner lane, 5 of bit)
+                auto listed_key = [&](uint32_t q) -> uint32_t {
+                    const uint32_t e = ring_window(S, done + (q >> 5) * P + (P - 1u - (q & 31u)), Geo::RING_WMASK) & kmask;
                     const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
-                    if (kmer_hash32(fw < rev ? fw : rev) < threshold) atomicOr(&pf_surv[owner], 1u << bit);
+                    return fw < rev ? fw : rev;
+                };
+                if (pf_table != nullptr) {
+                    // the verdicts from the selected-key table (prefilter.hpp): the loads of every round of the pass are issued before
+                    // the first is waited for; a lane without a listed position keeps a bucket of zeros, which selects nothing
+                    constexpr unsigned ROUNDS = (PF_LIST_CAP + 63u) / 64u;
+                    uint32_t lh[ROUNDS];
+                    uint4 lw[ROUNDS];
+#pragma unroll
+                    for (unsigned k = 0; k < ROUNDS; k++) {
+                        lh[k] = 0u; lw[k] = make_uint4(0u, 0u, 0u, 0u);
+                        if (64u * k < n) {
+                            const unsigned i = lane + 64u * k;
+                            if (i < n) {
+                                lh[k] = confirm_hash(listed_key(pf_list[i]));
+                                lw[k] = pf_table[lh[k] >> pf_table_shift];
+                            }
+                        }
+                    }
+                    uint32_t ask = 0u;
+#pragma unroll
+                    for (unsigned k = 0; k < ROUNDS; k++) {
+                        if (64u * k < n) {
+                            const uint32_t verdict = confirm_verdict(lw[k].x, lw[k].y, lw[k].z, lw[k].w, lh[k]);
+                            if (verdict == CONFIRM_YES) { const uint32_t q = pf_list[lane + 64u * k]; atomicOr(&pf_surv[q >> 5], 1u << (q & 31u)); }
+                            if (verdict == CONFIRM_ASK) ask |= 1u << k;
+                        }
+                    }
+                    // keys of buckets the builder marked ask the hash (no bucket is marked at density 0.005f): one loop for all rounds
+                    if (__ballot(ask != 0u) != 0ull) {
+#pragma nounroll
+                        for (unsigned k = 0; k < ROUNDS; k++) {
+                            if ((ask >> k) & 1u) {
+                                const uint32_t q = pf_list[lane + 64u * k];
+                                if (kmer_hash32(listed_key(q)) < threshold) atomicOr(&pf_surv[q >> 5], 1u << (q & 31u));
+                            }
+                        }
+                    }
+                } else {
+                    for (unsigned i = lane; i < n; i += 64u) {
+                        const uint32_t q = pf_list[i];
+                        if (kmer_hash32(listed_key(q)) < threshold) atomicOr(&pf_surv[q >> 5], 1u << (q & 31u));
+                    }
                 }
                 wave_lds_sync();
                 kept |= pf_surv[lane];
+                if (total <= PF_LIST_CAP) break;      // everything was listed: nothing is left in `bits`
                 wave_lds_sync();          // read before the next pass clears the words
+                cnt = (unsigned)__popc(bits);
+                incl = wave_inclusive_sum_dpp(cnt);
+                total -= PF_LIST_CAP;
             }
             return kept;
         };
@@ -1473,17 +1524,17 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             release_ring(((fill + 15u) & ~15u) + 16u);
         }
 
-        if (APPROX) {
+        if (APPROX && !PF) {
             // the full hash of every staged position, once per read (a block stages about ten of them: confirming them there kept
             // five lanes in six idle); a false one loses the read to the re-run.  The positions of a read that outgrew the stage
-            // after these were confirmed as they came (emit)
+            // after these were confirmed as they came (emit).  (PF: every staged position passed confirm, whose verdicts are exact)
             const uint32_t n_staged = outgrown ? n_staged_at_outgrowth : nout;
             for (uint32_t i = lane; i < ((n_staged + 63u) & ~63u); i += 64) {
                 const uint64_t fb = __ballot(i < n_staged && !(kmer_hash32(stage[i].x) < threshold));
                 if (fb) { n_false += (uint32_t)__popcll(fb); lost = true; }
             }
         }
-        if (((QUAL && HPC) || APPROX) && __ballot(lost) != 0ull) outgrown = true;      // a run start had left the history, or a false candidate:
+        if (((QUAL && HPC) || (APPROX && !PF)) && __ballot(lost) != 0ull) outgrown = true;      // a run start had left the history, or a false candidate:
                                                                                         // the general kernel redoes the read
         uint8_t flags = 0;
         if constexpr (SEG) {          // the read's decision is the join's, over the sums of all its views
@@ -1543,6 +1594,24 @@ __global__ __launch_bounds__(256) void prefilter_build_kernel(uint32_t *bitmap, 
         const uint32_t bit = 1u << (idx & 31u);
         if (!(atomicOr(&bitmap[idx >> 5], bit) & bit)) atomicAdd(n_set, 1u);
     });
+}
+
+// The selected-key table of the variant's confirm step (prefilter.hpp), built beside the bitmap in the header's three steps: `table`
+// and `counts` zeroed by the caller, the buckets marked "ask the hash" counted in *n_over.
+struct ConfirmAtomicOps {
+    __device__ uint32_t add(uint32_t *p, uint32_t v) const { return atomicAdd(p, v); }
+    __device__ uint32_t orr(uint32_t *p, uint32_t v) const { return atomicOr(p, v); }
+};
+__global__ __launch_bounds__(256) void confirm_table_insert_kernel(uint32_t *table, uint32_t *counts, uint64_t threshold, unsigned log2_buckets) {
+    confirm_table_insert_range(blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, threshold, log2_buckets, table, counts, ConfirmAtomicOps());
+}
+__global__ __launch_bounds__(256) void confirm_table_finish_kernel(uint32_t *table, const uint32_t *counts, unsigned log2_buckets, uint32_t *n_over) {
+    for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < (1u << log2_buckets); b += gridDim.x * 256u)
+        if (confirm_table_finish_bucket(table + (size_t)b * CONFIRM_BUCKET_WORDS, counts[b])) atomicAdd(n_over, 1u);
+}
+__global__ __launch_bounds__(256) void confirm_table_verify_kernel(uint32_t *table, uint64_t threshold, unsigned log2_buckets, uint32_t *n_over) {
+    confirm_table_verify_range(blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, threshold, log2_buckets, table, ConfirmAtomicOps(),
+                               [&]() { atomicAdd(n_over, 1u); });
 }
 
 // A batch the pre-filtered variant shares with the four-wave kernel: the reads the four-wave launch leaves alone -- those shorter than
@@ -1948,6 +2017,42 @@ static int prefilter_ensure(mdbg_ctx *ctx, uint64_t threshold, unsigned log2_bit
         ctx->scan_info[2]++; ctx->scan_info[3] = n_set; ctx->scan_info[4] = log2_bits;
     }
     *fill_ok = forced || (uint64_t)ctx->prefilter_set * 4ull <= (1ull << log2_bits);
+    // the selected-key table of the confirm step, for the same threshold: rebuilt with it or when its own geometry changes
+    if (*fill_ok && ctx->scan_confirm_table) {
+        constexpr size_t TABLE_WORDS = ((size_t)1 << CONFIRM_LOG2_BUCKETS) * CONFIRM_BUCKET_WORDS;      // allocated once, whatever the geometry
+        const unsigned log2_buckets = ctx->scan_confirm_table_log2_buckets ? ctx->scan_confirm_table_log2_buckets : CONFIRM_LOG2_BUCKETS;
+        if (!ctx->confirm_table) {
+            std::lock_guard<std::mutex> g(hip_mem_mutex());
+            hipError_t e = hipMalloc((void **)&ctx->confirm_table, (TABLE_WORDS + 4) * 4);
+            if (e != hipSuccess) { ctx->confirm_table = nullptr; return set_error(ctx, MDBG_ENOMEM, "hipMalloc of the scan's key table: %s", hipGetErrorString(e)); }
+            ctx->confirm_valid = false;
+        }
+        if (!ctx->confirm_valid || ctx->confirm_threshold != threshold || ctx->confirm_log2 != log2_buckets) {
+            ctx->confirm_valid = false;
+            const size_t words = ((size_t)1 << log2_buckets) * CONFIRM_BUCKET_WORDS;
+            DevBuf<uint32_t> counts;
+            MDBG_TRY(counts.alloc(ctx, (size_t)1 << log2_buckets));
+            MDBG_HIP_CHECK(ctx, hipMemsetAsync(ctx->confirm_table, 0, words * 4, ctx->stream));
+            MDBG_HIP_CHECK(ctx, hipMemsetAsync(ctx->confirm_table + TABLE_WORDS, 0, 16, ctx->stream));
+            MDBG_HIP_CHECK(ctx, hipMemsetAsync(counts.p, 0, ((size_t)1 << log2_buckets) * 4, ctx->stream));
+            {
+                LaunchTimer timer(ctx, "scan_confirm_table_build");
+                const dim3 grid((unsigned)ctx->n_cu * 16u), block(256);
+                hipLaunchKernelGGL(confirm_table_insert_kernel, grid, block, 0, ctx->stream, ctx->confirm_table, counts.p, threshold, log2_buckets);
+                hipLaunchKernelGGL(confirm_table_finish_kernel, dim3(grid_for((uint64_t)1 << log2_buckets, 256, (unsigned)ctx->n_cu * 16u)), block, 0, ctx->stream,
+                                   ctx->confirm_table, counts.p, log2_buckets, ctx->confirm_table + TABLE_WORDS);
+                if (confirm_table_needs_verify(log2_buckets))
+                    hipLaunchKernelGGL(confirm_table_verify_kernel, grid, block, 0, ctx->stream, ctx->confirm_table, threshold, log2_buckets, ctx->confirm_table + TABLE_WORDS);
+            }
+            MDBG_HIP_CHECK(ctx, hipGetLastError());
+            uint32_t n_over = 0;
+            hipError_t e = memcpy_sync(ctx, &n_over, ctx->confirm_table + TABLE_WORDS, 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "the scan's key table: %s", hipGetErrorString(e));
+            ctx->confirm_threshold = threshold; ctx->confirm_log2 = log2_buckets;
+            ctx->confirm_valid = true;
+            ctx->scan_confirm_info[0]++; ctx->scan_confirm_info[1] = 1ull << log2_buckets; ctx->scan_confirm_info[2] = n_over;
+        }
+    }
     return MDBG_OK;
 }
 
@@ -2061,6 +2166,7 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
         on = ctx->scan_stream;
     }
     if (fast) ctx->scan_info[6] = pf_kernel ? 1 : 0;
+    if (fast) ctx->scan_confirm_info[3] = 0;      // set below by a pre-filtered launch that takes the table
     {
         LaunchTimer timer(ctx, "scan", on);
         const uint8_t *const batch_skip = a.skip;
@@ -2115,6 +2221,10 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             // one workgroup of pf_waves waves per CU; it deals its chunk of reads out to its waves
             a.pf_bits = ctx->prefilter_bits;
             a.pf_shift = 32u - ctx->prefilter_log2;
+            const bool by_table = ctx->scan_confirm_table && ctx->confirm_valid && ctx->confirm_threshold == a.threshold;
+            a.pf_table = by_table ? reinterpret_cast<const uint4 *>(ctx->confirm_table) : nullptr;
+            a.pf_table_shift = by_table ? 32u - ctx->confirm_log2 : 0u;
+            ctx->scan_confirm_info[3] = by_table ? 1 : 0;
             const uint64_t chunk = std::min<uint64_t>((uint64_t)pf_waves * (ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : prefilter_reads_per_wave(ctx, n_items, pf_waves)), 1u << 24);
             a.pf_chunk = (uint32_t)chunk;
             const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, ((uint64_t)n_items + chunk - 1) / chunk), 0x7FFFFFFFull);
@@ -2684,6 +2794,12 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
     *out = m;
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
+
+extern "C" int mdbg_scan_confirm_info(const mdbg_ctx *ctx, uint64_t info[4]) {
+    if (!ctx || !info) return MDBG_EINVAL;
+    for (int i = 0; i < 4; i++) info[i] = ctx->scan_confirm_info[i];
+    return MDBG_OK;
+}
 
 extern "C" int mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]) {
     if (!ctx || !info) return MDBG_EINVAL;
