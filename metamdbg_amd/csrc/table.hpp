@@ -17,6 +17,7 @@ namespace mdbg {
 
 constexpr uint32_t TABLE_EXC_CAP = 64;
 constexpr uint32_t SLOT_NONE = 0xFFFFFFFFu;
+constexpr uint32_t TABLE_LOCK_SPINS = 1u << 20; // tries for the side list's lock before a lane gives up (the lock is held for microseconds)
 constexpr uint32_t TABLE_OCC_WAYS = 256;    // same-address atomics serialise at ~0.2 us each: spread the block sums
 
 // One slot = 32 bytes, half a 64-byte sector: key, value and representative arrive with ONE memory
@@ -58,11 +59,10 @@ __device__ __forceinline__ uint64_t table_home(uint64_t lo, uint64_t hi, uint64_
 }
 __device__ __forceinline__ uint64_t table_next(uint64_t s, uint64_t mask) { return s == mask ? 0 : s + 1; }
 
-// Side-list insert (serialised by a spin lock taken one lane at a time).  Returns the entry index.
+// Side-list insert (serialised by a spin lock; the lanes of a wave take it in turn).  Returns the entry index.
 __device__ inline uint32_t table_exc_upsert(const TableView &t, uint64_t lo, uint64_t hi, uint32_t add, uint32_t set_val,
                                             bool do_set, uint32_t rep, bool insert_if_absent) {
     uint32_t result = SLOT_NONE;
-    bool done = false;
     // a full list is final: look the key up without the lock (rows of zeros -- a transfer that did not arrive -- otherwise
     // queue millions of threads on one spin lock for minutes before the overflow is reported)
     if (__hip_atomic_load(t.exc_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= TABLE_EXC_CAP) {
@@ -79,38 +79,47 @@ __device__ inline uint32_t table_exc_upsert(const TableView &t, uint64_t lo, uin
         else if (add) atomicAdd(&t.exc_val[i], add);
         return 0x80000000u | i;
     }
-    while (!done) {
-        if (atomicCAS(t.exc_lock, 0u, 1u) == 0u) {
-            __threadfence();
-            uint32_t n = __hip_atomic_load(t.exc_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            uint32_t i = 0;
-            for (; i < n; i++)
-                if (__hip_atomic_load(&t.exc_lo[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == lo &&
-                    __hip_atomic_load(&t.exc_hi[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == hi) break;
-            if (i == n) {
-                if (!insert_if_absent) {
-                    i = SLOT_NONE;
-                } else if (n >= TABLE_EXC_CAP) {
-                    atomicExch(t.overflow, 1u);
-                    i = SLOT_NONE;
-                } else {
-                    __hip_atomic_store(&t.exc_lo[n], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&t.exc_hi[n], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&t.exc_val[n], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (t.exc_rep) __hip_atomic_store(&t.exc_rep[n], rep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __threadfence();
-                    __hip_atomic_store(t.exc_n, n + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+    // One lane of a wave at a time.  (Every lane spinning on the CAS, the winner doing its work inside the loop and leaving it, is
+    // compiled with the work moved BEHIND the loop: a lane that has the lock waits there, masked off, for the lanes of its own wave
+    // that spin for it -- two zero-word keys in one wave never returned.  Here the lane that spins has the wave to itself, and whoever
+    // holds the lock is a lane of another wave, on its way to release it.)  The spin is bounded all the same: a lock that does not
+    // come free in a million tries is reported like a full list.
+    const unsigned me = __lane_id();
+#pragma unroll 1
+    for (unsigned long long todo = __ballot(1); todo; todo &= todo - 1) {
+        if (me != (unsigned)(__ffsll(todo) - 1)) continue;
+        uint32_t spins = 0;
+#pragma unroll 1
+        while (atomicCAS(t.exc_lock, 0u, 1u) != 0u && ++spins < TABLE_LOCK_SPINS) {}
+        if (spins == TABLE_LOCK_SPINS) { atomicExch(t.overflow, 1u); continue; }
+        __threadfence();
+        uint32_t n = __hip_atomic_load(t.exc_n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t i = 0;
+        for (; i < n; i++)
+            if (__hip_atomic_load(&t.exc_lo[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == lo &&
+                __hip_atomic_load(&t.exc_hi[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == hi) break;
+        if (i == n) {
+            if (!insert_if_absent) {
+                i = SLOT_NONE;
+            } else if (n >= TABLE_EXC_CAP) {
+                atomicExch(t.overflow, 1u);
+                i = SLOT_NONE;
+            } else {
+                __hip_atomic_store(&t.exc_lo[n], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&t.exc_hi[n], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&t.exc_val[n], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t.exc_rep) __hip_atomic_store(&t.exc_rep[n], rep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __threadfence();
+                __hip_atomic_store(t.exc_n, n + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (i != SLOT_NONE) {
-                if (do_set) __hip_atomic_store(&t.exc_val[i], set_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else if (add) atomicAdd(&t.exc_val[i], add);
-            }
-            result = i;
-            __threadfence();
-            atomicExch(t.exc_lock, 0u);
-            done = true;
         }
+        if (i != SLOT_NONE) {
+            if (do_set) __hip_atomic_store(&t.exc_val[i], set_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (add) atomicAdd(&t.exc_val[i], add);
+        }
+        result = i;
+        __threadfence();
+        atomicExch(t.exc_lock, 0u);
     }
     return result == SLOT_NONE ? SLOT_NONE : (0x80000000u | result);
 }
