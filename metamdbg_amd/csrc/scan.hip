@@ -29,6 +29,7 @@
 #include "murmur.hpp"
 #include "objects.hpp"
 #include "prefilter.hpp"
+#include "scan_plan.hpp"
 #include "segments_dev.hpp"
 
 #include <fcntl.h>
@@ -40,6 +41,7 @@
 #include <cerrno>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
     const uint32_t kbits = (1u << K) - 1u;
     const uint32_t comp_mask = 0xAAAAAAAAu & kmask;
 
-    // a wave takes a few reads and retires (launch_variant sizes the grid); written as a grid-stride loop
+    // a wave takes a few reads and retires (scan_blocks sizes the grid); written as a grid-stride loop
     const uint32_t wave_global = blockIdx.x * (SCAN_BLOCK / 64) + wv;
     const uint32_t n_waves = (gridDim.x * SCAN_BLOCK) >> 6;
     for (uint32_t slot = wave_global; slot < a.n_reads; slot += n_waves) {
@@ -2056,47 +2058,107 @@ static int prefilter_ensure(mdbg_ctx *ctx, uint64_t threshold, unsigned log2_bit
     return MDBG_OK;
 }
 
-// "scan_reads_per_wave" left at 0: what a wave takes before its workgroup retires.  The four-wave and the general kernels keep 2 (see
-// launch_variant).  A workgroup of the pre-filtered variant copies the 64 KB bitmap, clears its rings and passes two barriers before its
-// first read, with nothing else of the scan on its CU meanwhile: at 2 reads a wave that is paid 312 500 times for 10 M reads.  Measured
-// (profiles/split_residency_reads_per_wave.txt), 10 M x 10 kb alone: 71.1 / 67.7 / 65.3 / 64.6 / 63.7 / 64.0 / 65.4 ms at 2 / 4 / 8 / 16 /
-// 32 / 64 / 128; 500 000 reads of 1 .. 25 kb: 3.94 / 3.27 / 3.00 / 2.85 / 2.79 / 2.74 / 2.71 ms.  With two batches in flight the step
-// gains more than the scan alone and keeps gaining up to 128 -- but from 64 on because the other batch's first pass is held back (its
-// kernels' time follows the life of a scan workgroup, DESIGN.md 4.4: 27 / 41 / 57 / 66 ms of first pass a step at 16 / 32 / 64 / 128 under a
-// scan launch of 82 / 80 / 78 / 77 ms), and a first pass as long as a scan launch is what the pipeline would wait for next.  32 is the
-// largest value at which it stays at half a launch.  The batch must also leave every CU PREFILTER_MIN_GROUPS_PER_CU workgroups (the 500 000
-// reads above are 1.9 a CU at 64): a small batch would otherwise leave CUs idle for the length of a workgroup.
-constexpr unsigned SCAN_READS_PER_WAVE = 2, PREFILTER_READS_PER_WAVE = 32, PREFILTER_MIN_GROUPS_PER_CU = 2;
-
-static unsigned prefilter_reads_per_wave(const mdbg_ctx *ctx, uint32_t n_items, unsigned waves) {
-    unsigned per_wave = PREFILTER_READS_PER_WAVE;
-    const uint64_t want = (uint64_t)PREFILTER_MIN_GROUPS_PER_CU * (uint64_t)std::max(ctx->n_cu, 1);
-    while (per_wave > SCAN_READS_PER_WAVE && (uint64_t)n_items / ((uint64_t)waves * per_wave) < want) per_wave /= 2;
-    return per_wave;
+// The scan's A/B switches, each read here and nowhere else: MDBG_SCAN_NO_FAST (the general kernel for everything; includes the other two),
+// MDBG_SCAN_NO_APPROX (the full 64-bit verdict at every position), MDBG_SCAN_NO_BUMP (mdbg_scan leaves its block path alone)
+struct ScanSwitches { bool no_fast, approx_allowed, bump_allowed; };
+static const ScanSwitches &scan_switches() {
+    static const bool no_fast = getenv("MDBG_SCAN_NO_FAST") != nullptr;
+    static const ScanSwitches s{no_fast, !no_fast && !getenv("MDBG_SCAN_NO_APPROX"), !no_fast && !getenv("MDBG_SCAN_NO_BUMP")};
+    return s;
 }
 
-template <bool HPC, bool Q, bool N>
-static void launch_variant(mdbg_ctx *ctx, const ScanArgs &a, unsigned max_blocks, uint32_t n_items) {
-    // A few reads per wave, then the wave retires.  One resident generation of persistent waves (the first design)
-    // took 17.9 ms for 1 M x 10 kb reads although every wave had the same work: CUs do not all run at the same
-    // speed, and the kernel ended with the slowest.  Dealt out by the dispatcher as slots free up, the same reads take
-    // 15.4 ms; short-lived workgroups also let the kernels of another stream (a second batch in flight, RCCL) in
-    // instead of queueing them behind the resident generation.  The per-block set-up (1024-entry LUT) is noise next
-    // to a 10 kb read.  2 reads per wave measured best with two batches in flight: a waiting kernel of the other batch gets
-    // a slot within ~0.2 ms (MDBG_SCAN_READS_PER_WAVE to tune).
-    (void)max_blocks;
-    const uint64_t per_wave = ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : SCAN_READS_PER_WAVE;
-    uint64_t blocks = ((uint64_t)n_items + SCAN_WAVES * per_wave - 1) / (SCAN_WAVES * per_wave);
-    if (blocks < 1) blocks = 1;
-    if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;
-    hipLaunchKernelGGL((scan_kernel<HPC, Q, N>), dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, ctx->stream, a);
+using ScanKernel = void (*)(ScanArgs);
+
+static ScanKernel select_general_kernel(bool hpc, bool has_q, bool has_n) {
+    static const ScanKernel k[8] = {scan_kernel<false, false, false>, scan_kernel<false, false, true>, scan_kernel<false, true, false>, scan_kernel<false, true, true>,
+                                    scan_kernel<true, false, false>,  scan_kernel<true, false, true>,  scan_kernel<true, true, false>,  scan_kernel<true, true, true>};
+    return k[(hpc ? 4 : 0) + (has_q ? 2 : 0) + (has_n ? 1 : 0)];
 }
 
-// static LDS of a kernel, asked once (0: the query failed)
+// pf_waves 16 or 8: the pre-filtered variant (compressed reads without qualities, candidate test); 0: a four-wave kernel -- bump mode:
+// candidates by the upper half of the hash (span_step<APPROX>); the host's re-run of a read covers a false one.  seg: views (approx only)
+static ScanKernel select_fast_kernel(bool hpc, bool has_q, bool approx, unsigned pf_waves, bool seg) {
+    if (pf_waves == 16) return seg ? scan_fast_kernel<true, false, true, 16, true> : scan_fast_kernel<true, false, true, 16>;
+    if (pf_waves == 8) return seg ? scan_fast_kernel<true, false, true, 8, true> : scan_fast_kernel<true, false, true, 8>;
+    static const ScanKernel four_wave[3][4] = {      // [exact, approx, views][hpc, qualities]
+        {scan_fast_kernel<false, false, false>, scan_fast_kernel<false, true, false>, scan_fast_kernel<true, false, false>, scan_fast_kernel<true, true, false>},
+        {scan_fast_kernel<false, false, true>, scan_fast_kernel<false, true, true>, scan_fast_kernel<true, false, true>, scan_fast_kernel<true, true, true>},
+        {scan_fast_kernel<false, false, true, 0, true>, scan_fast_kernel<false, true, true, 0, true>, scan_fast_kernel<true, false, true, 0, true>,
+         scan_fast_kernel<true, true, true, 0, true>}};
+    return four_wave[seg ? 2 : (approx ? 1 : 0)][(hpc ? 2 : 0) + (has_q ? 1 : 0)];
+}
+
+// static LDS of a kernel (0: the query failed)
 static size_t kernel_static_lds(const void *kernel) {
     hipFuncAttributes at;
     if (hipFuncGetAttributes(&at, kernel) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return at.sharedSizeBytes;
+}
+
+// The pre-filtered variant ("scan_prefilter", MDBG_SCAN_PREFILTER): compressed reads at l = 15 without qualities, the candidate
+// test as it is by default, a batch most of whose reads fit its smaller stage (mdbg_scan), a bitmap sparse enough (prefilter_ensure) -- and as many
+// waves a workgroup as leave "scan_lds_reserve" free: 16, else 8, else the four-wave kernels with their padding.  Decided, and
+// the bitmap queued on the context's stream, before the "scan" timer and the hand-over to the scan's stream.  *pf_waves: 0 when not taken.
+static int choose_prefilter(mdbg_ctx *ctx, const ScanArgs &a, bool approx, bool hpc, bool has_q, uint32_t pf_len_limit, unsigned *pf_waves) {
+    *pf_waves = 0;
+    if (!(approx && hpc && !has_q && a.K == PREFILTER_L && a.cand_slack == 0u && a.guard_slack == 0u && pf_len_limit && ctx->scan_prefilter && !ctx->scan_lds_pad))
+        return MDBG_OK;
+    static const size_t lds16 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 16>)),       // asked once
+                        lds8 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 8>));      // (the same with SEG)
+    if (!lds16 || !lds8) return set_error(ctx, MDBG_EHIP, "hipFuncGetAttributes of the pre-filtered scan kernels failed");
+    const unsigned waves = prefilter_wave_count(ctx->lds_per_cu, ctx->scan_lds_reserve, lds16, lds8);
+    if (!waves) return MDBG_OK;
+    const bool forced = ctx->scan_prefilter_log2_bits != 0u;
+    bool fill_ok = false;
+    MDBG_TRY(prefilter_ensure(ctx, a.threshold, forced ? ctx->scan_prefilter_log2_bits : PREFILTER_LOG2_BITS, forced, &fill_ok));
+    if (fill_ok) *pf_waves = waves;
+    return MDBG_OK;
+}
+
+// pf_split: flags in d_split what the four-wave launch in front of the variant skips -- every read but the long ones -- and counts
+// the long reads' bases: *split false when they outweigh the split (long_reads_outweigh_split; the batch then keeps the four-wave kernel)
+static int split_long_reads(mdbg_ctx *ctx, const ScanArgs &a, uint32_t n_items, uint32_t pf_len_limit, uint64_t batch_bases, DevBuf<uint8_t> &d_split, bool *split) {
+    DevBuf<unsigned long long> d_long;
+    MDBG_TRY(d_split.alloc(ctx, n_items));
+    MDBG_TRY(d_long.alloc(ctx, 1));
+    MDBG_HIP_CHECK(ctx, hipMemsetAsync(d_long.p, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(split_skip_kernel, dim3(grid_for(n_items, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0, ctx->stream, a.len, a.skip, n_items, pf_len_limit,
+                       d_split.p, d_long.p);
+    unsigned long long long_bases = 0;
+    if (memcpy_sync(ctx, &long_bases, d_long.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan: the long reads' bases could not be counted");
+    *split = !long_reads_outweigh_split(long_bases, batch_bases);
+    return MDBG_OK;
+}
+
+// "table_cu_count": the context's own stream is confined to a few CUs; the block-structured kernel goes to a stream over all of
+// them, ordered after what the context has queued so far (take) and before what it queues next (give_back)
+struct ScanStreamLoan {
+    hipStream_t on = nullptr;
+    hipEvent_t ordered = nullptr;
+    int take(mdbg_ctx *ctx, bool fast) {
+        on = ctx->stream;
+        if (!(fast && ctx->scan_stream)) return MDBG_OK;
+        MDBG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ordered, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ordered, ctx->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->scan_stream, ordered, 0);
+        if (e != hipSuccess) { (void)hipEventDestroy(ordered); return set_error(ctx, MDBG_EHIP, "scan stream hand-over: %s", hipGetErrorString(e)); }
+        on = ctx->scan_stream;
+        return MDBG_OK;
+    }
+    int give_back(mdbg_ctx *ctx) {
+        if (!ordered) return MDBG_OK;
+        hipError_t e = hipEventRecord(ordered, on);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ordered, 0);
+        (void)hipEventDestroy(ordered);         // released by the runtime once the recorded work is done
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan stream hand-back: %s", hipGetErrorString(e));
+        return MDBG_OK;
+    }
+};
+
+// "scan_lds_pad" / "scan_lds_reserve" (scan_lds_padding): the kernel's static LDS is asked only where the reserve decides
+static unsigned four_wave_lds_pad(const mdbg_ctx *ctx, ScanKernel fk) {
+    const bool by_reserve = !ctx->scan_lds_pad && ctx->scan_lds_reserve;
+    return scan_lds_padding(ctx->scan_lds_pad, ctx->scan_lds_reserve, ctx->lds_per_cu, by_reserve ? kernel_static_lds(reinterpret_cast<const void *>(fk)) : 0);
 }
 
 // pf_len_limit > 0: the batch may take the pre-filtered variant, whose stage a read shorter than that is expected to fit; pf_split:
@@ -2105,119 +2167,36 @@ static size_t kernel_static_lds(const void *kernel) {
 static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool has_n, uint32_t n_items, uint32_t pf_len_limit = 0, bool pf_split = false,
                        uint64_t batch_bases = 0, bool seg = false) {
     a.n_reads = n_items;
-    const unsigned max_blocks = (unsigned)ctx->n_cu * 8u;
-    static const bool no_fast = getenv("MDBG_SCAN_NO_FAST") != nullptr;      // A/B: the general kernel for everything
-    static const bool no_approx = getenv("MDBG_SCAN_NO_APPROX") != nullptr;  // A/B: full 64-bit verdict at every position
-    const bool fast = (!has_q || a.cursor) && !has_n && !a.subset && !no_fast;
-    using FastKernel = void (*)(ScanArgs);
-    // (not when the candidate limit would saturate -- a threshold within a few 2^32 of 2^64, density 1.0f: the full verdict then)
-    const bool approx = fast && a.cursor && !no_approx && (a.threshold >> 32) + 3ull + (uint64_t)a.cand_slack < 0xFFFFFFFFull;
+    const ScanSwitches &sw = scan_switches();
+    const bool fast = (!has_q || a.cursor) && !has_n && !a.subset && !sw.no_fast;
+    const bool approx = fast && a.cursor && sw.approx_allowed && candidate_test_usable(a.threshold, a.cand_slack);
     if (seg && !approx) return set_error(ctx, MDBG_EINVAL, "scan: views are scanned by the candidate-hash kernels only");
-    // The pre-filtered variant ("scan_prefilter", MDBG_SCAN_PREFILTER): compressed reads at l = 15 without qualities, the candidate
-    // test as it is by default, a batch most of whose reads fit its smaller stage (mdbg_scan), a bitmap sparse enough (prefilter_ensure) -- and as many
-    // waves a workgroup as leave "scan_lds_reserve" free: 16, else 8, else the four-wave kernels with their padding.  Decided, and
-    // the bitmap queued on the context's stream, before the "scan" timer and the hand-over to the scan's stream.
-    FastKernel pf_kernel = nullptr;
     unsigned pf_waves = 0;
-    if (approx && hpc && !has_q && a.K == PREFILTER_L && a.cand_slack == 0u && a.guard_slack == 0u && pf_len_limit &&
-        ctx->scan_prefilter && !ctx->scan_lds_pad) {
-        const size_t total = ctx->lds_per_cu ? ctx->lds_per_cu : 163840u;
-        const size_t room = total > ctx->scan_lds_reserve ? total - ctx->scan_lds_reserve : 0;
-        const FastKernel pf16 = seg ? scan_fast_kernel<true, false, true, 16, true> : scan_fast_kernel<true, false, true, 16>;
-        const FastKernel pf8 = seg ? scan_fast_kernel<true, false, true, 8, true> : scan_fast_kernel<true, false, true, 8>;
-        static const size_t lds16 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 16>)),
-                            lds8 = kernel_static_lds(reinterpret_cast<const void *>(scan_fast_kernel<true, false, true, 8>));      // (the same with SEG)
-        if (!lds16 || !lds8) return set_error(ctx, MDBG_EHIP, "hipFuncGetAttributes of the pre-filtered scan kernels failed");
-        if (lds16 <= room) { pf_kernel = pf16; pf_waves = 16; }
-        else if (lds8 <= room) { pf_kernel = pf8; pf_waves = 8; }
-        if (pf_kernel) {
-            const bool forced = ctx->scan_prefilter_log2_bits != 0u;
-            bool fill_ok = false;
-            MDBG_TRY(prefilter_ensure(ctx, a.threshold, forced ? ctx->scan_prefilter_log2_bits : PREFILTER_LOG2_BITS, forced, &fill_ok));
-            if (!fill_ok) pf_kernel = nullptr;
-        }
-    }
-    // Reads too long for the variant's stage: when they hold at most 1/32 of the batch's bases the four-wave kernel scans them in a launch
-    // of its own (every other read flagged in its `skip`), the variant the rest.  That launch is sparse -- most waves of a block idle -- so
-    // a batch with many long reads loses more there than the variant gains (measured: profiles/prefilter_varied_lengths.txt) and keeps
-    // the four-wave kernel for all its reads.
-    pf_split = pf_split && pf_kernel;
+    MDBG_TRY(choose_prefilter(ctx, a, approx, hpc, has_q, pf_len_limit, &pf_waves));
+    pf_split = pf_split && pf_waves;
     DevBuf<uint8_t> d_split;        // pf_split: what the four-wave launch skips (back to the pool on return: reuse is ordered on the context's stream)
     if (pf_split) {
-        DevBuf<unsigned long long> d_long;
-        MDBG_TRY(d_split.alloc(ctx, n_items));
-        MDBG_TRY(d_long.alloc(ctx, 1));
-        MDBG_HIP_CHECK(ctx, hipMemsetAsync(d_long.p, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(split_skip_kernel, dim3(grid_for(n_items, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0, ctx->stream, a.len, a.skip, n_items, pf_len_limit,
-                           d_split.p, d_long.p);
-        unsigned long long long_bases = 0;
-        if (memcpy_sync(ctx, &long_bases, d_long.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan: the long reads' bases could not be counted");
-        if (long_bases * 32ull > batch_bases) { pf_split = false; pf_kernel = nullptr; }
+        MDBG_TRY(split_long_reads(ctx, a, n_items, pf_len_limit, batch_bases, d_split, &pf_split));
+        if (!pf_split) pf_waves = 0;
     }
-    // "table_cu_count": the context's own stream is confined to a few CUs; the block-structured kernel goes to a stream over all of
-    // them, ordered after what the context has queued so far and before what it queues next
-    hipStream_t on = ctx->stream;
-    hipEvent_t ordered = nullptr;
-    if (fast && ctx->scan_stream) {
-        MDBG_HIP_CHECK(ctx, hipEventCreateWithFlags(&ordered, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ordered, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->scan_stream, ordered, 0);
-        if (e != hipSuccess) { (void)hipEventDestroy(ordered); return set_error(ctx, MDBG_EHIP, "scan stream hand-over: %s", hipGetErrorString(e)); }
-        on = ctx->scan_stream;
-    }
-    if (fast) ctx->scan_info[6] = pf_kernel ? 1 : 0;
+    ScanStreamLoan loan;
+    MDBG_TRY(loan.take(ctx, fast));
+    if (fast) ctx->scan_info[6] = pf_waves ? 1 : 0;
     if (fast) ctx->scan_confirm_info[3] = 0;      // set below by a pre-filtered launch that takes the table
     {
-        LaunchTimer timer(ctx, "scan", on);
+        LaunchTimer timer(ctx, "scan", loan.on);
         const uint8_t *const batch_skip = a.skip;
         if (pf_split) a.skip = d_split.p;           // first the long reads, by the four-wave kernel below
-        if (fast && (!pf_kernel || pf_split)) {
+        if (fast && (!pf_waves || pf_split)) {
             // plain ACGT without qualities: the block-structured kernel; a few reads per wave, then the wave retires
-            const uint64_t per_wave = ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : SCAN_READS_PER_WAVE;
-            uint64_t blocks = ((uint64_t)n_items + FAST_WAVES * per_wave - 1) / (FAST_WAVES * per_wave);
-            if (blocks < 1) blocks = 1;
-            if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;
-            // bump mode: candidates by the upper half of the hash (span_step<APPROX>); the host's re-run of a read covers a false one
-            const dim3 g((unsigned)blocks), b(FAST_BLOCK);
             ctx->scan_info[1]++;
-            const FastKernel fk = seg ? (hpc ? (has_q ? scan_fast_kernel<true, true, true, 0, true> : scan_fast_kernel<true, false, true, 0, true>)
-                                             : (has_q ? scan_fast_kernel<false, true, true, 0, true> : scan_fast_kernel<false, false, true, 0, true>))
-                                : approx ? (hpc ? (has_q ? scan_fast_kernel<true, true, true> : scan_fast_kernel<true, false, true>)
-                                                : (has_q ? scan_fast_kernel<false, true, true> : scan_fast_kernel<false, false, true>))
-                                         : (hpc ? (has_q ? scan_fast_kernel<true, true, false> : scan_fast_kernel<true, false, false>)
-                                                : (has_q ? scan_fast_kernel<false, true, false> : scan_fast_kernel<false, false, false>));
-            // Unused dynamic LDS caps this kernel's blocks per CU (mdbg_set_option): "scan_lds_pad" gives the bytes as they are;
-            // "scan_lds_reserve" says how much of a CU's LDS the kernel is to LEAVE to other contexts' kernels, whatever the variant
-            // (30 KB a block for FASTA with homopolymer compression, 36.5 KB for FASTQ): as many blocks as fit beside the reserve, and
-            // enough padding that one more does not.
-            unsigned lds_pad = ctx->scan_lds_pad;
-            if (!lds_pad && ctx->scan_lds_reserve) {
-                hipFuncAttributes at;
-                if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(fk)) == hipSuccess && at.sharedSizeBytes > 0) {
-                    const size_t total = ctx->lds_per_cu ? ctx->lds_per_cu : 163840u, lds = at.sharedSizeBytes;
-                    size_t fit = total > ctx->scan_lds_reserve ? (total - ctx->scan_lds_reserve) / lds : 1;
-                    // never fewer than two blocks per CU: one block would have to be padded to more than half a CU's LDS -- beyond the 64 KB
-                    // a block may ask for, the launch would fail with hipErrorInvalidValue instead of capping anything (round-4 ADVICE);
-                    // a reserve that large is answered with the two-block form (and whatever LDS that leaves)
-                    if (fit < 2) fit = 2;
-                    const size_t need = total / (fit + 1) + 1;          // a block of this size: fit + 1 of them are more than a CU has
-                    if (need > lds) lds_pad = (unsigned)(((need - lds) + 255u) / 256u * 256u);
-                    const size_t most = (size_t)65536 > lds ? (size_t)65536 - lds : 0;        // static + dynamic LDS of a block stay within 64 KB
-                    if (lds_pad > most) lds_pad = (unsigned)(most / 256u * 256u);
-                } else (void)hipGetLastError();
-            }
-            hipLaunchKernelGGL(fk, g, b, lds_pad, on, a);
-        } else if (fast) {
-            // (the pre-filtered variant below takes every read)
-        } else if (hpc) {
-            if (has_n) { if (has_q) launch_variant<true, true, true>(ctx, a, max_blocks, n_items); else launch_variant<true, false, true>(ctx, a, max_blocks, n_items); }
-            else { if (has_q) launch_variant<true, true, false>(ctx, a, max_blocks, n_items); else launch_variant<true, false, false>(ctx, a, max_blocks, n_items); }
-        } else {
-            if (has_n) { if (has_q) launch_variant<false, true, true>(ctx, a, max_blocks, n_items); else launch_variant<false, false, true>(ctx, a, max_blocks, n_items); }
-            else { if (has_q) launch_variant<false, true, false>(ctx, a, max_blocks, n_items); else launch_variant<false, false, false>(ctx, a, max_blocks, n_items); }
+            const ScanKernel fk = select_fast_kernel(hpc, has_q, approx, 0, seg);
+            hipLaunchKernelGGL(fk, dim3(scan_blocks(n_items, FAST_WAVES, ctx->scan_reads_per_wave)), dim3(FAST_BLOCK), four_wave_lds_pad(ctx, fk), loan.on, a);
+        } else if (!fast) {       // (else the pre-filtered variant below takes every read)
+            hipLaunchKernelGGL(select_general_kernel(hpc, has_q, has_n), dim3(scan_blocks(n_items, SCAN_WAVES, ctx->scan_reads_per_wave)), dim3(SCAN_BLOCK), 0, ctx->stream, a);
         }
         a.skip = batch_skip;
-        if (pf_kernel) {
+        if (pf_waves) {
             // one workgroup of pf_waves waves per CU; it deals its chunk of reads out to its waves
             a.pf_bits = ctx->prefilter_bits;
             a.pf_shift = 32u - ctx->prefilter_log2;
@@ -2225,33 +2204,26 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             a.pf_table = by_table ? reinterpret_cast<const uint4 *>(ctx->confirm_table) : nullptr;
             a.pf_table_shift = by_table ? 32u - ctx->confirm_log2 : 0u;
             ctx->scan_confirm_info[3] = by_table ? 1 : 0;
-            const uint64_t chunk = std::min<uint64_t>((uint64_t)pf_waves * (ctx->scan_reads_per_wave ? ctx->scan_reads_per_wave : prefilter_reads_per_wave(ctx, n_items, pf_waves)), 1u << 24);
-            a.pf_chunk = (uint32_t)chunk;
-            const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, ((uint64_t)n_items + chunk - 1) / chunk), 0x7FFFFFFFull);
+            const PrefilterGrid grid = prefilter_grid(n_items, pf_waves, ctx->scan_reads_per_wave, ctx->n_cu);
+            a.pf_chunk = grid.chunk;
             a.pf_len_split = pf_split ? pf_len_limit : 0u;
-            hipLaunchKernelGGL(pf_kernel, dim3((unsigned)blocks), dim3(64u * pf_waves), 0, on, a);
+            hipLaunchKernelGGL(select_fast_kernel(true, false, true, pf_waves, seg), dim3(grid.blocks), dim3(64u * pf_waves), 0, loan.on, a);
             ctx->scan_info[0]++; ctx->scan_info[5] = pf_waves;
         }
     }
-    if (ordered) {
-        hipError_t e = hipEventRecord(ordered, on);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ordered, 0);
-        (void)hipEventDestroy(ordered);         // released by the runtime once the recorded work is done
-        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan stream hand-back: %s", hipGetErrorString(e));
-    }
+    MDBG_TRY(loan.give_back(ctx));
     MDBG_HIP_CHECK(ctx, hipGetLastError());
     return MDBG_OK;
 }
 
 // The plan of a batch whose long reads are cut into views (segments_dev.hpp): built on the device by the pre-pass, of which the host
 // learns the totals only
-struct SegPlan {
+struct SegPlan : SegTotals {
     DevBuf<uint32_t> tiles_per_read, views_per_read, tile_runs, tile_excl;
     DevBuf<uint64_t> tile_off, view_off;
     DevBuf<SegView> views;
     DevBuf<uint8_t> skip, read_cut;      // per read: left out of the batch's own launch (masked or cut); 1 = cut, 2 = cut but fallen back
     DevBuf<unsigned long long> totals;   // [0] reads cut, [1] their views, [2] rows joined, [3] reads joined, [4] the joined rows did not fit
-    uint64_t n_cut = 0, n_views = 0, n_tiles = 0;       // reads cut; views and tiles of the reads long enough to be (those of unsegmentable reads are dead)
 };
 
 static int seg_prepass(mdbg_ctx *ctx, const mdbg_reads *reads, const uint8_t *masked, uint32_t G, uint32_t K, bool hpc, SegPlan &sp) {
@@ -2287,51 +2259,82 @@ static int seg_prepass(mdbg_ctx *ctx, const mdbg_reads *reads, const uint8_t *ma
     return MDBG_OK;
 }
 
-extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan_params *p, mdbg_minimizers **out) try {
-    if (!ctx || !reads || !p || !out) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: null argument");
-    if (p->quality_window != 0 && p->quality_window != 1) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: quality_window must be 0 or 1");
-    if (p->minimizer_size < 2 || p->minimizer_size > 16)
-        return set_error(ctx, MDBG_EINVAL, "mdbg_scan: minimizer_size %u outside [2,16]", p->minimizer_size);
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    MDBG_HIP_CHECK(ctx, reads_ready_on(ctx, reads));        // an upload still in flight (mdbg_reads_from_packed_async): ordered on the device
-    const uint32_t n = reads->n_reads;
-    const bool hpc = p->hpc != 0, has_q = reads->has_qual && !p->ignore_qualities, has_n = reads->has_invalid;
-    ctx->scan_info[7] = 0;
-    mdbg_minimizers *m = new mdbg_minimizers();
-    m->n_reads = n;
-    m->from_scan = true;
-    auto fail = [&](int rc) { delete m; return rc; };
-    hipError_t e;
-
-    DevBuf<uint32_t> d_cap, d_count, d_rep;
-    DevBuf<uint64_t> d_cap_off;
-    int rc;
-    if ((rc = d_cap.alloc(ctx, n)) || (rc = d_count.alloc(ctx, n)) || (rc = d_cap_off.alloc(ctx, (size_t)n + 1)) ||
-        (rc = m->d_flags.alloc(ctx, n)) || (rc = m->d_len.alloc(ctx, n)) || (rc = m->d_off.alloc(ctx, (size_t)n + 1)))
-        return fail(rc);
-    if (p->n_repetitive) {
-        std::vector<uint32_t> rep(p->repetitive, p->repetitive + p->n_repetitive);
-        std::sort(rep.begin(), rep.end());
-        if ((rc = d_rep.alloc(ctx, rep.size()))) return fail(rc);
-        e = memcpy_sync(ctx, d_rep.p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "copy of repetitive set failed"));
-    }
-    e = hipMemcpyAsync(m->d_len.p, reads->d_len.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "len copy failed: %s", hipGetErrorString(e)));
-
-    // ---- mean read quality (exact 128-bit sums on the device, long double finish on the host) ----
+// ---- mean read quality (exact 128-bit sums on the device, long double finish on the host) ----
+struct QualitySums {
     std::vector<uint8_t> low_quality;
     bool any_low_quality = false;
     DevBuf<uint64_t> d_qtab, d_slo, d_shi;
     struct SideGuard { hipStream_t s = nullptr; ~SideGuard() { if (s) (void)hipStreamSynchronize(s); } } side_guard;   // before the buffers go
-    bool quality_pending = false;
-    // the host's share of the mean qualities: the reference's long double division and log10 per read, on a few host threads
-    auto quality_finish = [&]() -> int {
-        if (!quality_pending) return MDBG_OK;
-        quality_pending = false;
+    bool pending = false;
+
+    // the table, the sums beside (or in front of) the scan, their downloads queued behind them
+    int start(mdbg_ctx *ctx, const mdbg_reads *reads, mdbg_minimizers *m, bool has_q) {
+        const uint32_t n = reads->n_reads;
+        hipError_t e;
+        if (!(has_q && n)) {
+            // no qualities: every read's mean quality is the NaN the reference writes; kept as one value, not n of them (a 40 MB
+            // host fill per 10 M reads sat on the critical path in front of the kernel launch)
+            m->h_mean_quality.clear();
+            m->mean_quality_all = mean_quality_from_sum(0, 0);
+            return MDBG_OK;
+        }
+        // table exactly as the reference builds it (ReadSelection.hpp:101-104, Commons.hpp:2338-2341)
+        std::vector<uint64_t> tsh(QBINS, 0);
+        for (int q = 33; q <= 127; q++) {
+            float qq = (float)(uint8_t)(q - 33);
+            float t = powf(10.0f, -qq / 10.0f);
+            long double scaled = (long double)t * 18446744073709551616.0L;   // * 2^64, exact (24-bit mantissa)
+            unsigned __int128 v = (unsigned __int128)scaled;
+            if ((uint64_t)v & ((1ull << QSHIFT) - 1ull)) return set_error(ctx, MDBG_EINVAL, "quality table entry %d is not a multiple of 2^%d", q, QSHIFT);
+            tsh[q - 33] = (uint64_t)(v >> QSHIFT);
+        }
+        MDBG_TRY(d_qtab.alloc(ctx, QBINS)); MDBG_TRY(d_slo.alloc(ctx, n)); MDBG_TRY(d_shi.alloc(ctx, n));
+        if ((e = memcpy_sync(ctx, d_qtab.p, tsh.data(), QBINS * 8, hipMemcpyHostToDevice)) != hipSuccess)
+            return set_error(ctx, MDBG_EHIP, "quality table upload failed: %s", hipGetErrorString(e));
+        // The sums run BESIDE the scan, on the side stream (round 5; until then in front of it, on the context's stream: 61 ms of a 0.52 s
+        // pass over 200 Gbp of ONT reads): they are a second pass over the quality bytes at 3 TB/s -- memory traffic the VALU-bound scan
+        // leaves idle -- in blocks of 768 bytes of LDS that fit beside the scan's.  Their way to the host (pinned memory) and the host's share
+        // (finish) follow on the same stream: nothing of the mean quality is needed before the rows are counted.
+        // ("scan_quality_stream" 0: in front of the scan as before, A/B.)
+        MDBG_TRY(pinned_reserve(ctx, (size_t)n * 20));
+        const bool beside = ctx->scan_quality_beside != 0;
+        hipStream_t qs = beside ? ctx->side_stream : ctx->stream;
+        hipEvent_t ev;
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return set_error(ctx, MDBG_EHIP, "hipEventCreate: %s", hipGetErrorString(e));
+        if (beside) {                                   // behind whatever the context's stream has queued so far (the reads, the table upload)
+            (void)hipEventRecord(ev, ctx->stream);
+            (void)hipStreamWaitEvent(ctx->side_stream, ev, 0);
+        }
+        side_guard.s = ctx->side_stream;     // from here on every way out waits for the side stream before d_slo / d_shi / d_qtab go back to the pool (round-5 ADVICE)
+        {
+            LaunchTimer timer(ctx, "quality_sum", qs);
+            unsigned blocks = grid_for((uint64_t)n * 64, 256, (unsigned)ctx->n_cu * 8u);
+            hipLaunchKernelGGL(quality_sum_kernel, dim3(blocks), dim3(256), 0, qs, reads->d_qual.p, reads->d_qual_off.p,
+                               reads->d_len.p, n, d_qtab.p, d_slo.p, d_shi.p);
+        }
+        if (!beside) {
+            (void)hipEventRecord(ev, ctx->stream);
+            (void)hipStreamWaitEvent(ctx->side_stream, ev, 0);
+        }
+        (void)hipEventDestroy(ev);
+        uint8_t *h = (uint8_t *)ctx->pinned;
+        if ((e = hipMemcpyAsync(h, d_slo.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(h + (size_t)n * 8, d_shi.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(h + (size_t)n * 16, reads->d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess)
+            return set_error(ctx, MDBG_EHIP, "quality sums download failed: %s", hipGetErrorString(e));
+        pending = true;
+        return MDBG_OK;
+    }
+
+    // the host's share of the mean qualities: the reference's long double division and log10 per read, on a few host threads.  Called
+    // once the scan kernel is queued and before the first blocking download -- host work while the kernel runs; a second call does nothing
+    int finish(mdbg_ctx *ctx, const mdbg_scan_params *p, mdbg_minimizers *m) {
+        if (!pending) return MDBG_OK;
+        pending = false;
         hipError_t qe;
         if ((qe = hipStreamSynchronize(ctx->side_stream)) != hipSuccess)
             return set_error(ctx, MDBG_EHIP, "quality sums download failed: %s", hipGetErrorString(qe));
+        const uint32_t n = m->n_reads;
         const uint64_t *slo = (const uint64_t *)ctx->pinned, *shi = slo + n;
         const uint32_t *lens = (const uint32_t *)(shi + n);
         m->h_mean_quality.resize(n);
@@ -2357,441 +2360,391 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
         }
         for (char c : any) any_low_quality |= c != 0;
         return MDBG_OK;
-    };
-    if (has_q && n) {
-        // table exactly as the reference builds it (ReadSelection.hpp:101-104, Commons.hpp:2338-2341)
-        std::vector<uint64_t> tsh(QBINS, 0);
-        for (int q = 33; q <= 127; q++) {
-            float qq = (float)(uint8_t)(q - 33);
-            float t = powf(10.0f, -qq / 10.0f);
-            long double scaled = (long double)t * 18446744073709551616.0L;   // * 2^64, exact (24-bit mantissa)
-            unsigned __int128 v = (unsigned __int128)scaled;
-            if ((uint64_t)v & ((1ull << QSHIFT) - 1ull)) return fail(set_error(ctx, MDBG_EINVAL, "quality table entry %d is not a multiple of 2^%d", q, QSHIFT));
-            tsh[q - 33] = (uint64_t)(v >> QSHIFT);
+    }
+};
+
+constexpr uint32_t CTL_OVER = 64, CTL_DROPPED = 65, CTL_WORDS = 66;     // the block path's u64 words: cursors, {n_over, n_suspect}, rows dropped
+constexpr uint32_t SCTL_WORDS = 66;                                     // the views' cursors and [64] = {views listed, -}
+
+// the block path's buffers that are not the batch's output
+struct BlockBufs {
+    DevBuf<uint32_t> d_over, d_susp;
+    DevBuf<unsigned long long> d_ctl;
+    DevBuf<uint32_t> sv_min, sv_pos, sv_cnt, sv_over;       // the views' own rows, counts and counters
+    DevBuf<uint8_t> sv_dir, sv_mq, sv_flags, sv_bad;
+    DevBuf<uint64_t> sv_begin, sv_row_off;
+    DevBuf<unsigned long long> sv_cx, sv_ctl;
+};
+
+// what the phases of one mdbg_scan share.  (The order of the members is the order in which they go: the quality sums first -- their side
+// stream waited for, then their buffers -- then the batch's own.)
+struct ScanJob {
+    mdbg_ctx *ctx;
+    const mdbg_reads *reads;
+    const mdbg_scan_params *p;
+    mdbg_minimizers *m;
+    uint32_t n;
+    bool hpc, has_q, has_n;
+    DevBuf<uint32_t> d_cap, d_count, d_rep;
+    DevBuf<uint64_t> d_cap_off;
+    QualitySums quality;
+
+
+    // the fields of ScanArgs that the block path and the general path set alike
+    ScanArgs base_scan_args() {
+        ScanArgs a{};
+        a.words = reads->d_words.p; a.word_off = reads->d_word_off.p; a.len = reads->d_len.p;
+        a.qual = has_q ? reads->d_qual.p : nullptr; a.qual_off = has_q ? reads->d_qual_off.p : nullptr;
+        a.K = p->minimizer_size; a.threshold = density_threshold(p->density);
+        a.trim = p->no_end_trim ? 0u : 1u; a.q_last = p->quality_window == 1 ? 1u : 0u;
+        a.rep = d_rep.p; a.n_rep = p->n_repetitive; a.apply_filters = p->apply_read_filters;
+        a.out_flags = m->d_flags.p;
+        return a;
+    }
+
+    // The exact complexity pass over the few reads the 2-mer bound could not clear, then the reads below --min-read-quality, which keep
+    // their (empty) record (ReadSelection.hpp:901-909).  d_dropped: the block path's counter of the rows these passes take away, read back
+    // into *dropped after each; null on the general path, which counts its rows afterwards.
+    int apply_read_verdicts(const uint32_t *d_suspects, uint32_t n_suspect, uint32_t *d_counts, unsigned long long *d_dropped, uint64_t *dropped) {
+        hipError_t e;
+        if (n_suspect) {
+            LaunchTimer timer(ctx, "complexity_exact");
+            hipLaunchKernelGGL(complexity_exact_kernel, dim3(grid_for((uint64_t)n_suspect * 64, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0,
+                               ctx->stream, reads->d_words.p, reads->d_word_off.p, reads->d_len.p, d_suspects, n_suspect,
+                               d_counts, m->d_flags.p, d_dropped);
+            if (d_dropped && (e = memcpy_sync(ctx, dropped, d_dropped, 8, hipMemcpyDeviceToHost)) != hipSuccess)
+                return set_error(ctx, MDBG_EHIP, "complexity pass failed: %s", hipGetErrorString(e));
         }
-        if ((rc = d_qtab.alloc(ctx, QBINS)) || (rc = d_slo.alloc(ctx, n)) || (rc = d_shi.alloc(ctx, n))) return fail(rc);
-        if ((e = memcpy_sync(ctx, d_qtab.p, tsh.data(), QBINS * 8, hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(set_error(ctx, MDBG_EHIP, "quality table upload failed: %s", hipGetErrorString(e)));
-        // The sums run BESIDE the scan, on the side stream (round 5; until then in front of it, on the context's stream: 61 ms of a 0.52 s
-        // pass over 200 Gbp of ONT reads): they are a second pass over the quality bytes at 3 TB/s -- memory traffic the VALU-bound scan
-        // leaves idle -- in blocks of 768 bytes of LDS that fit beside the scan's.  Their way to the host (pinned memory) and the host's share
-        // (quality_finish) follow on the same stream: nothing of the mean quality is needed before the rows are counted.
-        // ("scan_quality_stream" 0: in front of the scan as before, A/B.)
-        if ((rc = pinned_reserve(ctx, (size_t)n * 20))) return fail(rc);
+        if (quality.any_low_quality) {
+            DevBuf<uint8_t> d_low;
+            MDBG_TRY(d_low.alloc(ctx, n));
+            if ((e = memcpy_sync(ctx, d_low.p, quality.low_quality.data(), n, hipMemcpyHostToDevice)) != hipSuccess)
+                return set_error(ctx, MDBG_EHIP, "low-quality flags upload failed: %s", hipGetErrorString(e));
+            hipLaunchKernelGGL(apply_low_quality_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_low.p, n, d_counts, m->d_flags.p, d_dropped);
+            if (d_dropped) {
+                if ((e = memcpy_sync(ctx, dropped, d_dropped, 8, hipMemcpyDeviceToHost)) != hipSuccess)
+                    return set_error(ctx, MDBG_EHIP, "low-quality pass failed: %s", hipGetErrorString(e));
+            } else if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return set_error(ctx, MDBG_EHIP, "low-quality pass failed");
+        }
+        return MDBG_OK;
+    }
+
+    // the views, in one launch of the variant a batch of reads of segment length would take; then the join
+    int scan_views_and_join(const ScanArgs &a, SegPlan &seg, const RegionPlan &rp, BlockBufs &b) {
+        const uint32_t nv = (uint32_t)seg.n_views;
+        ScanArgs v = a;
+        v.views = seg.views.p; v.view_cx = b.sv_cx.p; v.seg_tiles = ctx->scan_segment_bases / SEG_TILE_BASES;
+        v.out_min = b.sv_min.p; v.out_pos = b.sv_pos.p; v.out_dir = b.sv_dir.p; v.out_mqual = b.sv_mq.p;
+        v.out_count = b.sv_cnt.p; v.out_flags = b.sv_flags.p; v.out_begin = b.sv_begin.p;
+        v.cursor = b.sv_ctl.p; v.n_regions = rp.seg_regions; v.out_capacity = rp.seg_region_cap;
+        v.over_list = b.sv_over.p; v.suspect_list = nullptr; v.list_counters = (uint32_t *)(b.sv_ctl.p + 64);
+        v.skip = nullptr;
+        MDBG_TRY(launch_scan(ctx, v, hpc, has_q, false, nv, rp.seg_pf_limit, false, 0, true));
+        MDBG_TRY(exclusive_scan_u32(ctx, b.sv_cnt.p, b.sv_row_off.p, nv));
         {
-            const bool beside = ctx->scan_quality_beside != 0;
-            hipStream_t qs = beside ? ctx->side_stream : ctx->stream;
-            hipEvent_t ev;
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "hipEventCreate: %s", hipGetErrorString(e)));
-            if (beside) {                                   // behind whatever the context's stream has queued so far (the reads, the table upload)
-                (void)hipEventRecord(ev, ctx->stream);
-                (void)hipStreamWaitEvent(ctx->side_stream, ev, 0);
-            }
-            side_guard.s = ctx->side_stream;     // from here on every way out waits for the side stream before d_slo / d_shi / d_qtab go back to the pool (round-5 ADVICE)
-            {
-                LaunchTimer timer(ctx, "quality_sum", qs);
-                unsigned blocks = grid_for((uint64_t)n * 64, 256, (unsigned)ctx->n_cu * 8u);
-                hipLaunchKernelGGL(quality_sum_kernel, dim3(blocks), dim3(256), 0, qs, reads->d_qual.p, reads->d_qual_off.p,
-                                   reads->d_len.p, n, d_qtab.p, d_slo.p, d_shi.p);
-            }
-            if (!beside) {
-                (void)hipEventRecord(ev, ctx->stream);
-                (void)hipStreamWaitEvent(ctx->side_stream, ev, 0);
-            }
-            (void)hipEventDestroy(ev);
-            uint8_t *h = (uint8_t *)ctx->pinned;
-            if ((e = hipMemcpyAsync(h, d_slo.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess ||
-                (e = hipMemcpyAsync(h + (size_t)n * 8, d_shi.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess ||
-                (e = hipMemcpyAsync(h + (size_t)n * 16, reads->d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->side_stream)) != hipSuccess)
-                return fail(set_error(ctx, MDBG_EHIP, "quality sums download failed: %s", hipGetErrorString(e)));
+            LaunchTimer timer(ctx, "scan_segments");
+            const unsigned cap_blocks = (unsigned)ctx->n_cu * 16u;
+            hipLaunchKernelGGL(seg_mark_views_kernel, dim3(grid_for(nv, 256, cap_blocks)), dim3(256), 0, ctx->stream, b.sv_over.p, (const uint32_t *)(b.sv_ctl.p + 64), nv, b.sv_bad.p);
+            hipLaunchKernelGGL(seg_join_reads_kernel, dim3(grid_for((uint64_t)n * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, a, n, seg.view_off.p,
+                               b.sv_row_off.p, b.sv_bad.p, b.sv_cx.p, seg.read_cut.p, rp.capacity, rp.seg_rows, seg.totals.p);
+            hipLaunchKernelGGL(seg_join_rows_kernel, dim3(grid_for((uint64_t)nv * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, seg.views.p, nv, seg.read_cut.p,
+                               b.sv_row_off.p, b.sv_begin.p, b.sv_cnt.p, rp.seg_region_cap * rp.seg_regions, b.sv_min.p, b.sv_pos.p, b.sv_dir.p, b.sv_mq.p, has_q ? 1 : 0,
+                               m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p, rp.capacity, rp.seg_rows);
         }
-        side_guard.s = ctx->side_stream;
-        quality_pending = true;
-    } else {
-        // no qualities: every read's mean quality is the NaN the reference writes; kept as one value, not n of them (a 40 MB
-        // host fill per 10 M reads sat on the critical path in front of the kernel launch)
-        m->h_mean_quality.clear();
-        m->mean_quality_all = mean_quality_from_sum(0, 0);
+        hipError_t e;
+        if ((e = hipGetLastError()) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan: the join of the views failed: %s", hipGetErrorString(e));
+        return MDBG_OK;
+    }
+
+    // the reads the block kernel skipped for their side masks: counted here by the general kernel with no room to write (masked_args is
+    // what their re-run takes); their suspects join the list, and *n_suspect is read again
+    int count_masked_reads(ScanArgs &masked_args, BlockBufs &b, std::vector<uint32_t> &m_cnt, uint32_t *n_suspect) {
+        const uint32_t n_masked = reads->n_masked;
+        hipError_t e;
+        if ((e = hipMemsetAsync(d_cap_off.p, 0, ((size_t)n + 1) * 8, ctx->stream)) != hipSuccess)
+            return set_error(ctx, MDBG_EHIP, "capacity clear failed: %s", hipGetErrorString(e));
+        masked_args.cursor = nullptr; masked_args.skip = nullptr;
+        masked_args.subset = reads->d_masked_list.p;
+        masked_args.cap_off = d_cap_off.p;                       // every read: no room -- the pass only counts
+        masked_args.invalid = reads->d_invalid.p;
+        masked_args.brk = reads->has_break ? reads->d_break.p : nullptr;
+        masked_args.inline_minq = 1;           // (counts and flags go where the block kernel's go)
+        MDBG_TRY(launch_scan(ctx, masked_args, hpc, has_q, true, n_masked));
+        hipLaunchKernelGGL(listed_suspects_kernel, dim3(grid_for(n_masked, 256)), dim3(256), 0, ctx->stream, reads->d_masked_list.p, n_masked,
+                           m->d_flags.p, b.d_susp.p, (uint32_t *)(b.d_ctl.p + CTL_OVER) + 1);
+        DevBuf<uint32_t> d_mc;
+        MDBG_TRY(d_mc.alloc(ctx, n_masked));
+        hipLaunchKernelGGL(gather_counts_kernel, dim3(grid_for(n_masked, 256)), dim3(256), 0, ctx->stream, reads->d_masked_list.p, n_masked, m->d_cnt.p, d_mc.p);
+        m_cnt.resize(n_masked);
+        unsigned long long ctl_over = 0;
+        if ((e = memcpy_sync(ctx, m_cnt.data(), d_mc.p, (size_t)n_masked * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = memcpy_sync(ctx, &ctl_over, b.d_ctl.p + CTL_OVER, 8, hipMemcpyDeviceToHost)) != hipSuccess)
+            return set_error(ctx, MDBG_EHIP, "masked counts copy failed: %s", hipGetErrorString(e));
+        *n_suspect = (uint32_t)(ctl_over >> 32);
+        return MDBG_OK;
+    }
+
+    // Both kinds of unfinished reads are placed in read order behind the regions (place_unfinished_reads) and scanned by the general kernel,
+    // each kind with its own variant.  *placed stays false when they do not fit the reserve.
+    int rerun_unfinished_reads(const ScanArgs &a, const ScanArgs &masked_args, const RegionPlan &rp, BlockBufs &b, uint32_t n_over, bool route_masked,
+                               const std::vector<uint32_t> &m_cnt, uint64_t h_join_rows, uint64_t *rows, bool *placed) {
+        hipError_t e;
+        std::vector<uint32_t> list(n_over), cnts(n_over);
+        DevBuf<uint32_t> d_oc;
+        MDBG_TRY(d_oc.alloc(ctx, (size_t)n_over + 1));
+        if (n_over) {
+            hipLaunchKernelGGL(gather_counts_kernel, dim3(grid_for(n_over, 256)), dim3(256), 0, ctx->stream, b.d_over.p, n_over, m->d_cnt.p, d_oc.p);
+            if ((e = memcpy_sync(ctx, list.data(), b.d_over.p, (size_t)n_over * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+                (e = memcpy_sync(ctx, cnts.data(), d_oc.p, (size_t)n_over * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+                return set_error(ctx, MDBG_EHIP, "overflow list copy failed: %s", hipGetErrorString(e));
+        }
+        std::vector<uint32_t> m_list(route_masked ? reads->n_masked : 0u);
+        if (!m_list.empty() && (e = memcpy_sync(ctx, m_list.data(), reads->d_masked_list.p, m_list.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+            return set_error(ctx, MDBG_EHIP, "masked list copy failed: %s", hipGetErrorString(e));
+        const Placement pl = place_unfinished_reads(list, cnts, m_list, m_cnt, rp.capacity, rp.capacity + h_join_rows /* behind the joined reads */, rp.reserve);
+        if (!pl.fits) return MDBG_OK;
+        DevBuf<uint32_t> scratch_count;
+        DevBuf<uint8_t> scratch_flags;
+        MDBG_TRY(scratch_count.alloc(ctx, n)); MDBG_TRY(scratch_flags.alloc(ctx, n));
+        DevBuf<uint64_t> d_start[2];
+        DevBuf<uint32_t> d_list[2], d_cnt2[2];
+        for (int kind = 0; kind < 2; kind++) {
+            const uint32_t nk = (uint32_t)pl.list[kind].size();
+            if (!nk) continue;
+            MDBG_TRY(d_start[kind].alloc(ctx, nk)); MDBG_TRY(d_list[kind].alloc(ctx, nk)); MDBG_TRY(d_cnt2[kind].alloc(ctx, nk));
+            if ((e = memcpy_sync(ctx, d_list[kind].p, pl.list[kind].data(), (size_t)nk * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+                (e = memcpy_sync(ctx, d_cnt2[kind].p, pl.cnt[kind].data(), (size_t)nk * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+                (e = memcpy_sync(ctx, d_start[kind].p, pl.start[kind].data(), (size_t)nk * 8, hipMemcpyHostToDevice)) != hipSuccess)
+                return set_error(ctx, MDBG_EHIP, "overflow plan upload failed: %s", hipGetErrorString(e));
+            hipLaunchKernelGGL(place_overflow_kernel, dim3(grid_for(nk, 256)), dim3(256), 0, ctx->stream, d_list[kind].p, d_start[kind].p, d_cnt2[kind].p, nk,
+                               d_cap_off.p, m->d_begin.p);
+        }
+        for (int kind = 0; kind < 2; kind++) {
+            const uint32_t nk = (uint32_t)pl.list[kind].size();
+            if (!nk) continue;
+            ScanArgs r = kind ? masked_args : a;
+            r.cursor = nullptr; r.skip = nullptr;
+            r.subset = d_list[kind].p;
+            r.cap_off = d_cap_off.p;
+            r.inline_minq = 1;
+            r.out_count = scratch_count.p; r.out_flags = scratch_flags.p;
+            MDBG_TRY(launch_scan(ctx, r, hpc, has_q, kind == 1, nk));
+        }
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return set_error(ctx, MDBG_EHIP, "overflow re-run failed: %s", hipGetErrorString(e));
+        *rows += pl.rows;
+        *placed = true;
+        return MDBG_OK;
     }
 
     // ---- plain ACGT without qualities: the block-structured kernel writes every read's rows once, where a wave found room
     // (mdbg_minimizers::scattered); one read-back instead of four.  Batches it cannot take -- a read selecting more than the
-    // LDS stage holds, more rows than the estimate allowed for -- go through the general path below.
-    static const bool no_bump = getenv("MDBG_SCAN_NO_BUMP") != nullptr || getenv("MDBG_SCAN_NO_FAST") != nullptr;
-    // (a read may stage STAGE_CAP minimizers: batches whose longest read is expected to select more go straight to the general path)
-    // A read may stage STAGE_CAP minimizers; the few that select more are re-run by the general kernel into a reserve behind
-    // the regions.  Batches whose AVERAGE read is expected to outgrow the stage go straight to the general path.
-    // A batch in which a few reads carry side-mask bits (an N here and there, soft-masked stretches) stays on this path: the block
-    // kernel skips those reads (ScanArgs::skip) and they alone are counted, placed and scanned by the general kernel below.
-    const uint32_t n_masked = has_n ? reads->n_masked : 0u;
-    const bool route_masked = has_n && reads->d_masked.p && (uint64_t)n_masked * 8ull <= (uint64_t)n + 128ull;
-    const bool block_path_but_length = n && (!has_n || route_masked) && !no_bump && p->density < 0.2f && reads->max_len < (1u << 31);
-    const double rows_per_base = (double)p->density * (hpc ? 0.8 : 1.0) * 1.4;
-    const bool avg_fits_stage = n && (double)reads->n_bases / (double)n * rows_per_base + 24.0 < (double)STAGE_CAP;
-    // "scan_segments": the plain reads of more than one segment are cut into views (segments_dev.hpp) -- 1: in a batch that would leave
-    // this path for its reads' length alone, and which stays if any read can be cut; 2: there and in every batch that takes this path.  Views are
-    // scanned by the candidate-hash kernels (as reads in bump mode are, but for MDBG_SCAN_NO_APPROX and thresholds near 2^64)
-    SegPlan seg;
-    const uint32_t seg_G = ctx->scan_segment_bases;
-    {
-        static const bool no_approx = getenv("MDBG_SCAN_NO_APPROX") != nullptr || getenv("MDBG_SCAN_NO_FAST") != nullptr;      // (launch_scan's own A/B switches)
-        const uint64_t thr = density_threshold(p->density);
-        const bool wanted = ctx->scan_segments == 2u || (ctx->scan_segments == 1u && !avg_fits_stage);        // (2 includes what 1 does)
-        if (block_path_but_length && wanted && reads->max_len > seg_G && (double)seg_G * rows_per_base + 24.0 < (double)STAGE_CAP && !no_approx &&
-            (thr >> 32) + 3ull + (uint64_t)ctx->scan_cand_slack < 0xFFFFFFFFull) {
-            if ((rc = seg_prepass(ctx, reads, route_masked ? reads->d_masked.p : nullptr, seg_G, p->minimizer_size, hpc, seg))) return fail(rc);
-        }
-    }
-    if (block_path_but_length && (avg_fits_stage || seg.n_cut)) {
-        // the output arrays are cut into regions, each with its own cursor (reads are dealt to the waves round-robin, so the regions
-        // fill evenly); small batches use one
-        uint32_t n_regions = 1;
-        while (n_regions < 64u && (uint64_t)n_regions * 8192ull <= n) n_regions <<= 1;
-        const uint64_t region_cap = ((uint64_t)((double)reads->n_bases * (double)p->density * 1.3) + 64ull * n) / n_regions + 4096ull;
-        const uint64_t capacity = region_cap * n_regions;
-        // views write their rows to arrays of their own, cut into regions like the batch's; the join copies them behind the batch's regions,
-        // in front of the reads that outgrow a stage.  (The batch's regions above are still sized from all its bases, the cut reads' included,
-        // which no longer write there: a batch of contigs holds about three times the rows it needs -- 10 bytes a row, 0.0065 rows a base.)
-        const uint64_t seg_bases = std::min<uint64_t>(seg.n_tiles * SEG_TILE_BASES, reads->n_bases);
-        const uint64_t seg_rows = seg.n_cut ? (uint64_t)((double)seg_bases * (double)p->density * 1.3) + 64ull * seg.n_views + 4096ull : 0ull;
-        uint32_t seg_regions = 1;
-        while (seg_regions < 64u && (uint64_t)seg_regions * 8192ull <= seg.n_views) seg_regions <<= 1;
-        const uint64_t seg_region_cap = seg_rows / seg_regions + 4096ull;
-        const uint64_t reserve = capacity / 16 + 65536 + seg_rows;       // rows behind the regions for reads that outgrow the stage (and the joined reads)
-        constexpr uint32_t CTL_OVER = 64, CTL_DROPPED = 65, CTL_WORDS = 66;     // u64 words: cursors, {n_over, n_suspect}, rows dropped
-        DevBuf<uint32_t> d_over, d_susp;
-        DevBuf<unsigned long long> d_ctl;
-        if ((rc = m->d_begin.alloc(ctx, n)) || (rc = m->d_cnt.alloc(ctx, n)) || (rc = d_over.alloc(ctx, n)) || (rc = d_susp.alloc(ctx, n)) ||
-            (rc = d_ctl.alloc(ctx, CTL_WORDS)) || (rc = m->d_min.alloc(ctx, capacity + reserve)) || (rc = m->d_pos.alloc(ctx, capacity + reserve)) ||
-            (rc = m->d_dir.alloc(ctx, capacity + reserve)) || (rc = m->d_mqual.alloc(ctx, capacity + reserve)))
-            return fail(rc);
-        (void)hipMemsetAsync(d_ctl.p, 0, CTL_WORDS * 8, ctx->stream);
-        ScanArgs a{};
-        a.words = reads->d_words.p; a.word_off = reads->d_word_off.p; a.len = reads->d_len.p;
-        a.qual = has_q ? reads->d_qual.p : nullptr;
-        a.qual_off = has_q ? reads->d_qual_off.p : nullptr;
-        a.K = p->minimizer_size;
-        a.threshold = density_threshold(p->density);
-        a.trim = p->no_end_trim ? 0u : 1u;
-        a.q_last = p->quality_window == 1 ? 1u : 0u;
-        a.rep = d_rep.p; a.n_rep = p->n_repetitive;
-        a.apply_filters = p->apply_read_filters;
-        a.out_min = m->d_min.p; a.out_pos = m->d_pos.p; a.out_dir = m->d_dir.p; a.out_mqual = m->d_mqual.p;
-        a.out_count = m->d_cnt.p; a.out_flags = m->d_flags.p;
-        a.cursor = d_ctl.p; a.n_regions = n_regions; a.out_capacity = region_cap; a.out_begin = m->d_begin.p;
-        a.over_list = d_over.p; a.suspect_list = d_susp.p; a.list_counters = (uint32_t *)(d_ctl.p + CTL_OVER);
-        a.cand_slack = ctx->scan_cand_slack;
-        a.guard_slack = ctx->scan_guard_slack;
-        a.wave_priority = ctx->scan_wave_priority;
-        // The pre-filtered variant stages PF_STAGE_CAP rows a read, under half of the above.  A read is expected to fit it below pf_len_limit
-        // bases (the expectation above against that stage: 27 kb at density 0.005f).  The variant is taken when the AVERAGE read is below that;
-        // a few longer reads in such a batch are scanned by the four-wave kernel in a launch of its own (launch_scan), so that a tail of
-        // long reads neither keeps the batch from the variant nor is left to the general kernel
-        const double pf_limit_bases = ((double)PF_STAGE_CAP - 24.0) / ((double)p->density * 0.8 * 1.4);
-        const uint32_t pf_len_limit = hpc && (double)reads->n_bases / (double)n < pf_limit_bases ? (uint32_t)std::min(pf_limit_bases, 4294967295.0) : 0u;
-        const bool pf_split = pf_len_limit && reads->max_len >= pf_len_limit;
+    // LDS stage holds, more rows than the estimate allowed for -- go through the general path: *done stays false (not this batch).
+    int scan_block_path(const BlockRoute &route, SegPlan &seg, bool *done) {
+        const uint32_t n_masked = has_n ? reads->n_masked : 0u;
+        const bool route_masked = route.route_masked;
+        hipError_t e;
+        const RegionPlan rp = plan_regions(n, reads->n_bases, reads->max_len, p->density, hpc, seg, ctx->scan_segment_bases, SEG_TILE_BASES, PF_STAGE_CAP);
+        const uint64_t extent = rp.capacity + rp.reserve;
+        BlockBufs b;
+        MDBG_TRY(m->d_begin.alloc(ctx, n)); MDBG_TRY(m->d_cnt.alloc(ctx, n)); MDBG_TRY(b.d_over.alloc(ctx, n)); MDBG_TRY(b.d_susp.alloc(ctx, n));
+        MDBG_TRY(b.d_ctl.alloc(ctx, CTL_WORDS)); MDBG_TRY(m->d_min.alloc(ctx, extent)); MDBG_TRY(m->d_pos.alloc(ctx, extent));
+        MDBG_TRY(m->d_dir.alloc(ctx, extent)); MDBG_TRY(m->d_mqual.alloc(ctx, extent));
+        (void)hipMemsetAsync(b.d_ctl.p, 0, CTL_WORDS * 8, ctx->stream);
+        ScanArgs a = base_scan_args();
+        a.out_min = m->d_min.p; a.out_pos = m->d_pos.p; a.out_dir = m->d_dir.p; a.out_mqual = m->d_mqual.p; a.out_count = m->d_cnt.p;
+        a.cursor = b.d_ctl.p; a.n_regions = rp.n_regions; a.out_capacity = rp.region_cap; a.out_begin = m->d_begin.p;
+        a.over_list = b.d_over.p; a.suspect_list = b.d_susp.p; a.list_counters = (uint32_t *)(b.d_ctl.p + CTL_OVER);
+        a.cand_slack = ctx->scan_cand_slack; a.guard_slack = ctx->scan_guard_slack; a.wave_priority = ctx->scan_wave_priority;
         a.skip = seg.n_cut ? seg.skip.p : (route_masked ? reads->d_masked.p : nullptr);       // (the plan's flags: masked or cut)
-        DevBuf<uint32_t> sv_min, sv_pos, sv_cnt, sv_over;
-        DevBuf<uint8_t> sv_dir, sv_mq, sv_flags, sv_bad;
-        DevBuf<uint64_t> sv_begin, sv_row_off;
-        DevBuf<unsigned long long> sv_cx, sv_ctl;
-        constexpr uint32_t SCTL_WORDS = 66;          // the views' cursors and [64] = {views listed, -}
         const uint32_t nv = (uint32_t)seg.n_views;
         if (seg.n_cut) {
-            const uint64_t ext = seg_region_cap * seg_regions;
-            if ((rc = sv_min.alloc(ctx, ext)) || (rc = sv_pos.alloc(ctx, ext)) || (rc = sv_dir.alloc(ctx, ext)) || (rc = sv_mq.alloc(ctx, has_q ? ext : 1)) ||
-                (rc = sv_cnt.alloc(ctx, nv)) || (rc = sv_over.alloc(ctx, nv)) || (rc = sv_flags.alloc(ctx, nv)) || (rc = sv_bad.alloc(ctx, nv)) ||
-                (rc = sv_begin.alloc(ctx, nv)) || (rc = sv_row_off.alloc(ctx, (size_t)nv + 1)) || (rc = sv_cx.alloc(ctx, nv)) || (rc = sv_ctl.alloc(ctx, SCTL_WORDS)))
-                return fail(rc);
-            if ((e = hipMemsetAsync(sv_ctl.p, 0, SCTL_WORDS * 8, ctx->stream)) != hipSuccess || (e = hipMemsetAsync(sv_bad.p, 0, nv, ctx->stream)) != hipSuccess)
-                return fail(set_error(ctx, MDBG_EHIP, "scan: clearing the views' counters failed: %s", hipGetErrorString(e)));
+            const uint64_t ext = rp.seg_region_cap * rp.seg_regions;
+            MDBG_TRY(b.sv_min.alloc(ctx, ext)); MDBG_TRY(b.sv_pos.alloc(ctx, ext)); MDBG_TRY(b.sv_dir.alloc(ctx, ext)); MDBG_TRY(b.sv_mq.alloc(ctx, has_q ? ext : 1));
+            MDBG_TRY(b.sv_cnt.alloc(ctx, nv)); MDBG_TRY(b.sv_over.alloc(ctx, nv)); MDBG_TRY(b.sv_flags.alloc(ctx, nv)); MDBG_TRY(b.sv_bad.alloc(ctx, nv));
+            MDBG_TRY(b.sv_begin.alloc(ctx, nv)); MDBG_TRY(b.sv_row_off.alloc(ctx, (size_t)nv + 1)); MDBG_TRY(b.sv_cx.alloc(ctx, nv)); MDBG_TRY(b.sv_ctl.alloc(ctx, SCTL_WORDS));
+            if ((e = hipMemsetAsync(b.sv_ctl.p, 0, SCTL_WORDS * 8, ctx->stream)) != hipSuccess || (e = hipMemsetAsync(b.sv_bad.p, 0, nv, ctx->stream)) != hipSuccess)
+                return set_error(ctx, MDBG_EHIP, "scan: clearing the views' counters failed: %s", hipGetErrorString(e));
         }
         unsigned long long h_ctl[CTL_WORDS], h_sctl[SCTL_WORDS] = {0}, h_seg[8] = {0}, h_join_rows = 0;
         {
-            ScanTurn scan_turn(ctx->device);      // one scan kernel at a time per device (see below)
+            ScanTurn scan_turn(ctx->device);      // one scan kernel at a time per device (see scan_general_path)
             if (!scans_may_interleave()) scan_turn.lock();
             // (a batch all of whose reads are cut or masked -- contigs -- has nothing for its own launch: the join and the masked pass below
             // set those reads' begin, count and flags)
             const bool nothing_left = seg.n_cut && seg.n_cut + (route_masked ? (uint64_t)n_masked : 0ull) >= n;
-            if (!nothing_left && (rc = launch_scan(ctx, a, hpc, has_q, false, n, pf_len_limit, pf_split, reads->n_bases))) return fail(rc);
-            if (seg.n_cut) {
-                // the views, in one launch of the variant a batch of reads of segment length would take; then the join
-                ScanArgs v = a;
-                v.views = seg.views.p; v.view_cx = sv_cx.p; v.seg_tiles = seg_G / SEG_TILE_BASES;
-                v.out_min = sv_min.p; v.out_pos = sv_pos.p; v.out_dir = sv_dir.p; v.out_mqual = sv_mq.p;
-                v.out_count = sv_cnt.p; v.out_flags = sv_flags.p; v.out_begin = sv_begin.p;
-                v.cursor = sv_ctl.p; v.n_regions = seg_regions; v.out_capacity = seg_region_cap;
-                v.over_list = sv_over.p; v.suspect_list = nullptr; v.list_counters = (uint32_t *)(sv_ctl.p + 64);
-                v.skip = nullptr;
-                const uint32_t seg_pf_limit = hpc && (double)seg_G < pf_limit_bases ? (uint32_t)std::min(pf_limit_bases, 4294967295.0) : 0u;
-                if ((rc = launch_scan(ctx, v, hpc, has_q, false, nv, seg_pf_limit, false, 0, true))) return fail(rc);
-                if ((rc = exclusive_scan_u32(ctx, sv_cnt.p, sv_row_off.p, nv))) return fail(rc);
-                {
-                    LaunchTimer timer(ctx, "scan_segments");
-                    const unsigned cap_blocks = (unsigned)ctx->n_cu * 16u;
-                    hipLaunchKernelGGL(seg_mark_views_kernel, dim3(grid_for(nv, 256, cap_blocks)), dim3(256), 0, ctx->stream, sv_over.p, (const uint32_t *)(sv_ctl.p + 64), nv, sv_bad.p);
-                    hipLaunchKernelGGL(seg_join_reads_kernel, dim3(grid_for((uint64_t)n * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, a, n, seg.view_off.p,
-                                       sv_row_off.p, sv_bad.p, sv_cx.p, seg.read_cut.p, capacity, seg_rows, seg.totals.p);
-                    hipLaunchKernelGGL(seg_join_rows_kernel, dim3(grid_for((uint64_t)nv * 64u, 256, cap_blocks)), dim3(256), 0, ctx->stream, seg.views.p, nv, seg.read_cut.p,
-                                       sv_row_off.p, sv_begin.p, sv_cnt.p, seg_region_cap * seg_regions, sv_min.p, sv_pos.p, sv_dir.p, sv_mq.p, has_q ? 1 : 0,
-                                       m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p, capacity, seg_rows);
-                }
-                if ((e = hipGetLastError()) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan: the join of the views failed: %s", hipGetErrorString(e)));
-            }
-            if ((rc = quality_finish())) return fail(rc);          // host work while the kernel runs
-            e = memcpy_sync(ctx, h_ctl, d_ctl.p, CTL_WORDS * 8, hipMemcpyDeviceToHost);
+            if (!nothing_left) MDBG_TRY(launch_scan(ctx, a, hpc, has_q, false, n, rp.pf_len_limit, rp.pf_split, reads->n_bases));
+            if (seg.n_cut) MDBG_TRY(scan_views_and_join(a, seg, rp, b));
+            MDBG_TRY(quality.finish(ctx, p, m));          // host work while the kernel runs
+            e = memcpy_sync(ctx, h_ctl, b.d_ctl.p, CTL_WORDS * 8, hipMemcpyDeviceToHost);
             if (e == hipSuccess && seg.n_cut) {
-                if ((e = memcpy_sync(ctx, h_sctl, sv_ctl.p, SCTL_WORDS * 8, hipMemcpyDeviceToHost)) == hipSuccess &&
+                if ((e = memcpy_sync(ctx, h_sctl, b.sv_ctl.p, SCTL_WORDS * 8, hipMemcpyDeviceToHost)) == hipSuccess &&
                     (e = memcpy_sync(ctx, h_seg, seg.totals.p, 64, hipMemcpyDeviceToHost)) == hipSuccess)
-                    e = memcpy_sync(ctx, &h_join_rows, sv_row_off.p + nv, 8, hipMemcpyDeviceToHost);
+                    e = memcpy_sync(ctx, &h_join_rows, b.sv_row_off.p + nv, 8, hipMemcpyDeviceToHost);
             }
         }
-        if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan counters copy failed: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan counters copy failed: %s", hipGetErrorString(e));
         uint64_t rows = 0;
         bool fits = true;
-        for (uint32_t g = 0; g < n_regions; g++) { rows += h_ctl[g]; fits = fits && h_ctl[g] <= region_cap; }
+        for (uint32_t g = 0; g < rp.n_regions; g++) { rows += h_ctl[g]; fits = fits && h_ctl[g] <= rp.region_cap; }
         if (seg.n_cut) {          // the views' rows fitted their regions and the joined reads their room; the rows of the reads joined
-            for (uint32_t g = 0; g < seg_regions; g++) fits = fits && h_sctl[g] <= seg_region_cap;
-            fits = fits && h_seg[4] == 0ull && h_join_rows <= seg_rows;
+            for (uint32_t g = 0; g < rp.seg_regions; g++) fits = fits && h_sctl[g] <= rp.seg_region_cap;
+            fits = fits && h_seg[4] == 0ull && h_join_rows <= rp.seg_rows;
             rows += h_seg[2];
         }
         const uint32_t n_over = (uint32_t)h_ctl[CTL_OVER];
         uint32_t n_suspect = (uint32_t)(h_ctl[CTL_OVER] >> 32);
         // ---- reads the block kernel did not finish: those that outgrew its stage (long reads; listed with their exact counts) and
-        // those it skipped for their side masks (counted here by the general kernel with no room to write).  Both kinds are placed
-        // in read order behind the regions and scanned by the general kernel, each kind with its own variant.
+        // those it skipped for their side masks
         ScanArgs masked_args = a;
         std::vector<uint32_t> m_cnt;
         bool counted = true;
-        if (fits && n_masked && route_masked) {
-            if ((e = hipMemsetAsync(d_cap_off.p, 0, ((size_t)n + 1) * 8, ctx->stream)) != hipSuccess)
-                return fail(set_error(ctx, MDBG_EHIP, "capacity clear failed: %s", hipGetErrorString(e)));
-            masked_args.cursor = nullptr; masked_args.skip = nullptr;
-            masked_args.subset = reads->d_masked_list.p;
-            masked_args.cap_off = d_cap_off.p;                       // every read: no room -- the pass only counts
-            masked_args.invalid = reads->d_invalid.p;
-            masked_args.brk = reads->has_break ? reads->d_break.p : nullptr;
-            masked_args.q_last = p->quality_window == 1 ? 1u : 0u;
-            masked_args.inline_minq = 1;
-            masked_args.out_count = m->d_cnt.p; masked_args.out_flags = m->d_flags.p;
-            if ((rc = launch_scan(ctx, masked_args, hpc, has_q, true, n_masked))) return fail(rc);
-            hipLaunchKernelGGL(listed_suspects_kernel, dim3(grid_for(n_masked, 256)), dim3(256), 0, ctx->stream, reads->d_masked_list.p, n_masked,
-                               m->d_flags.p, d_susp.p, (uint32_t *)(d_ctl.p + CTL_OVER) + 1);
-            DevBuf<uint32_t> d_mc;
-            if ((rc = d_mc.alloc(ctx, n_masked))) return fail(rc);
-            hipLaunchKernelGGL(gather_counts_kernel, dim3(grid_for(n_masked, 256)), dim3(256), 0, ctx->stream, reads->d_masked_list.p, n_masked, m->d_cnt.p, d_mc.p);
-            m_cnt.resize(n_masked);
-            unsigned long long ctl_over = 0;
-            if ((e = memcpy_sync(ctx, m_cnt.data(), d_mc.p, (size_t)n_masked * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-                (e = memcpy_sync(ctx, &ctl_over, d_ctl.p + CTL_OVER, 8, hipMemcpyDeviceToHost)) != hipSuccess)
-                return fail(set_error(ctx, MDBG_EHIP, "masked counts copy failed: %s", hipGetErrorString(e)));
-            n_suspect = (uint32_t)(ctl_over >> 32);
-        } else if (n_masked && route_masked) counted = false;
+        if (fits && n_masked && route_masked) MDBG_TRY(count_masked_reads(masked_args, b, m_cnt, &n_suspect));
+        else if (n_masked && route_masked) counted = false;
         bool placed = n_over == 0 && (!route_masked || n_masked == 0);
-        if (fits && counted && !placed && n_over <= n / 4 + 16) {
-            std::vector<uint32_t> list(n_over), cnts(n_over);
-            DevBuf<uint32_t> d_oc;
-            if ((rc = d_oc.alloc(ctx, (size_t)n_over + 1))) return fail(rc);
-            if (n_over) {
-                hipLaunchKernelGGL(gather_counts_kernel, dim3(grid_for(n_over, 256)), dim3(256), 0, ctx->stream, d_over.p, n_over, m->d_cnt.p, d_oc.p);
-                if ((e = memcpy_sync(ctx, list.data(), d_over.p, (size_t)n_over * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-                    (e = memcpy_sync(ctx, cnts.data(), d_oc.p, (size_t)n_over * 4, hipMemcpyDeviceToHost)) != hipSuccess)
-                    return fail(set_error(ctx, MDBG_EHIP, "overflow list copy failed: %s", hipGetErrorString(e)));
-            }
-            std::vector<uint32_t> m_list(route_masked ? n_masked : 0u);
-            if (!m_list.empty() && (e = memcpy_sync(ctx, m_list.data(), reads->d_masked_list.p, m_list.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess)
-                return fail(set_error(ctx, MDBG_EHIP, "masked list copy failed: %s", hipGetErrorString(e)));
-            // one order over both kinds: (read, count, kind)
-            struct Item { uint32_t read, cnt, kind; };
-            std::vector<Item> items;
-            items.reserve((size_t)n_over + m_list.size());
-            for (uint32_t i = 0; i < n_over; i++) items.push_back(Item{list[i], cnts[i], 0u});
-            for (size_t i = 0; i < m_list.size(); i++) items.push_back(Item{m_list[i], m_cnt[i], 1u});
-            std::sort(items.begin(), items.end(), [](const Item &x, const Item &y) { return x.read < y.read; });
-            std::vector<uint32_t> slist[2], scnt[2];
-            std::vector<uint64_t> sstart[2];
-            uint64_t at = capacity + h_join_rows;       // (behind the joined reads)
-            for (const Item &it : items) { slist[it.kind].push_back(it.read); scnt[it.kind].push_back(it.cnt); sstart[it.kind].push_back(at); at += it.cnt; }
-            if (at - capacity <= reserve) {
-                DevBuf<uint32_t> scratch_count;
-                DevBuf<uint8_t> scratch_flags;
-                if ((rc = scratch_count.alloc(ctx, n)) || (rc = scratch_flags.alloc(ctx, n))) return fail(rc);
-                DevBuf<uint64_t> d_start[2];
-                DevBuf<uint32_t> d_list[2], d_cnt2[2];
-                for (int kind = 0; kind < 2; kind++) {
-                    const uint32_t nk = (uint32_t)slist[kind].size();
-                    if (!nk) continue;
-                    if ((rc = d_start[kind].alloc(ctx, nk)) || (rc = d_list[kind].alloc(ctx, nk)) || (rc = d_cnt2[kind].alloc(ctx, nk))) return fail(rc);
-                    if ((e = memcpy_sync(ctx, d_list[kind].p, slist[kind].data(), (size_t)nk * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-                        (e = memcpy_sync(ctx, d_cnt2[kind].p, scnt[kind].data(), (size_t)nk * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-                        (e = memcpy_sync(ctx, d_start[kind].p, sstart[kind].data(), (size_t)nk * 8, hipMemcpyHostToDevice)) != hipSuccess)
-                        return fail(set_error(ctx, MDBG_EHIP, "overflow plan upload failed: %s", hipGetErrorString(e)));
-                    hipLaunchKernelGGL(place_overflow_kernel, dim3(grid_for(nk, 256)), dim3(256), 0, ctx->stream, d_list[kind].p, d_start[kind].p, d_cnt2[kind].p, nk,
-                                       d_cap_off.p, m->d_begin.p);
-                }
-                for (int kind = 0; kind < 2; kind++) {
-                    const uint32_t nk = (uint32_t)slist[kind].size();
-                    if (!nk) continue;
-                    ScanArgs b = kind ? masked_args : a;
-                    b.cursor = nullptr; b.skip = nullptr;
-                    b.subset = d_list[kind].p;
-                    b.cap_off = d_cap_off.p;
-                    b.q_last = p->quality_window == 1 ? 1u : 0u;
-                    b.inline_minq = 1;
-                    b.out_count = scratch_count.p; b.out_flags = scratch_flags.p;
-                    if ((rc = launch_scan(ctx, b, hpc, has_q, kind == 1, nk))) return fail(rc);
-                }
-                if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "overflow re-run failed: %s", hipGetErrorString(e)));
-                rows += at - capacity - h_join_rows;
-                placed = true;
-            }
-        }
-        if (placed && fits) {
-            uint64_t dropped = 0;
-            if (n_suspect) {
-                LaunchTimer timer(ctx, "complexity_exact");
-                hipLaunchKernelGGL(complexity_exact_kernel, dim3(grid_for((uint64_t)n_suspect * 64, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0,
-                                   ctx->stream, reads->d_words.p, reads->d_word_off.p, reads->d_len.p, d_susp.p, n_suspect,
-                                   m->d_cnt.p, m->d_flags.p, d_ctl.p + CTL_DROPPED);
-                if ((e = memcpy_sync(ctx, &dropped, d_ctl.p + CTL_DROPPED, 8, hipMemcpyDeviceToHost)) != hipSuccess)
-                    return fail(set_error(ctx, MDBG_EHIP, "complexity pass failed: %s", hipGetErrorString(e)));
-            }
-            if (any_low_quality) {          // reads below --min-read-quality keep their (empty) record (ReadSelection.hpp:901-909)
-                DevBuf<uint8_t> d_low;
-                if ((rc = d_low.alloc(ctx, n))) return fail(rc);
-                if ((e = memcpy_sync(ctx, d_low.p, low_quality.data(), n, hipMemcpyHostToDevice)) != hipSuccess)
-                    return fail(set_error(ctx, MDBG_EHIP, "low-quality flags upload failed: %s", hipGetErrorString(e)));
-                hipLaunchKernelGGL(apply_low_quality_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_low.p, n, m->d_cnt.p, m->d_flags.p,
-                                   d_ctl.p + CTL_DROPPED);
-                if ((e = memcpy_sync(ctx, &dropped, d_ctl.p + CTL_DROPPED, 8, hipMemcpyDeviceToHost)) != hipSuccess)
-                    return fail(set_error(ctx, MDBG_EHIP, "low-quality pass failed: %s", hipGetErrorString(e)));
-            }
-            if (!has_q) (void)hipMemsetAsync(m->d_mqual.p, 1, capacity + reserve, ctx->stream);     // no qualities: ReadSelection.hpp:1047-1051
-            m->scattered = true;
-            m->owner = ctx;
-            m->n_rows = capacity + reserve;        // extent of the row arrays (regions are not filled to the brim)
-            m->n_min = rows - dropped;
-            if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan failed: %s", hipGetErrorString(e)));
-            ctx->scan_info[7] = h_seg[3];
-            *out = m;
+        if (fits && counted && !placed && overflowing_reads_are_few(n_over, n))
+            MDBG_TRY(rerun_unfinished_reads(a, masked_args, rp, b, n_over, route_masked, m_cnt, h_join_rows, &rows, &placed));
+        if (!(placed && fits)) {
+            // not this batch: give the buffers back and take the general path
+            m->d_begin.release(); m->d_cnt.release(); m->d_min.release(); m->d_pos.release(); m->d_dir.release(); m->d_mqual.release();
             return MDBG_OK;
         }
-        // not this batch: give the buffers back and take the general path
-        m->d_begin.release(); m->d_cnt.release(); m->d_min.release(); m->d_pos.release(); m->d_dir.release(); m->d_mqual.release();
+        uint64_t dropped = 0;
+        MDBG_TRY(apply_read_verdicts(b.d_susp.p, n_suspect, m->d_cnt.p, b.d_ctl.p + CTL_DROPPED, &dropped));
+        if (!has_q) (void)hipMemsetAsync(m->d_mqual.p, 1, extent, ctx->stream);     // no qualities: ReadSelection.hpp:1047-1051
+        m->scattered = true;
+        m->owner = ctx;
+        m->n_rows = extent;        // extent of the row arrays (regions are not filled to the brim)
+        m->n_min = rows - dropped;
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan failed: %s", hipGetErrorString(e));
+        ctx->scan_info[7] = h_seg[3];
+        *done = true;
+        return MDBG_OK;
     }
 
-    if (n) hipLaunchKernelGGL(capacity_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream,
-                              reads->d_len.p, n, p->density, d_cap.p);
-    if ((rc = exclusive_scan_u32(ctx, d_cap.p, d_cap_off.p, n))) return fail(rc);
-    uint64_t cap_total = 0;
-    e = memcpy_sync(ctx, &cap_total, d_cap_off.p + n, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "cap total copy failed"));
-
-    DevBuf<uint32_t> p_min, p_pos, p_os, p_oe;
-    DevBuf<uint8_t> p_dir;
-    if ((rc = p_min.alloc(ctx, cap_total)) || (rc = p_pos.alloc(ctx, cap_total)) || (rc = p_dir.alloc(ctx, cap_total)))
-        return fail(rc);
-    if (has_q && ((rc = p_os.alloc(ctx, cap_total)) || (rc = p_oe.alloc(ctx, cap_total)))) return fail(rc);
-
-    ScanArgs a{};
-    a.words = reads->d_words.p; a.word_off = reads->d_word_off.p; a.len = reads->d_len.p;
-    a.invalid = has_n ? reads->d_invalid.p : nullptr;
-    a.brk = reads->has_break ? reads->d_break.p : nullptr;
-    a.qual = has_q ? reads->d_qual.p : nullptr;
-    a.qual_off = has_q ? reads->d_qual_off.p : nullptr;
-    a.K = p->minimizer_size;
-    a.threshold = density_threshold(p->density);
-    a.q_last = p->quality_window == 1 ? 1u : 0u;
-    a.trim = p->no_end_trim ? 0u : 1u;
-    a.rep = d_rep.p; a.n_rep = p->n_repetitive;
-    a.apply_filters = p->apply_read_filters;
-    a.subset = nullptr;
-    a.cap_off = d_cap_off.p;
-    a.out_min = p_min.p; a.out_pos = p_pos.p; a.out_dir = p_dir.p;
-    a.out_os = p_os.p; a.out_oe = p_oe.p; a.out_mqual = nullptr; a.inline_minq = 0;
-    a.out_count = d_count.p; a.out_flags = m->d_flags.p;
-    // One scan kernel at a time per device, whatever the number of contexts: two of them interleaved workgroup by
-    // workgroup each run at half speed and worse (measured: 2 x 15.5 ms alone, 2 x 30 ms interleaved), while everything
-    // else a second context does -- table building, purge, RCCL -- overlaps a running scan nicely.  The lock covers the
-    // launch and is released when the kernel has finished (the counter download below waits for it).
-    ScanTurn scan_turn(ctx->device);
-    if (!scans_may_interleave()) scan_turn.lock();
-    if (n && (rc = launch_scan(ctx, a, hpc, has_q, has_n, n))) return fail(rc);
-    if ((rc = quality_finish())) return fail(rc);                  // host work while the kernel runs (once: the call above may have done it)
-
-    // overflow handling (reads that selected more than their padded capacity are re-run with exact room)
-    // and the exact complexity pass over the few reads the 2-mer bound could not clear
-    DevBuf<uint32_t> d_list, d_suspects, d_nlist;
-    if ((rc = d_list.alloc(ctx, n)) || (rc = d_suspects.alloc(ctx, n)) || (rc = d_nlist.alloc(ctx, 2))) return fail(rc);
-    (void)hipMemsetAsync(d_nlist.p, 0, 8, ctx->stream);
-    if (n) hipLaunchKernelGGL(post_scan_lists_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream,
-                              d_count.p, d_cap.p, m->d_flags.p, n, d_list.p, d_suspects.p, d_nlist.p);
-    uint32_t h_counters[2] = {0, 0};
-    e = memcpy_sync(ctx, h_counters, d_nlist.p, 8, hipMemcpyDeviceToHost);
-    if (scan_turn.owns_lock()) scan_turn.unlock();
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "overflow count copy failed: %s", hipGetErrorString(e)));
-    const uint32_t n_over = h_counters[0], n_suspect = h_counters[1];
-    if (n_suspect) {
-        LaunchTimer timer(ctx, "complexity_exact");
-        hipLaunchKernelGGL(complexity_exact_kernel, dim3(grid_for((uint64_t)n_suspect * 64, 256, (unsigned)ctx->n_cu * 8u)), dim3(256), 0,
-                           ctx->stream, reads->d_words.p, reads->d_word_off.p, reads->d_len.p, d_suspects.p, n_suspect,
-                           d_count.p, m->d_flags.p, (unsigned long long *)nullptr);
-    }
-    if (any_low_quality) {
-        DevBuf<uint8_t> d_low;
-        if ((rc = d_low.alloc(ctx, n))) return fail(rc);
-        if ((e = memcpy_sync(ctx, d_low.p, low_quality.data(), n, hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(set_error(ctx, MDBG_EHIP, "low-quality flags upload failed: %s", hipGetErrorString(e)));
-        hipLaunchKernelGGL(apply_low_quality_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_low.p, n, d_count.p, m->d_flags.p, (unsigned long long *)nullptr);
-        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "low-quality pass failed"));
+    template <bool Q, int G>
+    void launch_compact(unsigned blocks, const uint32_t *p_min, const uint32_t *p_pos, const uint8_t *p_dir, const uint32_t *p_os, const uint32_t *p_oe) {
+        hipLaunchKernelGGL((compact_minimizers_kernel<Q, G>), dim3(blocks), dim3(256), 0, ctx->stream, d_cap_off.p, m->d_off.p, n, p_min, p_pos, p_dir,
+                           Q ? p_os : nullptr, Q ? p_oe : nullptr, Q ? reads->d_qual.p : nullptr, Q ? reads->d_qual_off.p : nullptr,
+                           m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
     }
 
-    // dense offsets from the true counts
-    if ((rc = exclusive_scan_u32(ctx, d_count.p, m->d_off.p, n))) return fail(rc);
-    uint64_t total = 0;
-    e = memcpy_sync(ctx, &total, m->d_off.p + n, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "total copy failed"));
-    m->n_min = total;
-    if ((rc = m->d_min.alloc(ctx, total)) || (rc = m->d_pos.alloc(ctx, total)) || (rc = m->d_dir.alloc(ctx, total)) ||
-        (rc = m->d_mqual.alloc(ctx, total)))
-        return fail(rc);
+    // every kind of batch: padded slots per read, the general kernel (or, for plain reads, a block-structured one without cursors), the
+    // counts, then dense rows
+    int scan_general_path() {
+        hipError_t e;
+        if (n) hipLaunchKernelGGL(capacity_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream,
+                                  reads->d_len.p, n, p->density, d_cap.p);
+        MDBG_TRY(exclusive_scan_u32(ctx, d_cap.p, d_cap_off.p, n));
+        uint64_t cap_total = 0;
+        e = memcpy_sync(ctx, &cap_total, d_cap_off.p + n, 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "cap total copy failed");
 
-    if (n) {
-        const bool few = total / (n ? n : 1) < 96;   // minimizers per read
-        unsigned blocks = grid_for((uint64_t)n * (few ? 16 : 64), 256, (unsigned)ctx->n_cu * (few ? 32u : 8u));
-        LaunchTimer timer(ctx, "scan_compact");
-#define MDBG_COMPACT(Q, G, ...) hipLaunchKernelGGL((compact_minimizers_kernel<Q, G>), dim3(blocks), dim3(256), 0, ctx->stream, __VA_ARGS__)
-        if (has_q) {
-            if (few) MDBG_COMPACT(true, 16, d_cap_off.p, m->d_off.p, n, p_min.p, p_pos.p, p_dir.p, p_os.p, p_oe.p, reads->d_qual.p, reads->d_qual_off.p,
-                                  m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
-            else MDBG_COMPACT(true, 64, d_cap_off.p, m->d_off.p, n, p_min.p, p_pos.p, p_dir.p, p_os.p, p_oe.p, reads->d_qual.p, reads->d_qual_off.p,
-                              m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
-        } else {
-            if (few) MDBG_COMPACT(false, 16, d_cap_off.p, m->d_off.p, n, p_min.p, p_pos.p, p_dir.p, nullptr, nullptr, nullptr, nullptr,
-                                  m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
-            else MDBG_COMPACT(false, 64, d_cap_off.p, m->d_off.p, n, p_min.p, p_pos.p, p_dir.p, nullptr, nullptr, nullptr, nullptr,
-                              m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
+        DevBuf<uint32_t> p_min, p_pos, p_os, p_oe;
+        DevBuf<uint8_t> p_dir;
+        MDBG_TRY(p_min.alloc(ctx, cap_total)); MDBG_TRY(p_pos.alloc(ctx, cap_total)); MDBG_TRY(p_dir.alloc(ctx, cap_total));
+        if (has_q) { MDBG_TRY(p_os.alloc(ctx, cap_total)); MDBG_TRY(p_oe.alloc(ctx, cap_total)); }
+
+        ScanArgs a = base_scan_args();
+        a.invalid = has_n ? reads->d_invalid.p : nullptr;
+        a.brk = reads->has_break ? reads->d_break.p : nullptr;
+        a.cap_off = d_cap_off.p;
+        a.out_min = p_min.p; a.out_pos = p_pos.p; a.out_dir = p_dir.p;
+        a.out_os = p_os.p; a.out_oe = p_oe.p; a.out_mqual = nullptr; a.inline_minq = 0;
+        a.out_count = d_count.p;
+        // One scan kernel at a time per device, whatever the number of contexts: two of them interleaved workgroup by
+        // workgroup each run at half speed and worse (measured: 2 x 15.5 ms alone, 2 x 30 ms interleaved), while everything
+        // else a second context does -- table building, purge, RCCL -- overlaps a running scan nicely.  The lock covers the
+        // launch and is released when the kernel has finished (the counter download below waits for it).
+        ScanTurn scan_turn(ctx->device);
+        if (!scans_may_interleave()) scan_turn.lock();
+        if (n) MDBG_TRY(launch_scan(ctx, a, hpc, has_q, has_n, n));
+        MDBG_TRY(quality.finish(ctx, p, m));                  // host work while the kernel runs (once: an abandoned block path has done it)
+
+        // overflow handling (reads that selected more than their padded capacity are re-run with exact room)
+        // and the exact complexity pass over the few reads the 2-mer bound could not clear
+        DevBuf<uint32_t> d_list, d_suspects, d_nlist;
+        MDBG_TRY(d_list.alloc(ctx, n)); MDBG_TRY(d_suspects.alloc(ctx, n)); MDBG_TRY(d_nlist.alloc(ctx, 2));
+        (void)hipMemsetAsync(d_nlist.p, 0, 8, ctx->stream);
+        if (n) hipLaunchKernelGGL(post_scan_lists_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream,
+                                  d_count.p, d_cap.p, m->d_flags.p, n, d_list.p, d_suspects.p, d_nlist.p);
+        uint32_t h_counters[2] = {0, 0};
+        e = memcpy_sync(ctx, h_counters, d_nlist.p, 8, hipMemcpyDeviceToHost);
+        if (scan_turn.owns_lock()) scan_turn.unlock();
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "overflow count copy failed: %s", hipGetErrorString(e));
+        const uint32_t n_over = h_counters[0], n_suspect = h_counters[1];
+        MDBG_TRY(apply_read_verdicts(d_suspects.p, n_suspect, d_count.p, nullptr, nullptr));
+
+        // dense offsets from the true counts
+        MDBG_TRY(exclusive_scan_u32(ctx, d_count.p, m->d_off.p, n));
+        uint64_t total = 0;
+        e = memcpy_sync(ctx, &total, m->d_off.p + n, 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "total copy failed");
+        m->n_min = total;
+        MDBG_TRY(m->d_min.alloc(ctx, total)); MDBG_TRY(m->d_pos.alloc(ctx, total)); MDBG_TRY(m->d_dir.alloc(ctx, total)); MDBG_TRY(m->d_mqual.alloc(ctx, total));
+
+        if (n) {
+            const bool few = total / (n ? n : 1) < 96;   // minimizers per read
+            unsigned blocks = grid_for((uint64_t)n * (few ? 16 : 64), 256, (unsigned)ctx->n_cu * (few ? 32u : 8u));
+            LaunchTimer timer(ctx, "scan_compact");
+            if (has_q) { if (few) launch_compact<true, 16>(blocks, p_min.p, p_pos.p, p_dir.p, p_os.p, p_oe.p); else launch_compact<true, 64>(blocks, p_min.p, p_pos.p, p_dir.p, p_os.p, p_oe.p); }
+            else { if (few) launch_compact<false, 16>(blocks, p_min.p, p_pos.p, p_dir.p, nullptr, nullptr); else launch_compact<false, 64>(blocks, p_min.p, p_pos.p, p_dir.p, nullptr, nullptr); }
         }
-#undef MDBG_COMPACT
-    }
-    if (n_over) {
-        // reads that overflowed their padded slots are re-run straight into their dense slots
-        // (capacity == exact count), after the gather so the exact rows win over the truncated prefix
-        ScanArgs b = a;
-        b.subset = d_list.p;
-        b.cap_off = m->d_off.p;
-        b.out_min = m->d_min.p; b.out_pos = m->d_pos.p; b.out_dir = m->d_dir.p;
-        b.out_mqual = m->d_mqual.p; b.inline_minq = 1;
-        DevBuf<uint32_t> scratch_count;
+        DevBuf<uint32_t> scratch_count;     // (of the re-run below: they go after the last synchronisation)
         DevBuf<uint8_t> scratch_flags;
-        if ((rc = scratch_count.alloc(ctx, n)) || (rc = scratch_flags.alloc(ctx, n))) return fail(rc);
-        b.out_count = scratch_count.p; b.out_flags = scratch_flags.p;
-        if ((rc = launch_scan(ctx, b, hpc, has_q, has_n, n_over))) return fail(rc);
-        (void)hipStreamSynchronize(ctx->stream);
+        if (n_over) {
+            // reads that overflowed their padded slots are re-run straight into their dense slots
+            // (capacity == exact count), after the gather so the exact rows win over the truncated prefix
+            ScanArgs r = a;
+            r.subset = d_list.p;
+            r.cap_off = m->d_off.p;
+            r.out_min = m->d_min.p; r.out_pos = m->d_pos.p; r.out_dir = m->d_dir.p;
+            r.out_mqual = m->d_mqual.p; r.inline_minq = 1;
+            MDBG_TRY(scratch_count.alloc(ctx, n)); MDBG_TRY(scratch_flags.alloc(ctx, n));
+            r.out_count = scratch_count.p; r.out_flags = scratch_flags.p;
+            MDBG_TRY(launch_scan(ctx, r, hpc, has_q, has_n, n_over));
+        }
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return set_error(ctx, MDBG_EHIP, "scan failed: %s", hipGetErrorString(e));
+        return MDBG_OK;
     }
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "scan failed: %s", hipGetErrorString(e)));
-    *out = m;
+};
+
+extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan_params *p, mdbg_minimizers **out) try {
+    if (!ctx || !reads || !p || !out) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: null argument");
+    if (p->quality_window != 0 && p->quality_window != 1) return set_error(ctx, MDBG_EINVAL, "mdbg_scan: quality_window must be 0 or 1");
+    if (p->minimizer_size < 2 || p->minimizer_size > 16)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_scan: minimizer_size %u outside [2,16]", p->minimizer_size);
+    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    MDBG_HIP_CHECK(ctx, reads_ready_on(ctx, reads));        // an upload still in flight (mdbg_reads_from_packed_async): ordered on the device
+    const uint32_t n = reads->n_reads;
+    ctx->scan_info[7] = 0;
+    std::unique_ptr<mdbg_minimizers> m(new mdbg_minimizers());     // released into *out on success
+    m->n_reads = n;
+    m->from_scan = true;
+    ScanJob j{ctx, reads, p, m.get(), n, p->hpc != 0, reads->has_qual && !p->ignore_qualities, reads->has_invalid};
+    MDBG_TRY(j.d_cap.alloc(ctx, n)); MDBG_TRY(j.d_count.alloc(ctx, n)); MDBG_TRY(j.d_cap_off.alloc(ctx, (size_t)n + 1));
+    MDBG_TRY(m->d_flags.alloc(ctx, n)); MDBG_TRY(m->d_len.alloc(ctx, n)); MDBG_TRY(m->d_off.alloc(ctx, (size_t)n + 1));
+    hipError_t e;
+    if (p->n_repetitive) {
+        std::vector<uint32_t> rep(p->repetitive, p->repetitive + p->n_repetitive);
+        std::sort(rep.begin(), rep.end());
+        MDBG_TRY(j.d_rep.alloc(ctx, rep.size()));
+        e = memcpy_sync(ctx, j.d_rep.p, rep.data(), rep.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "copy of repetitive set failed");
+    }
+    e = hipMemcpyAsync(m->d_len.p, reads->d_len.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "len copy failed: %s", hipGetErrorString(e));
+    MDBG_TRY(j.quality.start(ctx, reads, m.get(), j.has_q));
+
+    const ScanSwitches &sw = scan_switches();
+    const BlockRoute route = plan_block_route(n, reads->n_bases, reads->max_len, p->density, j.hpc, j.has_n, reads->d_masked.p != nullptr, j.has_n ? reads->n_masked : 0u,
+                                              sw.bump_allowed, STAGE_CAP);
+    SegPlan seg;
+    if (segments_wanted(route, ctx->scan_segments, reads->max_len, ctx->scan_segment_bases, STAGE_CAP, sw.approx_allowed, density_threshold(p->density), ctx->scan_cand_slack))
+        MDBG_TRY(seg_prepass(ctx, reads, route.route_masked ? reads->d_masked.p : nullptr, ctx->scan_segment_bases, p->minimizer_size, j.hpc, seg));
+    bool done = false;
+    if (route.block_path_but_length && (route.avg_fits_stage || seg.n_cut)) MDBG_TRY(j.scan_block_path(route, seg, &done));
+    if (!done) MDBG_TRY(j.scan_general_path());
+    *out = m.release();
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
 

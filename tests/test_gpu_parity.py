@@ -1580,6 +1580,44 @@ def test_scan_long_reads_among_short(ctx, orc, hpc, with_q):
         assert hc["minimizers"][int(hc["offsets"][i]): int(hc["offsets"][i + 1])].tolist() == w.tolist()
 
 
+@pytest.mark.parametrize("hpc", [True, False])
+@pytest.mark.parametrize("n_long,abandoned", [(70, True), (60, False)])
+def test_scan_too_many_long_reads_abandon_the_block_path(ctx, orc, hpc, n_long, abandoned):
+    """200 reads whose AVERAGE stays under the block kernel's stage (hpc, 70 long: 14 325 bases x 0.0224 + 24 = 345 < 384) but of
+    which many outgrow it (about 600 minimizers each).  The host places and re-runs at most n / 4 + 16 = 66 such reads: with 60
+    the block path finishes the batch; with 70 it gives its buffers back and the general path scans every read again.  Either
+    way every record, in order, is the oracle's.  (The average is far above the pre-filtered variant's length limit, 6786 bases, and
+    segmentation at its default is not wanted, so neither comes into it.)"""
+    rng = np.random.default_rng(91 + 2 * int(hpc) + n_long)
+    lens = [500] * 200
+    long_at = np.round(np.linspace(1, 198, n_long)).astype(int)
+    assert len(set(long_at.tolist())) == n_long
+    for at in long_at:
+        lens[int(at)] = 40_000 if hpc else 30_000
+    seqs = [bytes(synth.CODE2ASCII[rng.integers(0, 4, n)]) for n in lens]
+    reads = ctx.reads_from_ascii(seqs)
+    before = ctx.scan_info()
+    try:
+        ctx.timing(True); ctx.timing_reset()
+        h = ctx.scan(reads, K=15, density=0.02, hpc=hpc).to_host()
+        launches = ctx.timing_get("scan")[1]
+    finally:
+        ctx.timing(False)
+    after = ctx.scan_info()
+    counts = np.diff(h["offsets"].astype(np.int64))
+    print(f"n_long {n_long} hpc {hpc}: smallest long read {int(counts[long_at].min())} minimizers, block launches "
+          f"+{after['block_launches'] - before['block_launches']}, prefiltered +{after['prefiltered_launches'] - before['prefiltered_launches']}, "
+          f"'scan' launches {launches}")
+    assert counts[long_at].min() > 384                      # every long read is really beyond the stage
+    exp = b"".join(orc.read_selection(s, None, K=15, density=0.02, hpc=hpc)["record"] for s in seqs)
+    assert formats.build_read_data_init(h) == exp
+    assert after["prefiltered_launches"] == before["prefiltered_launches"]
+    # abandoned: the block kernel, then the general path's launch into padded slots (no read overflows those);
+    # placed: the block kernel, then the general kernel over the 60 reads
+    assert after["block_launches"] - before["block_launches"] == (2 if abandoned else 1)
+    assert launches == 2
+
+
 @pytest.mark.parametrize("hpc,with_q", [(True, False), (False, False), (True, True)])
 def test_scan_false_candidates_are_rerun(ctx, orc, hpc, with_q):
     """The block kernel records candidate positions by the upper half of the hash and confirms each with the full hash when it
