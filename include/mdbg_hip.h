@@ -399,6 +399,51 @@ int  mdbg_table_keys_to_host(mdbg_ctx *ctx, const mdbg_table *t, uint64_t *keys_
 int  mdbg_unitig_edge_index(mdbg_ctx *ctx, const mdbg_minimizers *unitigs, uint32_t k, mdbg_table **edges, uint64_t *checksum);
 void mdbg_table_free(mdbg_table *t);
 
+/* ---- k-min-mer spans in base space ---------------------------------------------------------------------------------------------------
+ * Replaces, for a whole batch, what the callers that scan raw reads or contigs again do with a scan -- ToBasespaceGfa::
+ * ExtractKminmerSequenceFunctor (toBasespace/ToBasespaceGfa.hpp:1177-1237), MappingContigToGraph (mapping/MappingContigToGraph.hpp:187-217,
+ * :308), GenerateGfa::LoadUnitigsFunctor: MDBG::getKminmers(l, k, minimizers, minimizersPos, kminmers, kminmersInfo, rlePositions, ...)
+ * (Commons.hpp:5401-5526) over the rlePositions of EncoderRLE::execute (Commons.hpp:4163-4203).  The reads and their scan go in; per
+ * window of k minimizers the identity and the ReadKminmer fields come out, on the device.
+ *
+ * rle[j] is the original coordinate of compressed position j: L' + 1 entries, rle[L'] = the read's length; without homopolymer
+ * compression rle[j] = j.  A minimizer selected at compressed position p spans [S, E) = [rle[p], rle[p + l]) of the original read.
+ * Window i of a read with n minimizers (0 <= i <= n - k; none when n < k), in read order:
+ *     reversed           the flag of KmerVec::normalize (a tie reverses; Commons.hpp:886-916)
+ *     hash_lo, hash_hi   the identity of the normalised window, as the records of mdbg_table_to_host carry it (mdbg_table_lookup takes it)
+ *     pos_start          S of its first minimizer          (ReadKminmer::_read_pos_start)
+ *     pos_end            E of its last minimizer           (_read_pos_end; _length is pos_end - pos_start)
+ *     seq_length_start   with f = S(second) - S(first) and b = E(last) - E(last but one): f, or b when reversed   (_seq_length_start)
+ *     seq_length_end     b, or f when reversed                                                                     (_seq_length_end)
+ * The four _position_of_* fields are always 0 in the reference and get no array.  One case differs from the reference on purpose:
+ * without compression, with no_end_trim and the read's last l-mer selected, the reference reads one element behind rlePositions; the
+ * library returns the natural p + l.
+ *
+ * mdbg_kminmer_spans   `mins` must carry positions and per-read lengths -- an mdbg_scan output, or an mdbg_minimizers_concat /
+ *                      mdbg_apply_density_threshold result that kept them -- and describe `reads`: as many
+ *                      reads, every read's recorded length the read's own, the positions of a read strictly increasing with
+ *                      p + minimizer_size <= L' (minimizer_size and hpc as they were given to the scan).  Anything else is MDBG_EINVAL with
+ *                      a message that names the first offending read; *out is untouched and no byte outside the inputs has been read:
+ *                      the checks run on the device before anything is looked up.  k >= 2 (a window's second minimizer is read); like
+ *                      mdbg_kminmer_index the call sets no upper limit: a k above every read's count gives zero windows.  A fresh scan
+ *                      output is brought into read order first, as by mdbg_minimizers_to_host.  Zero reads or zero windows give empty
+ *                      arrays.  The kernels are queued on the context's stream behind an asynchronous upload of `reads`; one status word
+ *                      is read back, and the call returns when the result is complete.  Timer names: "spans_map", "spans_windows".
+ * mdbg_spans_to_host   host copies, any pointer may be NULL: window_offsets has n_reads + 1 entries (the windows in front of each read),
+ *                      min_start / min_end (S and E of every minimizer) n_minimizers, the rest n_windows.
+ * mdbg_spans_device_ptrs  the same arrays on the device, for a caller that cuts the bases out there. */
+typedef struct mdbg_spans mdbg_spans;
+int  mdbg_kminmer_spans(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_minimizers *mins,
+                        uint32_t minimizer_size, int32_t hpc, uint32_t k, mdbg_spans **out);
+int  mdbg_spans_info(const mdbg_spans *s, uint32_t *n_reads, uint64_t *n_minimizers, uint64_t *n_windows, uint32_t *k);
+int  mdbg_spans_to_host(mdbg_ctx *ctx, const mdbg_spans *s, uint64_t *window_offsets,
+                        uint32_t *min_start, uint32_t *min_end,
+                        uint64_t *hash_lo, uint64_t *hash_hi, uint8_t *reversed,
+                        uint32_t *pos_start, uint32_t *pos_end, uint32_t *seq_length_start, uint32_t *seq_length_end);
+int  mdbg_spans_device_ptrs(const mdbg_spans *s, const uint64_t **d_window_offsets, const uint64_t **d_hash_lo, const uint64_t **d_hash_hi,
+                            const uint32_t **d_pos_start, const uint32_t **d_pos_end);
+void mdbg_spans_free(mdbg_spans *s);
+
 /* ---- files of records handed over as BYTES (round 6) ---------------------------------------------------------------------------
  * What `graph` reads at every k -- read_data_corrected.txt and unitig_data.txt (`u32 n; u8 circular; u32 m[n]` per record,
  * readSelection/ReadSelection.hpp:1420-1426, read back by KminmerParserParallel under one critical section, Commons.hpp:7394-7424)

@@ -103,6 +103,11 @@ SIGNATURES = {
     "mdbg_small_contigs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
     "mdbg_table_keys_to_host": (C.c_int, [_P, _P, _P]),
     "mdbg_table_free": (None, [_P]),
+    "mdbg_kminmer_spans": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(_P)]),
+    "mdbg_spans_info": (C.c_int, [_P, _u32p, _u64p, _u64p, _u32p]),
+    "mdbg_spans_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mdbg_spans_device_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "mdbg_spans_free": (None, [_P]),
     "mdbg_row_words": (C.c_uint32, [C.c_uint32]),
     "mdbg_shard_begin": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(_P), _u64p]),
     "mdbg_shard_reduce": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
@@ -373,6 +378,12 @@ class Context:
         h = C.c_void_p()
         self.check(lib().mdbg_kminmer_index(self.h, reads.h, unitigs.h if unitigs else None, k, prev.h, C.byref(h)))
         return Table(self, h)
+
+    def kminmer_spans(self, reads: "Reads", m: "Minimizers", K: int = 15, hpc: bool = True, k: int = 4) -> "Spans":
+        """Per window of k minimizers its identity and where it lies in the original read (mdbg_kminmer_spans); K and hpc as the scan's."""
+        h = C.c_void_p()
+        self.check(lib().mdbg_kminmer_spans(self.h, reads.h, m.h, K, int(hpc), k, C.byref(h)))
+        return Spans(self, h)
 
     def memcpy_device(self, dst_ptr: int, src_ptr: int, nbytes: int) -> None:
         self.check(lib().mdbg_memcpy_device(self.h, C.c_void_p(dst_ptr), C.c_void_p(src_ptr), nbytes))
@@ -804,6 +815,44 @@ class Minimizers:
     def free(self) -> None:
         if self.h:
             lib().mdbg_minimizers_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Spans:
+    """The k-min-mer spans of a batch (mdbg_kminmer_spans)."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self) -> dict:
+        n, t, w, k = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        lib().mdbg_spans_info(self.h, C.byref(n), C.byref(t), C.byref(w), C.byref(k))
+        return dict(n_reads=n.value, n_minimizers=t.value, n_windows=w.value, k=k.value)
+
+    def to_host(self) -> dict:
+        i = self.info()
+        n, t, w = i["n_reads"], i["n_minimizers"], i["n_windows"]
+        out = dict(window_offsets=np.zeros(n + 1, np.uint64), min_start=np.zeros(t, np.uint32), min_end=np.zeros(t, np.uint32),
+                   hash_lo=np.zeros(w, np.uint64), hash_hi=np.zeros(w, np.uint64), reversed=np.zeros(w, np.uint8),
+                   pos_start=np.zeros(w, np.uint32), pos_end=np.zeros(w, np.uint32),
+                   seq_length_start=np.zeros(w, np.uint32), seq_length_end=np.zeros(w, np.uint32))
+        self.ctx.check(lib().mdbg_spans_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = [C.c_void_p() for _ in range(5)]
+        lib().mdbg_spans_device_ptrs(self.h, *[C.byref(x) for x in p])
+        return dict(zip(("window_offsets", "hash_lo", "hash_hi", "pos_start", "pos_end"), [x.value or 0 for x in p]))
+
+    def free(self) -> None:
+        if self.h:
+            lib().mdbg_spans_free(self.h)
             self.h = None
 
     def __del__(self):
