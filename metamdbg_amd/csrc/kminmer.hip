@@ -1854,20 +1854,28 @@ __global__ __launch_bounds__(256) void owner_scatter_kernel(TableView t, uint64_
     }
 }
 
+// The owner's table keys a row by (fmix64(hash_lo), hash_hi), not by the identity itself.  A slot's home is the TOP bits of
+// lo ^ (hi >> 17) (table_home), of which the first 17 are hash_lo's alone; and this table is what takes the rows over when a bucket
+// of part_owner_reduce outgrew its LDS table -- which is when more keys share the top bits of hash_lo than a table has slots.  With
+// the identity as the key those very keys shared a handful of home slots here as well, and the hand-over ended in "hash table
+// overflow" at any capacity.  fmix64 is a bijection that keeps 0 at 0: distinct keys stay distinct, a zero word stays a zero word
+// (the side list), and the table belongs to this call alone (mdbg_shard_reduce drops it once the replies are written).
+__device__ __forceinline__ uint64_t owner_key_lo(uint64_t lo) { return fmix64(lo); }
+
 // owner: sum the received rows by key; rep = index of the received row that created the key -- its sender is the
 // one rank that will list the key
 __global__ __launch_bounds__(256) void rows_add_kernel(const uint64_t *rows, uint64_t n, TableView t) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t *r = rows + i * SHARD_ROW_WORDS;
-    table_upsert_count(t, r[0], r[1], (uint32_t)r[2], (uint32_t)i);
+    table_upsert_count(t, owner_key_lo(r[0]), r[1], (uint32_t)r[2], (uint32_t)i);
 }
 
 __global__ __launch_bounds__(256) void rows_reply_kernel(const uint64_t *rows, uint64_t n, TableView t, uint64_t *reply) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t *r = rows + i * SHARD_ROW_WORDS;
-    const uint32_t slot = table_lookup_slot(t, r[0], r[1]);
+    const uint32_t slot = table_lookup_slot(t, owner_key_lo(r[0]), r[1]);
     uint64_t out = 0;
     if (slot != SLOT_NONE) out = (uint64_t)table_slot_val(t, slot) | (table_slot_rep(t, slot) == (uint32_t)i ? SHARD_EMIT_BIT : 0ull);
     reply[i] = out;
