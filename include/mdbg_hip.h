@@ -444,6 +444,54 @@ int  mdbg_spans_device_ptrs(const mdbg_spans *s, const uint64_t **d_window_offse
                             const uint32_t **d_pos_start, const uint32_t **d_pos_end);
 void mdbg_spans_free(mdbg_spans *s);
 
+/* ---- k-min-mer sequences cut out of the reads ------------------------------------------------------------------------------------------
+ * Replaces, for a whole batch, what the callers of the spans do with them: ToBasespaceGfa::extractKminmerSequence (toBasespace/
+ * ToBasespaceGfa.hpp:1050-1103) -- a memcpy of the window, Utils::revcomp (Commons.hpp:3007-3014) of a reversed window, a substr for the
+ * left or right overhang -- as the loop body of ExtractKminmerSequenceFunctor calls it (:1177-1237), and the DnaBitset2 the result is kept
+ * as (utils/DnaBitset.hpp:118-242); with whole reads, LoadUnitigsFunctor's DnaBitset2(read._seq) (graph/GenerateGfa.hpp:418).  The reads
+ * stay in HBM at 2 bits a base; nothing is exported as characters and cut on the host.
+ *
+ * A request names a window by its flat index (window_offsets[read] + i of mdbg_spans_to_host) and a part (LoadType Entire / Left / Right).
+ * With the window's fields ps = pos_start, pe = pos_end, ls = seq_length_start, le = seq_length_end (the spans already exchange ls and le
+ * for a reversed window) the range of the read that is taken is
+ *     part               forward             reversed (the output is the reverse complement of the range)
+ *     MDBG_SEQ_ENTIRE    [ps, pe)            [ps, pe)
+ *     MDBG_SEQ_LEFT      [ps, ps + ls)       [pe - ls, pe)
+ *     MDBG_SEQ_RIGHT     [pe - le, pe)       [ps, ps + le)
+ * which is the first ls / last le characters of the oriented string, as the reference's substr takes them.  mdbg_reads_extract_ranges
+ * takes the ranges from the caller instead (reversed: 0 = as it stands, anything else = reverse complement); the whole read [0, length)
+ * forward is LoadUnitigsFunctor's case.  Requests may repeat, come in any order and number zero; the output keeps their order.
+ *
+ * Forms.  MDBG_SEQ_BITSET is DnaBitset2::_m_data: base i of a sequence in byte i / 4 at bits 6 - 2 (i % 4), codes A 0, C 1, G 2, T 3,
+ * ceil(length / 4) bytes meaningful, unused bits 0.  MDBG_SEQ_ASCII is the string before it is packed: upper-case ACGT, and N where the
+ * read's invalid mask is set.  In both forms sequence i starts at byte_offsets[i], a multiple of 8, and everything between its last
+ * meaningful byte and byte_offsets[i + 1] is 0.  A position whose character had bit 3 set (N, n, K, M, Y ...) is code 0 in the bitset
+ * in both orientations: what DnaBitset2 stores for any character outside ACGT.  One case differs from the reference on purpose: a
+ * lower-case acgt, or an IUPAC letter without bit 3 (R, S, W), comes out as the base its 2-bit code names, where DnaBitset2 stores A --
+ * the packed reads no longer know the case.
+ *
+ * Refusals, MDBG_EINVAL with a message that names the first offending request, *out untouched: a part or form out of range, reserved != 0,
+ * window >= n_windows, a read index >= n_reads, spans that do not describe `reads` (another number of reads, or another length of a read
+ * a request touches), a range whose start + length lies behind its read's end, ls or le larger than pe - ps.  The checks run on the
+ * device before any base is read; one status word is read back, and the call returns when the result is complete.  2^32 requests or more
+ * are MDBG_ERANGE.  Timer names: "extract_plan", "extract_copy".
+ * mdbg_sequences_info         n sequences, their bases in all, the bytes of the buffer (padding included), the form.
+ * mdbg_sequences_to_host      host copies, any pointer may be NULL: byte_offsets n + 1 entries, lengths (bases) n, bytes n_bytes.
+ * mdbg_sequences_device_ptrs  the same arrays on the device. */
+typedef struct { uint64_t window; uint32_t part; uint32_t reserved; } mdbg_seq_request;
+typedef struct { uint32_t read, start, length, reversed; } mdbg_seq_range;
+enum { MDBG_SEQ_ENTIRE = 0, MDBG_SEQ_LEFT = 1, MDBG_SEQ_RIGHT = 2 };
+enum { MDBG_SEQ_BITSET = 0, MDBG_SEQ_ASCII = 1 };
+typedef struct mdbg_sequences mdbg_sequences;
+int  mdbg_spans_extract(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_spans *spans, const mdbg_seq_request *requests, uint64_t n,
+                        int form, mdbg_sequences **out);
+int  mdbg_reads_extract_ranges(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_seq_range *ranges, uint64_t n, int form,
+                               mdbg_sequences **out);
+int  mdbg_sequences_info(const mdbg_sequences *s, uint64_t *n, uint64_t *n_bases, uint64_t *n_bytes, int *form);
+int  mdbg_sequences_to_host(mdbg_ctx *ctx, const mdbg_sequences *s, uint64_t *byte_offsets, uint32_t *lengths, uint8_t *bytes);
+int  mdbg_sequences_device_ptrs(const mdbg_sequences *s, const uint64_t **d_byte_offsets, const uint32_t **d_lengths, const uint8_t **d_bytes);
+void mdbg_sequences_free(mdbg_sequences *s);
+
 /* ---- files of records handed over as BYTES (round 6) ---------------------------------------------------------------------------
  * What `graph` reads at every k -- read_data_corrected.txt and unitig_data.txt (`u32 n; u8 circular; u32 m[n]` per record,
  * readSelection/ReadSelection.hpp:1420-1426, read back by KminmerParserParallel under one critical section, Commons.hpp:7394-7424)

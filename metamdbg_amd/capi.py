@@ -16,6 +16,10 @@ LIB_PATH = os.environ.get("MDBG_LIB") or os.path.join(_HERE, "libmdbg_hip.so")  
 MDBG_READ_LOW_COMPLEXITY = 1
 MDBG_READ_LOW_QUALITY = 2
 RECORDS_PLAIN, RECORDS_INIT = 0, 1      # MDBG_RECORDS_*: the forms of mdbg_minimizers_to_record_bytes
+SEQ_ENTIRE, SEQ_LEFT, SEQ_RIGHT = 0, 1, 2   # MDBG_SEQ_*: the parts of a window mdbg_spans_extract cuts out ...
+SEQ_BITSET, SEQ_ASCII = 0, 1                # ... and the forms it writes them in
+SEQ_REQUEST = np.dtype([("window", "<u8"), ("part", "<u4"), ("reserved", "<u4")])                  # mdbg_seq_request
+SEQ_RANGE = np.dtype([("read", "<u4"), ("start", "<u4"), ("length", "<u4"), ("reversed", "<u4")])  # mdbg_seq_range
 
 
 class MdbgError(RuntimeError):
@@ -108,6 +112,12 @@ SIGNATURES = {
     "mdbg_spans_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mdbg_spans_device_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "mdbg_spans_free": (None, [_P]),
+    "mdbg_spans_extract": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P)]),
+    "mdbg_reads_extract_ranges": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P)]),
+    "mdbg_sequences_info": (C.c_int, [_P, _u64p, _u64p, _u64p, C.POINTER(C.c_int)]),
+    "mdbg_sequences_to_host": (C.c_int, [_P, _P, _P, _P, _P]),
+    "mdbg_sequences_device_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "mdbg_sequences_free": (None, [_P]),
     "mdbg_row_words": (C.c_uint32, [C.c_uint32]),
     "mdbg_shard_begin": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(_P), _u64p]),
     "mdbg_shard_reduce": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
@@ -384,6 +394,28 @@ class Context:
         h = C.c_void_p()
         self.check(lib().mdbg_kminmer_spans(self.h, reads.h, m.h, K, int(hpc), k, C.byref(h)))
         return Spans(self, h)
+
+    def spans_extract(self, reads: "Reads", spans: "Spans", windows, parts, form: int = SEQ_BITSET) -> "Sequences":
+        """The oriented sequences of (window, part) requests, packed as DnaBitset2 keeps them or as characters (mdbg_spans_extract):
+        windows are flat window indices, parts SEQ_ENTIRE / SEQ_LEFT / SEQ_RIGHT (one value or one per request)."""
+        req = np.zeros(len(windows), SEQ_REQUEST)
+        req["window"], req["part"] = windows, parts
+        return self.spans_extract_requests(reads, spans, req, form)
+
+    def spans_extract_requests(self, reads: "Reads", spans: "Spans", requests: np.ndarray, form: int = SEQ_BITSET) -> "Sequences":
+        """... from an array of SEQ_REQUEST records as the C ABI takes them."""
+        req = np.ascontiguousarray(requests, SEQ_REQUEST)
+        h = _P()
+        self.check(lib().mdbg_spans_extract(self.h, reads.h, spans.h, _ptr(req), len(req), form, C.byref(h)))
+        return Sequences(self, h)
+
+    def reads_extract_ranges(self, reads: "Reads", read, start, length, reversed, form: int = SEQ_BITSET) -> "Sequences":
+        """The sequences of ranges [start, start + length) of reads, reverse-complemented where `reversed` (mdbg_reads_extract_ranges)."""
+        rg = np.zeros(len(read), SEQ_RANGE)
+        rg["read"], rg["start"], rg["length"], rg["reversed"] = read, start, length, reversed
+        h = _P()
+        self.check(lib().mdbg_reads_extract_ranges(self.h, reads.h, _ptr(rg), len(rg), form, C.byref(h)))
+        return Sequences(self, h)
 
     def memcpy_device(self, dst_ptr: int, src_ptr: int, nbytes: int) -> None:
         self.check(lib().mdbg_memcpy_device(self.h, C.c_void_p(dst_ptr), C.c_void_p(src_ptr), nbytes))
@@ -858,6 +890,42 @@ class Spans:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+class Sequences:
+    """Sequences cut out of the reads (mdbg_spans_extract / mdbg_reads_extract_ranges)."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+
+    def info(self) -> dict:
+        n, b, y, f = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+        lib().mdbg_sequences_info(self.h, C.byref(n), C.byref(b), C.byref(y), C.byref(f))
+        return dict(n=n.value, n_bases=b.value, n_bytes=y.value, form=f.value)
+
+    def to_host(self) -> dict:
+        i = self.info()
+        out = dict(byte_offsets=np.zeros(i["n"] + 1, np.uint64), lengths=np.zeros(i["n"], np.uint32), bytes=np.zeros(i["n_bytes"], np.uint8))
+        self.ctx.check(lib().mdbg_sequences_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = [C.c_void_p() for _ in range(3)]
+        lib().mdbg_sequences_device_ptrs(self.h, *[C.byref(x) for x in p])
+        return dict(zip(("byte_offsets", "lengths", "bytes"), [x.value or 0 for x in p]))
+
+    def close(self) -> None:
+        if self.h:
+            lib().mdbg_sequences_free(self.h)
+            self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

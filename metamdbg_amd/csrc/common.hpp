@@ -216,6 +216,7 @@ const StepKernel *partition_step_kernels(uint32_t *n);
 const StepKernel *minimizers_step_kernels(uint32_t *n);
 const StepKernel *prims_step_kernels(uint32_t *n);
 const StepKernel *scan_step_kernels(uint32_t *n);
+const StepKernel *extract_step_kernels(uint32_t *n);
 
 int set_error(mdbg_ctx *ctx, int code, const char *fmt, ...);
 extern thread_local std::string g_last_error;  // for failures before a context exists (per calling thread)
@@ -360,6 +361,42 @@ __device__ __forceinline__ unsigned lane_below(unsigned v, unsigned first) {
 
 __device__ __forceinline__ unsigned long long lanemask_lt() {
     return (1ull << lane_id()) - 1ull;
+}
+
+// the sequence that owns flat item i of a CSR: the last r with off[r] <= i (off[0] <= i < off[n])
+__device__ __forceinline__ uint32_t csr_owner(const uint64_t *off, uint32_t n, uint64_t i) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// ... when the owner `from` of an item at or in front of i is known (off[from] <= i): a few steps forward, else the search over the rest
+__device__ __forceinline__ uint32_t csr_owner_from(const uint64_t *off, uint32_t n, uint64_t i, uint32_t from) {
+    uint32_t lo = from;
+    for (int step = 0; step < 4; step++) {
+        if (lo + 1u >= n || off[lo + 1u] > i) return lo;
+        lo++;
+    }
+    uint32_t hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The items of a CSR are dealt to the waves in CONTIGUOUS spans, `unit` items a trip: a wave searches the owner of its first item once
+// (about twenty dependent loads at a million sequences) and walks from there -- the owner of the next trip's items is a few sequences
+// on.  Searched anew at every trip of a grid-stride loop, that chain of loads was most of the map's time (profiles/kminmer_spans.txt).
+struct WaveSpan { uint64_t begin, end; };
+__device__ __forceinline__ WaveSpan wave_span(uint64_t n_items, uint32_t unit) {
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    const uint64_t per = ((n_items + n_waves - 1u) / n_waves + unit - 1u) / unit * unit;
+    const uint64_t begin = wave * per < n_items ? wave * per : n_items;
+    return WaveSpan{begin, n_items - begin < per ? n_items : begin + per};
 }
 #endif
 

@@ -125,3 +125,15 @@ struct mdbg_table {
     // pass that built the table, or made on first use from `lookup` (if present: it may carry a unitig overlay) or from the rows
     std::unique_ptr<mdbg::BucketTable> image;
 };
+
+// The k-min-mer spans of a batch (spans.hip); mdbg_spans_extract (extract.hip) reads the windows' fields.
+struct mdbg_spans {
+    uint32_t n_reads = 0, k = 0;
+    uint64_t n_min = 0, n_windows = 0;
+    mdbg::DevBuf<uint64_t> d_woff;              // n_reads + 1
+    mdbg::DevBuf<uint32_t> d_len;               // n_reads: the lengths of the reads the spans were made of (mdbg_spans_extract checks them)
+    mdbg::DevBuf<uint32_t> d_s, d_e;            // n_min: [S, E) of every minimizer in original coordinates
+    mdbg::DevBuf<uint64_t> d_lo, d_hi;          // n_windows
+    mdbg::DevBuf<uint8_t> d_rev;
+    mdbg::DevBuf<uint32_t> d_ps, d_pe, d_ls, d_le;
+};

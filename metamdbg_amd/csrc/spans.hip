@@ -21,57 +21,11 @@
 
 #include <memory>
 
-struct mdbg_spans {
-    uint32_t n_reads = 0, k = 0;
-    uint64_t n_min = 0, n_windows = 0;
-    mdbg::DevBuf<uint64_t> d_woff;              // n_reads + 1
-    mdbg::DevBuf<uint32_t> d_s, d_e;            // n_min: [S, E) of every minimizer in original coordinates
-    mdbg::DevBuf<uint64_t> d_lo, d_hi;          // n_windows
-    mdbg::DevBuf<uint8_t> d_rev;
-    mdbg::DevBuf<uint32_t> d_ps, d_pe, d_ls, d_le;
-};
-
 namespace mdbg {
 
 // what the checks found: (read << 8) | reason, the smallest wins; SPANS_FINE = nothing
 constexpr unsigned long long SPANS_FINE = ~0ull;
 constexpr uint32_t SPANS_BAD_LENGTH = 1, SPANS_BAD_ORDER = 2, SPANS_BAD_END = 3;
-
-// the sequence that owns flat item i of a CSR: the last r with off[r] <= i (off[0] <= i < off[n])
-__device__ __forceinline__ uint32_t csr_owner(const uint64_t *off, uint32_t n, uint64_t i) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// ... when the owner `from` of an item at or in front of i is known (off[from] <= i): a few steps forward, else the search over the rest
-__device__ __forceinline__ uint32_t csr_owner_from(const uint64_t *off, uint32_t n, uint64_t i, uint32_t from) {
-    uint32_t lo = from;
-    for (int step = 0; step < 4; step++) {
-        if (lo + 1u >= n || off[lo + 1u] > i) return lo;
-        lo++;
-    }
-    uint32_t hi = n;
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// The items of a CSR are dealt to the waves in CONTIGUOUS spans, `unit` items a trip: a wave searches the owner of its first item once
-// (about twenty dependent loads at a million sequences) and walks from there -- the owner of the next trip's items is a few sequences
-// on.  Searched anew at every trip of a grid-stride loop, that chain of loads was most of the map's time (profiles/kminmer_spans.txt).
-struct WaveSpan { uint64_t begin, end; };
-__device__ __forceinline__ WaveSpan wave_span(uint64_t n_items, uint32_t unit) {
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const uint64_t per = ((n_items + n_waves - 1u) / n_waves + unit - 1u) / unit * unit;
-    const uint64_t begin = wave * per < n_items ? wave * per : n_items;
-    return WaveSpan{begin, n_items - begin < per ? n_items : begin + per};
-}
 
 // per read: the tiles of its map, its windows, and the first check -- the scan recorded the length the reads have
 __global__ __launch_bounds__(256) void spans_plan_kernel(const uint32_t *read_len, const uint32_t *scan_len, const uint64_t *off, uint32_t n_reads, uint32_t k,
@@ -224,6 +178,8 @@ extern "C" int mdbg_kminmer_spans(mdbg_ctx *ctx, const mdbg_reads *reads, const 
     std::unique_ptr<mdbg_spans> sp(new mdbg_spans());
     sp->n_reads = n; sp->k = k; sp->n_min = n_min;
     MDBG_TRY(sp->d_woff.alloc(ctx, (size_t)n + 1));
+    MDBG_TRY(sp->d_len.alloc(ctx, n));
+    if (n) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(sp->d_len.p, reads->d_len.p, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
 
     // ---- the map's counts and the checks --------------------------------------------------------------------------------------
     const uint64_t tiles_bound = comp ? reads->n_words / SPANS_TILE_WORDS + n + 1u : 1u;     // sum of ceil(words / 64) over the reads
