@@ -354,9 +354,14 @@ int  mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]);
  * 16-wave scan workgroup leaves of a SIMD, which the eight-wave forms are not.  Beside that scan the four-wave forms measured SLOWER and
  * the scan no faster, so they are opt-in: for that comparison and for tests.  Results never depend on it.
  * mdbg_first_pass_form tells which form the context's last split kernels took: form[0] = threads per block, [1] = records per tile,
- * [2] and [3] = 0. */
+ * [2] and [3] = 0.
+ * mdbg_first_pass_slot_fall_backs: the instances of the last partitioned first pass whose LDS slot the bucket count looked up a second
+ * time.  Counting a bucket walks its records twice (count, then a byte per instance of a rare key); the form without a slot list keeps
+ * the slots of a bucket's first 8192 records in registers between the walks, the form with one those of its first 8000 (4096 beside 2048
+ * slots) in LDS, and only the records behind them are found again by their key.  0 for mdbg_shard_begin (no second walk). */
 int  mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]);
 int  mdbg_first_pass_form(const mdbg_ctx *ctx, uint64_t form[4]);
+int  mdbg_first_pass_slot_fall_backs(const mdbg_ctx *ctx, uint64_t *n);
 /* The kernels of the headline step (scan, purge, first pass) by name, and what the runtime knows of each in the loaded code object
  * (hipFuncGetAttributes): what a kernel of one context needs of a compute unit -- registers, wave slots, LDS -- against what another
  * context's scan workgroup leaves of it.  mdbg_step_kernel_name(i) = the i-th name, NULL past the last.  attr[0] = vector registers per lane, [1] = bytes

@@ -95,6 +95,7 @@ SIGNATURES = {
     "mdbg_scan_info": (C.c_int, [_P, _u64p]),
     "mdbg_scan_confirm_info": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_form": (C.c_int, [_P, _u64p]),
+    "mdbg_first_pass_slot_fall_backs": (C.c_int, [_P, _u64p]),
     "mdbg_step_kernel_name": (C.c_char_p, [C.c_uint32]),
     "mdbg_kernel_attributes": (C.c_int, [_P, C.c_char_p, _u64p]),
     "mdbg_stream_spin": (C.c_int, [_P, C.c_uint32]),
@@ -235,6 +236,13 @@ class Context:
         a = (C.c_uint64 * 4)()
         self.check(lib().mdbg_first_pass_form(self.h, a))
         return {"split_threads": int(a[0]), "split_tile": int(a[1])}
+
+    def first_pass_slot_fall_backs(self) -> int:
+        """Instances of the last partitioned first pass whose LDS slot the bucket count looked up a second time
+        (mdbg_first_pass_slot_fall_backs)."""
+        n = C.c_uint64()
+        self.check(lib().mdbg_first_pass_slot_fall_backs(self.h, C.byref(n)))
+        return int(n.value)
 
     @staticmethod
     def step_kernel_names() -> list[str]:

@@ -185,6 +185,7 @@ struct mdbg_ctx {
     uint32_t part_threads = 0;              // threads per block of the split kernels: 0 or 512 = eight waves; 256 = four waves, tiles of 1024 records (fits beside a
                                             // 16-wave scan workgroup by registers, measured slower there: DESIGN.md 4.4; for that comparison and for tests)
     uint64_t part_form[4] = {0};            // mdbg_first_pass_form: [0] threads per block, [1] records per tile of the split kernels last launched
+    uint64_t part_fell_back = 0;            // last partitioned first pass: instances whose LDS slot bucket_count looked up a second time (mdbg_first_pass_slot_fall_backs)
     uint32_t part_slot_list = 1;            // 0: bucket_count keeps no slot list (24 KB of LDS per 1024-slot bucket instead of 40)
     uint32_t scan_lds_pad = 0;              // bytes of unused dynamic LDS per block of the block-structured scan: caps its blocks per CU and so
                                             // leaves LDS, registers and wave slots to other contexts' kernels (mdbg_set_option)

@@ -1620,6 +1620,12 @@ extern "C" int mdbg_first_pass_form(const mdbg_ctx *ctx, uint64_t form[4]) {
     return MDBG_OK;
 }
 
+extern "C" int mdbg_first_pass_slot_fall_backs(const mdbg_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return MDBG_EINVAL;
+    *n = ctx->part_fell_back;
+    return MDBG_OK;
+}
+
 extern "C" int mdbg_table_checksum(mdbg_ctx *ctx, const mdbg_table *t, uint64_t sums[4]) try {
     if (!ctx || !t || !sums) return set_error(ctx, MDBG_EINVAL, "mdbg_table_checksum: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));

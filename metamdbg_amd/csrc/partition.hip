@@ -28,6 +28,7 @@
 // times the buckets; if that is not enough the caller's one-table path takes over.
 #include "common.hpp"
 #include "kminmer_dev.hpp"
+#include "partition_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -55,7 +56,7 @@ constexpr uint32_t PART_E_SMALL = 4;
 constexpr uint32_t PART_TILE_SMALL = PART_NT_SMALL * PART_E_SMALL;
 static_assert(PART_NT_SMALL >= PART_MAXW && PART_NT >= PART_MAXW, "the scatter scans a tile's histogram with one thread per way");
 // bucket_count remembers the LDS slot of a bucket's first records between its two passes: 8000 of them beside 1024 slots (not 8192:
-// four such buckets then fit a CU's 160 KB), 4096 beside 2048 (the 64 KB of static LDS), none when the kernel is to fit beside a scan
+// four such buckets then fit a CU's 160 KB), 4096 beside 2048 (the 64 KB of static LDS), in registers instead (16 a thread, BC_KEEP_TRIPS) when the kernel is to fit beside a scan
 constexpr uint32_t PART_MAX_K = 32;                    // window validity is one 64-bit extract of the start bits
 
 struct RecView { unsigned long long *lo, *hi; uint32_t *rep; };
@@ -131,15 +132,12 @@ __device__ __forceinline__ uint64_t window_mix(const uint32_t *m, uint32_t k) {
     return acc ^ (acc >> 32);
 }
 
+// a block's work item (partition_plan.hpp): its segment, its share of it, the share's records [b, e)
 __device__ __forceinline__ void split_range(const SplitArgs &a, uint32_t &seg, uint32_t &j, uint64_t &b, uint64_t &e) {
-    seg = blockIdx.x / a.blocks_per_seg; j = blockIdx.x % a.blocks_per_seg;
+    split_item(blockIdx.x, a.blocks_per_seg, seg, j);
     uint64_t s0 = 0, s1 = a.n_min;
     if (a.seg_pos) { s0 = a.seg_pos[(uint64_t)seg * a.seg_stride]; s1 = a.seg_pos[(uint64_t)(seg + 1) * a.seg_stride]; }
-    const uint64_t len = s1 - s0;
-    uint64_t per = (len + a.blocks_per_seg - 1) / a.blocks_per_seg;
-    per = (per + a.tile - 1) / a.tile * a.tile;
-    b = s0 + (uint64_t)j * per; if (b > s1) b = s1;
-    e = b + per; if (e > s1) e = s1;
+    split_share(s0, s1, j, a.blocks_per_seg, a.tile, b, e);
 }
 
 // hist[(seg * ways + digit) * blocks_per_seg + j]: scanned in this order the table is every (block, digit)'s first output place,
@@ -344,13 +342,18 @@ __device__ __forceinline__ uint32_t lds_find(const LdsTable<C> &t, uint64_t lo, 
 // and only the instances that differ are stored: random one-byte stores are what this costs).
 constexpr uint32_t BC_NT = 512;                        // threads per bucket: 4 blocks of 40 KB fill a CU's 32 wave slots
 constexpr uint32_t BC_U = 4;                           // records of a thread in flight
+// The form without a slot list keeps the slots of a thread's first records in registers between the two walks, two to a register: BC_KEEP_TRIPS
+// trips of BC_U records, 16 a thread and 8192 a bucket -- the bench's buckets hold about 5 250 (344 M instances in 2^16 buckets).  The second walk
+// then loads only `rep` of those records; the records behind them find their slot again by their key (lds_find), and are counted (*fell_back).
+constexpr uint32_t BC_KEEP_TRIPS = 4;
 
 template <uint32_t C, uint32_t LIST>
 __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const uint64_t *pos, uint32_t stride, uint32_t min_abundance, uint32_t clip,
                                                            int keep_all, RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept,
-                                                           uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow) {
+                                                           uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow, uint32_t *fell_back) {
     __shared__ LdsTable<C> t;
     constexpr uint32_t PART_SLOTLIST = LIST;           // 0: none (24 bytes of LDS per slot and nothing else: fits beside a scan)
+    constexpr uint32_t KEEP_TRIPS = LIST ? 0u : BC_KEEP_TRIPS;
     __shared__ uint16_t slot_of[LIST ? LIST : 1];
     __shared__ uint32_t kept, occupied;
     const uint32_t tid = threadIdx.x;
@@ -366,9 +369,14 @@ __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const u
     __syncthreads();
     if (give_up) return;
     bool failed = false, zero_key = false;
-    for (uint64_t i0 = 0; i0 < n; i0 += BC_NT * BC_U) {
+    // 16 bits each.  The trip count is the same for every lane, and a slot is chosen by comparing it with constants: registers, no scratch
+    uint32_t kept_slot[KEEP_TRIPS ? KEEP_TRIPS * BC_U / 2 : 1];
+#pragma unroll
+    for (uint32_t w = 0; w < KEEP_TRIPS * BC_U / 2; w++) kept_slot[w] = LDS_NONE | (LDS_NONE << 16);
+    uint32_t trip = 0;
+    for (uint64_t i0 = 0; i0 < n; i0 += BC_NT * BC_U, trip++) {
         if (__hip_atomic_load(&give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-        uint64_t lo[BC_U], hi[BC_U]; uint32_t rep[BC_U];
+        uint64_t lo[BC_U], hi[BC_U]; uint32_t rep[BC_U], slots[BC_U];
 #pragma unroll
         for (uint32_t q = 0; q < BC_U; q++) {
             const uint64_t i = i0 + (uint64_t)q * BC_NT + tid;
@@ -377,12 +385,20 @@ __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const u
 #pragma unroll
         for (uint32_t q = 0; q < BC_U; q++) {
             const uint64_t i = i0 + (uint64_t)q * BC_NT + tid;
+            slots[q] = LDS_NONE;
             if (i >= n) continue;
             uint32_t s = LDS_NONE;
             const bool zero_word = lo[q] == 0ull || hi[q] == 0ull;       // 0 marks an empty slot: such a key (2^-63) is not for this pass at all
             if (!zero_word) s = lds_upsert<C>(t, lo[q], hi[q], rep[q]);
             if (s == LDS_NONE) { failed = true; zero_key = zero_key || zero_word; __hip_atomic_store(&give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-            if (i < PART_SLOTLIST) slot_of[i] = (uint16_t)s;
+            if (LIST && i < PART_SLOTLIST) slot_of[i] = (uint16_t)s;
+            slots[q] = s;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < KEEP_TRIPS; k++) {
+            if (trip != k) continue;
+#pragma unroll
+            for (uint32_t q = 0; q < BC_U; q += 2) kept_slot[(k * BC_U + q) / 2] = slots[q] | (slots[q + 1] << 16);
         }
     }
     // void pass.  PART_OVERFLOW_TABLE: a bucket outgrew its table -- the host repeats the pass with more buckets; PART_OVERFLOW_ZERO_KEY: no
@@ -404,15 +420,37 @@ __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const u
     }
     if (my_occ) atomicAdd(&occupied, my_occ);
     if (cnt8) {
-        for (uint64_t i0 = 0; i0 < n; i0 += BC_NT * BC_U) {
+        // the records whose slot was kept: only `rep` is loaded; the others by the slot list or by their key
+        uint32_t n_fell_back = 0;
+        trip = 0;
+        for (uint64_t i0 = 0; i0 < n; i0 += BC_NT * BC_U, trip++) {
             uint32_t rep[BC_U], sl[BC_U];
+            if (trip < KEEP_TRIPS) {
+                uint32_t pair[BC_U / 2];
 #pragma unroll
-            for (uint32_t q = 0; q < BC_U; q++) {
-                const uint64_t i = i0 + (uint64_t)q * BC_NT + tid;
-                sl[q] = LDS_NONE;
-                if (i < n) {
-                    rep[q] = in.rep[s0 + i];
-                    sl[q] = i < PART_SLOTLIST ? (uint32_t)slot_of[i] : lds_find<C>(t, in.lo[s0 + i], in.hi[s0 + i]);
+                for (uint32_t w = 0; w < BC_U / 2; w++) pair[w] = LDS_NONE | (LDS_NONE << 16);
+#pragma unroll
+                for (uint32_t k = 0; k < KEEP_TRIPS; k++) {
+                    if (trip != k) continue;
+#pragma unroll
+                    for (uint32_t w = 0; w < BC_U / 2; w++) pair[w] = kept_slot[k * BC_U / 2 + w];
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < BC_U; q++) {
+                    const uint64_t i = i0 + (uint64_t)q * BC_NT + tid;
+                    sl[q] = (pair[q / 2] >> (16u * (q & 1u))) & 0xFFFFu;           // (LDS_NONE: no such record, too)
+                    if (i < n) rep[q] = in.rep[s0 + i];
+                }
+            } else {
+#pragma unroll
+                for (uint32_t q = 0; q < BC_U; q++) {
+                    const uint64_t i = i0 + (uint64_t)q * BC_NT + tid;
+                    sl[q] = LDS_NONE;
+                    if (i < n) {
+                        rep[q] = in.rep[s0 + i];
+                        if (i < PART_SLOTLIST) sl[q] = (uint32_t)slot_of[i];
+                        else { sl[q] = lds_find<C>(t, in.lo[s0 + i], in.hi[s0 + i]); n_fell_back++; }
+                    }
                 }
             }
 #pragma unroll
@@ -422,6 +460,8 @@ __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const u
                 if (v != cnt8_default) cnt8[rep[q]] = (uint8_t)v;     // the array was filled with the value most instances have
             }
         }
+        // (a pass has fewer than 2^32 instances.  Not a 64-bit sum: the wave-wide reduction the compiler makes of one costs 27 registers)
+        if (n_fell_back) atomicAdd(fell_back, n_fell_back);
     }
     __syncthreads();
     if (tid == 0) { n_keys[blockIdx.x] = occupied; n_kept[blockIdx.x] = kept; }
@@ -706,9 +746,10 @@ struct LevelPlan { uint32_t bits, shift, ways, blocks_per_seg; uint64_t n_seg; }
 
 template <uint32_t C, uint32_t LIST>
 static void launch_bucket_count(mdbg_ctx *ctx, uint64_t n_buckets, RecView in, const uint64_t *pos, uint32_t stride, uint32_t min_abundance, uint32_t clip, int keep_all,
-                                RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept, uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow) {
+                                RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept, uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow,
+                                uint32_t *fell_back) {
     hipLaunchKernelGGL((bucket_count_kernel<C, LIST>), dim3((unsigned)n_buckets), dim3(BC_NT), 0, ctx->stream, in, pos, stride, min_abundance, clip, keep_all, keys, kcnt,
-                       n_keys, n_kept, cnt8, cnt8_default, overflow);
+                       n_keys, n_kept, cnt8, cnt8_default, overflow, fell_back);
 }
 
 // the rows of one group of keys, kept aside while the next group reuses the record buffers (several groups only)
@@ -751,6 +792,8 @@ struct PartRun {
     LevelPlan lv[3];
     // buffers
     DevBuf<uint32_t> start_bits, kcnt, hist, n_keys, n_kept, overflow, hll_merged;
+    DevBuf<uint32_t> fell_back;                        // instances whose slot bucket_count looked up a second time (lds_find)
+    uint32_t fell_back_host = 0;
     DevBuf<uint64_t> place[3], key_pos, row_of;
     DevBuf<uint8_t> hll_blocks;
     RecBufs buf[2];
@@ -810,12 +853,14 @@ struct PartRun {
         form = split_form(ctx);
         tile = form.tile;
         MDBG_TRY(overflow.alloc(ctx, 1));
+        MDBG_TRY(fell_back.alloc(ctx, 1));
         plan();
         return MDBG_OK;
     }
     int begin_attempt() {
         plan();
         MDBG_HIP_CHECK(ctx, hipMemsetAsync(overflow.p, 0, 4, ctx->stream));
+        MDBG_HIP_CHECK(ctx, hipMemsetAsync(fell_back.p, 0, 4, ctx->stream));
         return MDBG_OK;
     }
 
@@ -828,10 +873,9 @@ struct PartRun {
         a.group_bits = group_bits; a.group = g;
         a.tile = tile;
         // level 1: histogram, scan, the group's instance count, scatter
-        const uint64_t tiles = (M + tile - 1) / tile;
         uint64_t entries = 0;
         for (;;) {
-            lv[0].blocks_per_seg = (uint32_t)std::min<uint64_t>(tiles, 2048);
+            lv[0].blocks_per_seg = level1_blocks_per_seg(M, tile);
             a.seg_pos = nullptr; a.seg_stride = 1; a.blocks_per_seg = lv[0].blocks_per_seg; a.shift = lv[0].shift; a.ways = lv[0].ways; a.mix_bits = lv[0].bits;
             entries = (uint64_t)lv[0].ways * lv[0].blocks_per_seg;
             MDBG_TRY(hist.alloc(ctx, entries));
@@ -877,8 +921,7 @@ struct PartRun {
         cur = 0;
         for (uint32_t l = 1; l < n_levels; l++) {
             const uint64_t n_seg = lv[l].n_seg;
-            const uint64_t avg_tiles = (I / n_seg + tile - 1) / tile;
-            lv[l].blocks_per_seg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(1, 4096 / n_seg), avg_tiles));
+            lv[l].blocks_per_seg = deeper_blocks_per_seg(I, n_seg, tile);
             SplitArgs d{};
             d.in = buf[cur].view();
             d.seg_pos = place[l - 1].p; d.seg_stride = lv[l - 1].blocks_per_seg; d.blocks_per_seg = lv[l].blocks_per_seg;
@@ -886,7 +929,7 @@ struct PartRun {
             entries = n_seg * lv[l].ways * lv[l].blocks_per_seg;
             MDBG_TRY(hist.alloc(ctx, entries));
             MDBG_TRY(place[l].alloc(ctx, entries + 1));
-            const unsigned grid = (unsigned)(n_seg * lv[l].blocks_per_seg);
+            const unsigned grid = level_grid(n_seg, lv[l].blocks_per_seg);
             {
                 LaunchTimer timer(ctx, "kminmer_split");
                 launch_split_hist(ctx, false, form, grid, d, hist.p);
@@ -915,7 +958,7 @@ struct PartRun {
         }
         {
             LaunchTimer timer(ctx, "kminmer_insert");
-#define MDBG_BC(C, L) launch_bucket_count<C, L>(ctx, n_buckets, records(), pos, stride, min_abundance, clip, keep_all, keys(), kcnt.p, n_keys.p, n_kept.p, cnt8, cnt8_default, overflow.p)
+#define MDBG_BC(C, L) launch_bucket_count<C, L>(ctx, n_buckets, records(), pos, stride, min_abundance, clip, keep_all, keys(), kcnt.p, n_keys.p, n_kept.p, cnt8, cnt8_default, overflow.p, fell_back.p)
             const bool list = ctx->part_slot_list != 0;
             if (lds_slots == 256) { if (list) MDBG_BC(256, 8000); else MDBG_BC(256, 0); }
             else if (lds_slots == 1024) { if (list) MDBG_BC(1024, 8000); else MDBG_BC(1024, 0); }
@@ -930,6 +973,12 @@ struct PartRun {
     void record_info(uint32_t attempt, uint64_t total_inst) const {
         ctx->part_info[0] = 2; ctx->part_info[1] = n_groups; ctx->part_info[2] = bucket_bits; ctx->part_info[3] = n_levels;
         ctx->part_info[4] = attempt; ctx->part_info[5] = lds_slots; ctx->part_info[6] = n_buckets; ctx->part_info[7] = total_inst;
+        ctx->part_fell_back = fell_back_host;
+    }
+    // (with the pass's other totals: the caller synchronises before it reads fell_back_host)
+    int read_fell_back() {
+        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&fell_back_host, fell_back.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        return MDBG_OK;
     }
 };
 
@@ -1000,6 +1049,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
 
         // rescue decision per read, row positions
         uint64_t n_resc = 0;
+        MDBG_TRY(run.read_fell_back());
         if (!overflowed && do_rescue) {
             MDBG_TRY(resc_cnt.alloc(ctx, n_reads));
             MDBG_TRY(resc_pos.alloc(ctx, (size_t)n_reads + 1));
@@ -1220,13 +1270,12 @@ int part_owner_reduce(mdbg_ctx *ctx, const uint64_t *d_rows, uint64_t n_recv, ui
         d.in = buf[cur].view();
         d.n_min = n_recv;                                          // level 1: one segment, the rows as they arrived
         d.seg_pos = l ? place[l - 1].p : nullptr; d.seg_stride = prev_bps;
-        const uint64_t avg_tiles = (n_recv / n_seg + tile - 1) / tile;
-        d.blocks_per_seg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(1, 4096 / n_seg), avg_tiles));
+        d.blocks_per_seg = deeper_blocks_per_seg(n_recv, n_seg, tile);
         d.ways = 1u << b; d.shift = b ? 64u - used - b : 0u; d.tile = tile;
         const uint64_t entries = n_seg * d.ways * d.blocks_per_seg;
         MDBG_TRY(hist.alloc(ctx, entries));
         MDBG_TRY(place[l].alloc(ctx, entries + 1));
-        const unsigned grid = (unsigned)(n_seg * d.blocks_per_seg);
+        const unsigned grid = level_grid(n_seg, d.blocks_per_seg);
         launch_split_hist(ctx, false, form, grid, d, hist.p);
         MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[l].p, entries));
         launch_split_scatter(ctx, false, form, grid, d, place[l].p, buf[cur ^ 1].view());
