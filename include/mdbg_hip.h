@@ -102,6 +102,20 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *                           never depend on it; mdbg_scan_confirm_info tells which path ran
  *   "scan_confirm_table_log2_buckets"  tests only: the table is built and probed with 2^value buckets (10 .. 16; 0 = the kernel's own 2^16), so
  *                           that most buckets overflow and looked-up and hashed verdicts mix in one round.  Results never depend on it
+ *   "scan_persistent"       1 (default) = the pre-filtered variant is launched with as many workgroups as fit the device at once (one per
+ *                           CU, fewer for a small batch) and none pending behind them; its waves draw runs of consecutive reads from one
+ *                           64-bit counter in device memory until it is used up, and rows go to the region of their read's run: alone 3 %
+ *                           faster on 10 kb reads and 6 % on reads of 1 - 25 kb, the benchmark's step 2 %.  0 = the chunked
+ *                           form: a workgroup per chunk of reads, dealt out by the dispatcher.  An explicit non-zero "scan_reads_per_wave"
+ *                           (or MDBG_SCAN_READS_PER_WAVE) names the chunked form and gets it whatever this says.  A context with
+ *                           "scan_lds_reserve" > 0 and "partition_threads" 0 whose last block-kernel scan was such a launch also takes the
+ *                           four-wave split kernels (below), which fit beside a scan workgroup that never retires.
+ *                           MDBG_SCAN_PERSISTENT=0 / 1 sets the default of new contexts.
+ *                           Results never depend on it (the rows' places do); mdbg_scan_persistent_info tells which form ran
+ *   "scan_grab_reads"       consecutive reads a wave of the persistent launch draws at a time (1 .. 65536); 0 (default) = the library's own, 4.
+ *                           MDBG_SCAN_GRAB_READS sets the default of new contexts
+ *   "scan_persistent_blocks"  tests only: at most this many workgroups in a persistent launch (0 = no cap), so that the waves of a small
+ *                           batch draw many runs.  Results never depend on it
  *   "scan_segments"         long reads, contigs and unitigs cut into segments that the block-structured scan takes one wave each: a plain read
  *                           (no N, no case flip) of more than one segment is scanned as several views -- each owns the windows that start
  *                           in its segment and reads one 2048-base tile on behind it -- and the views' rows are joined in read order.
@@ -352,7 +366,9 @@ int  mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]);
  * kernels: 0 (the default) or 512 = eight waves, tiles of 4096 records (2048 under "partition_tile" 2048); 256 = four waves, one per
  * SIMD, tiles of 1024 records, at most 72 vector registers and 15 KB of LDS -- within the 96 registers per lane that another context's
  * 16-wave scan workgroup leaves of a SIMD, which the eight-wave forms are not.  Beside that scan the four-wave forms measured SLOWER and
- * the scan no faster, so they are opt-in: for that comparison and for tests.  Results never depend on it.
+ * the scan no faster, so they are opt-in: for that comparison and for tests -- and what 0 means in a context with
+ * "scan_lds_reserve" > 0 whose last block-kernel scan was a persistent launch ("scan_persistent"): those workgroups never retire to let an eight-wave block
+ * in, and beside them the four-wave forms measured faster.  Results never depend on it.
  * mdbg_first_pass_form tells which form the context's last split kernels took: form[0] = threads per block, [1] = records per tile,
  * [2] and [3] = 0.
  * mdbg_first_pass_slot_fall_backs: the instances of the last partitioned first pass whose LDS slot the bucket count looked up a second
@@ -379,6 +395,9 @@ int  mdbg_scan_info(const mdbg_ctx *ctx, uint64_t info[8]);
  * the last one, [2] = buckets of it that ask the hash (more than seven keys; or, in a test geometry below 2^16 buckets, a tag shared with a
  * key that is not selected), [3] = 1 when the last pre-filtered launch took its verdicts from the table, 0 when it hashed its candidates. */
 int  mdbg_scan_confirm_info(const mdbg_ctx *ctx, uint64_t info[4]);
+/* The form of the context's last pre-filtered launch ("scan_persistent" above): info[0] = 1 persistent / 0 chunked, [1] = its workgroups,
+ * [2] = reads a wave drew at a time (0 when chunked), [3] = persistent launches of the context so far. */
+int  mdbg_scan_persistent_info(const mdbg_ctx *ctx, uint64_t info[4]);
 /* Order-independent sums over the rows, wrapping at 2^64, computed on the device (nothing but 32 bytes travels):
  *   sums[0] = sum abundance * hash_lo -- the "Checksum kminmer abundance" the reference logs when it loads the table again
  *             (CreateMdbg::loadRefinedAbundances, graph/CreateMdbg.cpp:3300-3321, :3397: `abundance * vecHash` truncated to u64),

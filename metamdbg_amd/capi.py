@@ -94,6 +94,7 @@ SIGNATURES = {
     "mdbg_first_pass_info": (C.c_int, [_P, _u64p]),
     "mdbg_scan_info": (C.c_int, [_P, _u64p]),
     "mdbg_scan_confirm_info": (C.c_int, [_P, _u64p]),
+    "mdbg_scan_persistent_info": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_form": (C.c_int, [_P, _u64p]),
     "mdbg_first_pass_slot_fall_backs": (C.c_int, [_P, _u64p]),
     "mdbg_step_kernel_name": (C.c_char_p, [C.c_uint32]),
@@ -274,6 +275,12 @@ class Context:
         self.check(lib().mdbg_scan_confirm_info(self.h, a))
         names = ("tables_built", "table_buckets", "table_overflowed", "last_by_table")
         return {k: int(v) for k, v in zip(names, a)}
+
+    def scan_persistent_info(self) -> dict:
+        """The form of this context's last pre-filtered scan launch (mdbg_scan_persistent_info)."""
+        a = (C.c_uint64 * 4)()
+        self.check(lib().mdbg_scan_persistent_info(self.h, a))
+        return {"form": "persistent" if a[0] else "chunked", "workgroups": int(a[1]), "grab_reads": int(a[2]), "persistent_launches": int(a[3])}
 
     # -- timing ---------------------------------------------------------------------------
     def timing(self, on: bool) -> None:

@@ -171,6 +171,15 @@ struct mdbg_ctx {
     uint64_t scan_info[8] = {0};            // mdbg_scan_info: [0] launches of the pre-filtered variant, [1] of the four-wave block kernels, [2] bitmaps built,
                                             // [3] bits set in the last, [4] its log2 size, [5] waves a workgroup of the last pre-filtered launch, [6] 1 when
                                             // the last block-kernel launch was pre-filtered, [7] reads the last mdbg_scan scanned as segments
+    // the pre-filtered variant's persistent launch (scan_plan.hpp): one workgroup per CU, reads dealt from one counter in device memory
+    uint32_t scan_persistent = 1;           // "scan_persistent": 1 = taken unless "scan_reads_per_wave" names the chunked form (default), 0 = the chunked form (mdbg_set_option, MDBG_SCAN_PERSISTENT)
+    uint32_t scan_grab_reads = 0;           // "scan_grab_reads": consecutive items a wave draws at a time; 0 = the default (PERSISTENT_GRAB_READS)
+    uint32_t scan_persistent_blocks = 0;    // tests: caps the persistent grid, so that the waves of a small batch draw many runs
+    static constexpr uint32_t SCAN_COUNTER_SLOTS = 16;
+    unsigned long long *scan_counters = nullptr;    // device: SCAN_COUNTER_SLOTS counters, one per pre-filtered launch of a call (the batch's, its views'), taken
+    uint32_t scan_counter_next = 0;         // in turn; each is zeroed on its launch's stream in front of the launch
+    uint64_t scan_persistent_info[4] = {0}; // mdbg_scan_persistent_info: the last pre-filtered launch -- [0] 1 persistent / 0 chunked, [1] its workgroups, [2] R (0 when
+                                            // chunked), [3] persistent launches so far
     // distinct keys per k-min-mer instance seen by the last call OF THE SAME KIND (table sizing): the first pass keeps every
     // key, refined / index only those above abundance 1 -- one shared hint made every first pass after an index pass rebuild its table
     double key_ratio_hint[4] = {0.0625, 0.0625, 0.0625, 0.0625};   // [0] first pass, [1] refined, [2] index, [3] sharded first pass

@@ -68,6 +68,8 @@ extern "C" int mdbg_create(int device, mdbg_ctx **out) try {
     if (const char *e = getenv("MDBG_SCAN_LDS_RESERVE")) ctx->scan_lds_reserve = (uint32_t)std::max(0, std::min(131072, atoi(e)));
     if (const char *e = getenv("MDBG_SCAN_PREFILTER")) ctx->scan_prefilter = atoi(e) != 0;
     if (const char *e = getenv("MDBG_SCAN_CONFIRM_TABLE")) ctx->scan_confirm_table = atoi(e) != 0;
+    if (const char *e = getenv("MDBG_SCAN_PERSISTENT")) ctx->scan_persistent = atoi(e) != 0;
+    if (const char *e = getenv("MDBG_SCAN_GRAB_READS")) ctx->scan_grab_reads = (uint32_t)std::max(0, std::min(1 << 16, atoi(e)));
     if (const char *e = getenv("MDBG_SCAN_SEGMENTS")) ctx->scan_segments = atoi(e) == 0 ? 0u : (atoi(e) == 2 ? 2u : 1u);
     if (const char *e = getenv("MDBG_SCAN_LDS_PAD")) ctx->scan_lds_pad = (uint32_t)std::max(0, std::min(32768, atoi(e)));
     if (const char *e = getenv("MDBG_PARTITION_TILE")) ctx->part_tile = atoi(e) == 2048 ? 2048u : 0u;
@@ -105,6 +107,7 @@ extern "C" void mdbg_destroy(mdbg_ctx *ctx) {
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->prefilter_bits) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->prefilter_bits); }
     if (ctx->confirm_table) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->confirm_table); }
+    if (ctx->scan_counters) { std::lock_guard<std::mutex> g(hip_mem_mutex()); (void)hipFree(ctx->scan_counters); }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -191,6 +194,9 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
     if (n == "scan_guard_slack") { ctx->scan_guard_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll - 68) : 0u; return MDBG_OK; }
     if (n == "scan_prefilter") { ctx->scan_prefilter = value != 0; return MDBG_OK; }
     if (n == "scan_confirm_table") { ctx->scan_confirm_table = value != 0; return MDBG_OK; }
+    if (n == "scan_persistent") { ctx->scan_persistent = value != 0; return MDBG_OK; }
+    if (n == "scan_grab_reads") { ctx->scan_grab_reads = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 16, value)); return MDBG_OK; }
+    if (n == "scan_persistent_blocks") { ctx->scan_persistent_blocks = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 20, value)); return MDBG_OK; }
     if (n == "scan_confirm_table_log2_buckets") {
         if (value != 0 && (value < 10 || value > 16)) return set_error(ctx, MDBG_EINVAL, "scan_confirm_table_log2_buckets: 0 (the kernel's own) or 10 .. 16");
         ctx->scan_confirm_table_log2_buckets = (uint32_t)value; return MDBG_OK;

@@ -709,11 +709,17 @@ struct RecBufs {
 };
 
 // Which form of the split kernels a context takes: threads per block and records per tile.  "partition_threads" 256 takes the four-wave
-// forms; 0 and 512 the eight-wave ones, whose tile "partition_tile" chooses as before.
+// forms; 0 and 512 the eight-wave ones, whose tile "partition_tile" chooses as before.  Left at 0 in a context that shares its device
+// ("scan_lds_reserve" > 0), has "scan_persistent" on and whose last block-kernel scan WAS a persistent launch of the pre-filtered variant, it
+// takes the four-wave forms too: the eight-wave ones need 112 - 160 registers a lane where a scan workgroup leaves 96, and beside a scan whose
+// workgroups never retire they do not start before the launch ends (measured: DESIGN.md 4.4; + 1.1 % of the benchmark's step).  The context's own
+// last scan stands for its neighbour's -- the contexts of a process scan alike -- so one that has not scanned, or whose batches take the four-wave
+// scan kernels (qualities, other l), keeps the eight-wave forms, which win beside a scan whose workgroups retire.
 struct SplitForm { uint32_t threads, tile; };
 
 static SplitForm split_form(const mdbg_ctx *ctx) {
-    if (ctx->part_threads == PART_NT_SMALL) return SplitForm{PART_NT_SMALL, PART_TILE_SMALL};
+    const bool beside_persistent_scan = ctx->part_threads == 0 && ctx->scan_lds_reserve && ctx->scan_persistent && ctx->scan_info[6] && ctx->scan_persistent_info[0];
+    if (ctx->part_threads == PART_NT_SMALL || beside_persistent_scan) return SplitForm{PART_NT_SMALL, PART_TILE_SMALL};
     return SplitForm{PART_NT, ctx->part_tile == 2048 ? PART_TILE / 2 : PART_TILE};
 }
 

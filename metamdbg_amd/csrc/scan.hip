@@ -111,6 +111,10 @@ struct ScanArgs {
     const SegView *views;
     unsigned long long *view_cx;  // per view: its words' share of the read's complexity sum
     uint32_t seg_tiles;           // tiles of a segment ("scan_segment_bases" / 2048)
+    // scan_fast_kernel<.., PFW>, the persistent launch (scan_plan.hpp): non-null, the waves of every workgroup draw runs of pf_grab
+    // consecutive items from this one counter (zeroed on the launch's stream in front of it) instead of from their workgroup's chunk
+    unsigned long long *pf_counter;
+    uint32_t pf_grab;
 };
 
 // squeeze the 2-bit fields of x whose flag bit (bit 2i of d) is set down to the low end
@@ -938,7 +942,26 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
     constexpr uint32_t NO_READ = 0xFFFFFFFFu;               // no read has this index: n_reads is a 32-bit count
     const uint64_t chunk0 = (uint64_t)blockIdx.x * a.pf_chunk;
     const uint32_t chunk_n = PF ? (chunk0 >= a.n_reads ? 0u : (uint32_t)(a.n_reads - chunk0 < a.pf_chunk ? a.n_reads - chunk0 : a.pf_chunk)) : 0u;
+    // ... or, in the persistent launch, runs of pf_grab consecutive items come from one counter in device memory for the whole grid
+    // (scan_plan.hpp: persistent_run_end, persistent_region).  run_next .. run_end is what is left of this wave's run; all wave-uniform
+    unsigned long long *const pf_counter = PF ? a.pf_counter : nullptr;
+    uint32_t run_next = 0, run_end = 0, run_region = 0;
     auto take_read = [&]() -> uint32_t {
+        if (pf_counter) {
+            if (run_next == run_end) {
+                uint32_t lo = 0, hi = 0;
+                if (lane == 0) {
+                    const unsigned long long s0 = __hip_atomic_fetch_add(pf_counter, (unsigned long long)a.pf_grab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    lo = (uint32_t)s0; hi = (uint32_t)(s0 >> 32);
+                }
+                lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo); hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi);
+                if (hi || lo >= a.n_reads) return NO_READ;        // used up: this wave leaves
+                run_next = lo;
+                run_end = a.n_reads - lo < a.pf_grab ? a.n_reads : lo + a.pf_grab;        // the last run is clipped
+                run_region = (lo / a.pf_grab) & (a.n_regions - 1u);
+            }
+            return run_next++;
+        }
         uint32_t k = 0;
         if (lane == 0) k = atomicAdd(pf_next, 1u);
         k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
@@ -1550,7 +1573,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             uint64_t start = 0;
             if (!outgrown && nout) {
                 uint32_t lo = 0, hi = 0;
-                const uint32_t region = wave_global & (a.n_regions - 1u);
+                const uint32_t region = pf_counter ? run_region : wave_global & (a.n_regions - 1u);
                 if (lane == 0) { const unsigned long long s0 = atomicAdd(a.cursor + region, (unsigned long long)nout); lo = (uint32_t)s0; hi = (uint32_t)(s0 >> 32); }
                 start = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
                 const bool fits = start + nout <= a.out_capacity;
@@ -2161,12 +2184,28 @@ static unsigned four_wave_lds_pad(const mdbg_ctx *ctx, ScanKernel fk) {
     return scan_lds_padding(ctx->scan_lds_pad, ctx->scan_lds_reserve, ctx->lds_per_cu, by_reserve ? kernel_static_lds(reinterpret_cast<const void *>(fk)) : 0);
 }
 
+// The counter of one persistent launch: the context's next slot, zeroed on the stream the launch goes to.  A call makes more than one
+// such launch (the batch's, its views'); each has a slot of its own, and a slot comes round again only SCAN_COUNTER_SLOTS launches
+// later on a stream that orders them.
+static int scan_counter_take(mdbg_ctx *ctx, hipStream_t on, unsigned long long **counter) {
+    if (!ctx->scan_counters) {
+        std::lock_guard<std::mutex> g(hip_mem_mutex());
+        hipError_t e = hipMalloc((void **)&ctx->scan_counters, mdbg_ctx::SCAN_COUNTER_SLOTS * sizeof(unsigned long long));
+        if (e != hipSuccess) { ctx->scan_counters = nullptr; return set_error(ctx, MDBG_ENOMEM, "hipMalloc of the scan's read counters: %s", hipGetErrorString(e)); }
+    }
+    *counter = ctx->scan_counters + ctx->scan_counter_next;
+    ctx->scan_counter_next = (ctx->scan_counter_next + 1u) % mdbg_ctx::SCAN_COUNTER_SLOTS;
+    MDBG_HIP_CHECK(ctx, hipMemsetAsync(*counter, 0, sizeof(unsigned long long), on));
+    return MDBG_OK;
+}
+
 // pf_len_limit > 0: the batch may take the pre-filtered variant, whose stage a read shorter than that is expected to fit; pf_split:
 // the batch also holds longer reads -- a launch of the four-wave kernel in front of it scans those (ScanArgs::pf_len_split)
 // seg: the items are views of long reads (ScanArgs::views): the SEG instantiations of the block-structured kernels, chosen as for reads
 static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool has_n, uint32_t n_items, uint32_t pf_len_limit = 0, bool pf_split = false,
                        uint64_t batch_bases = 0, bool seg = false) {
     a.n_reads = n_items;
+    a.pf_counter = nullptr; a.pf_grab = 0;
     const ScanSwitches &sw = scan_switches();
     const bool fast = (!has_q || a.cursor) && !has_n && !a.subset && !sw.no_fast;
     const bool approx = fast && a.cursor && sw.approx_allowed && candidate_test_usable(a.threshold, a.cand_slack);
@@ -2204,10 +2243,24 @@ static int launch_scan(mdbg_ctx *ctx, ScanArgs &a, bool hpc, bool has_q, bool ha
             a.pf_table = by_table ? reinterpret_cast<const uint4 *>(ctx->confirm_table) : nullptr;
             a.pf_table_shift = by_table ? 32u - ctx->confirm_log2 : 0u;
             ctx->scan_confirm_info[3] = by_table ? 1 : 0;
-            const PrefilterGrid grid = prefilter_grid(n_items, pf_waves, ctx->scan_reads_per_wave, ctx->n_cu);
-            a.pf_chunk = grid.chunk;
             a.pf_len_split = pf_split ? pf_len_limit : 0u;
-            hipLaunchKernelGGL(select_fast_kernel(true, false, true, pf_waves, seg), dim3(grid.blocks), dim3(64u * pf_waves), 0, loan.on, a);
+            if (persistent_taken(ctx->scan_persistent, ctx->scan_reads_per_wave)) {
+                // as many workgroups as CUs and none pending; every wave draws runs of reads from the launch's counter until it is used up
+                unsigned long long *counter = nullptr;
+                MDBG_TRY(scan_counter_take(ctx, loan.on, &counter));
+                a.pf_counter = counter;
+                a.pf_grab = persistent_grab(ctx->scan_grab_reads);
+                a.pf_chunk = 0;
+                const unsigned blocks = persistent_grid(n_items, pf_waves, a.pf_grab, ctx->n_cu, ctx->scan_persistent_blocks);
+                hipLaunchKernelGGL(select_fast_kernel(true, false, true, pf_waves, seg), dim3(blocks), dim3(64u * pf_waves), 0, loan.on, a);
+                ctx->scan_persistent_info[0] = 1; ctx->scan_persistent_info[1] = blocks; ctx->scan_persistent_info[2] = a.pf_grab; ctx->scan_persistent_info[3]++;
+            } else {
+                const PrefilterGrid grid = prefilter_grid(n_items, pf_waves, ctx->scan_reads_per_wave, ctx->n_cu);
+                a.pf_chunk = grid.chunk;
+                a.pf_counter = nullptr; a.pf_grab = 0;
+                hipLaunchKernelGGL(select_fast_kernel(true, false, true, pf_waves, seg), dim3(grid.blocks), dim3(64u * pf_waves), 0, loan.on, a);
+                ctx->scan_persistent_info[0] = 0; ctx->scan_persistent_info[1] = grid.blocks; ctx->scan_persistent_info[2] = 0;
+            }
             ctx->scan_info[0]++; ctx->scan_info[5] = pf_waves;
         }
     }
@@ -2751,6 +2804,12 @@ extern "C" int mdbg_scan(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_scan
 extern "C" int mdbg_scan_confirm_info(const mdbg_ctx *ctx, uint64_t info[4]) {
     if (!ctx || !info) return MDBG_EINVAL;
     for (int i = 0; i < 4; i++) info[i] = ctx->scan_confirm_info[i];
+    return MDBG_OK;
+}
+
+extern "C" int mdbg_scan_persistent_info(const mdbg_ctx *ctx, uint64_t info[4]) {
+    if (!ctx || !info) return MDBG_EINVAL;
+    for (int i = 0; i < 4; i++) info[i] = ctx->scan_persistent_info[i];
     return MDBG_OK;
 }
 

@@ -135,6 +135,34 @@ inline PrefilterGrid prefilter_grid(uint32_t n_items, unsigned pf_waves, uint32_
     return PrefilterGrid{(uint32_t)chunk, (unsigned)blocks};
 }
 
+// ---- the pre-filtered variant's PERSISTENT launch ("scan_persistent"): as many workgroups as fit the device at once -- one per CU --
+// and none pending behind them.  Every wave draws runs of R consecutive items from one 64-bit counter in device memory (a returning
+// add of R; the kernel repeats this arithmetic) until it draws a start at or behind n_items.  No workgroup waits for another: whatever
+// subset of the grid is resident, the counter hands every item out exactly once and a workgroup that starts late finds it used up.
+// R ("scan_grab_reads"; 0 = this default): one address takes about 88 returning adds a microsecond (the cursors' price, ScanArgs::cursor);
+// 10 M reads in 62 ms would be 161 / 80 / 40 / 20 adds a microsecond at R = 1 / 2 / 4 / 8.  Measured alone (profiles/scan_persistent_lone_scan.txt),
+// 10 M x 10 kb: 121.2 / 61.6 / 61.05 / 60.95 / 61.0 ms at R = 1 / 2 / 4 / 8 / 16 against 62.9 ms chunked -- at R = 1 the launch runs at the
+// counter's rate, 83 adds a microsecond; 500 000 reads of 1 .. 25 kb: 6.09 / 3.11 / 2.57 / 2.62 / 2.72 ms against 2.74 chunked -- a long run
+// leaves the end of a launch to the wave that drew it.  4 is the smallest R within a run's spread (0.1 ms) of the best on the first and the best on the second.
+constexpr unsigned PERSISTENT_GRAB_READS = 4, PERSISTENT_GRAB_MAX = 1u << 16;
+inline unsigned persistent_grab(uint32_t grab_option) { return grab_option ? std::min<uint32_t>(grab_option, PERSISTENT_GRAB_MAX) : PERSISTENT_GRAB_READS; }
+// an explicit "scan_reads_per_wave" asks for the chunked form by name and gets it, whatever "scan_persistent" says
+inline bool persistent_taken(uint32_t persistent_option, uint32_t reads_per_wave_option) { return persistent_option && !reads_per_wave_option; }
+// workgroups: min(n_cu, ceil(n_items / (waves * R))), at least 1; blocks_cap > 0 ("scan_persistent_blocks", tests) caps them further
+inline unsigned persistent_grid(uint32_t n_items, unsigned waves, unsigned grab, int n_cu, uint32_t blocks_cap) {
+    const uint64_t per_group = (uint64_t)waves * grab;
+    uint64_t blocks = std::min<uint64_t>(((uint64_t)n_items + per_group - 1) / per_group, (uint64_t)std::max(n_cu, 1));
+    if (blocks_cap) blocks = std::min<uint64_t>(blocks, blocks_cap);
+    return (unsigned)std::max<uint64_t>(blocks, 1);
+}
+// the run a wave holds after drawing `start` (the counter's value before its add): [start, end), empty when the counter is used up
+inline uint32_t persistent_run_end(uint64_t start, unsigned grab, uint32_t n_items) {
+    return start >= n_items ? (uint32_t)n_items : (uint32_t)std::min<uint64_t>(start + grab, n_items);
+}
+// Rows to regions: by the item's run, not by the wave that drew it -- consecutive runs go to consecutive regions, so the fill is even
+// within one run a region whichever workgroups got onto a CU and when
+inline uint32_t persistent_region(uint32_t item, unsigned grab, uint32_t n_regions) { return (item / grab) & (n_regions - 1u); }
+
 // ---- LDS (lds_per_cu 0: not known, a CU of gfx950 has 160 KB)
 inline size_t lds_of_a_cu(size_t lds_per_cu) { return lds_per_cu ? lds_per_cu : 163840u; }
 // the pre-filtered variant takes as many waves a workgroup as leave "scan_lds_reserve" free: 16, else 8, else none
