@@ -569,6 +569,59 @@ int  mdbg_prev_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records, uint6
 #define MDBG_RECORDS_INIT  1   /* read_data_init.txt: mdbg_scan output only */
 int  mdbg_minimizers_to_record_bytes(mdbg_ctx *ctx, const mdbg_minimizers *m, int form, mdbg_bytes **out, uint64_t *n_bytes /* optional */);
 
+/* ---- contig sequences stitched from pieces, and their FASTA text ---------------------------------------------------------------------------
+ * Replaces the last step of the same caller: ToBasespaceGfa::createBaseContigs / CreateBaseContigsFunctor::operator() (toBasespace/
+ * ToBasespaceGfa.hpp:1437-1795), which walks a contig's windows, looks up the stored piece of each (_readPosition_entire / _right /
+ * _left, :1547-1702), to_string()s it, runs Utils::revcomp over it when the contig's window is reversed, appends, and writes
+ * ">ctg<index><l|c>\n<sequence>\n" through gzwrite (:1756-1785).  The pieces of mdbg_spans_extract start at multiples of 8 bytes and
+ * cannot be joined by copying; here the contig is gathered from the resident reads directly, at 2 bits a base.
+ *
+ * Sequence c of the result is the concatenation, in order, of the oriented pieces piece_offsets[c] .. piece_offsets[c + 1] (piece_offsets:
+ * host, n_contigs + 1 entries, starts at 0, never decreases; its last entry is the number of pieces).
+ *   mdbg_spans_stitch         a piece is (window, part, flip): the range extract_part_range gives for (window, part) exactly as
+ *                             mdbg_spans_extract takes it, oriented by the READ's window; flip != 0 reverse-complements that oriented
+ *                             piece once more -- the CONTIG window's own _isReversed -- so the net orientation of the range is
+ *                             reversed ^ flip.  window == MDBG_STITCH_NONE is "no sequence for this k-min-mer": it contributes nothing
+ *                             (the reference's `continue`) and its other fields are not looked at.
+ *   mdbg_reads_stitch_ranges  the pieces are mdbg_seq_range as they stand; length 0 is allowed and contributes nothing.
+ * The piece rule CreateBaseContigsFunctor uses: window 0 of a contig takes MDBG_SEQ_ENTIRE (flip when the contig's window is reversed);
+ * every later window takes MDBG_SEQ_RIGHT with flip 0 when the contig's window is forward and MDBG_SEQ_LEFT with flip 1 when it is
+ * reversed.  A window without a stored sequence is skipped but still counts as a position: the window behind a skipped window 0 is not
+ * ENTIRE.
+ *
+ * The result is an ordinary mdbg_sequences (mdbg_sequences_info / _to_host / _device_ptrs / _free): forms MDBG_SEQ_BITSET and
+ * MDBG_SEQ_ASCII, every contig at a multiple of 8 bytes, padding zero, lengths = the contig's bases.  Zero contigs, contigs without pieces
+ * and contigs of empty pieces give empty sequences (length 0, no bytes).
+ *
+ * Invalid bases -- the one rule that differs from mdbg_spans_extract.  The reference stores the READ-oriented piece as DnaBitset2, where
+ * a character outside ACGT is A, and calls Utils::revcomp on the string of a reversed contig window afterwards.  So in BITSET form a base
+ * under the invalid mask is code 0 (A) when flip == 0 and code 3 (T) when flip != 0, whatever the read window's orientation.  In
+ * mdbg_reads_stitch_ranges it is code 0 always, as in mdbg_reads_extract_ranges.  In ASCII form it is N in both entries.
+ *
+ * Refusals, MDBG_EINVAL with a message that names the first offending piece and its contig, *out untouched, no base read before the
+ * checks have run on the device: every refusal of mdbg_spans_extract / mdbg_reads_extract_ranges, per piece (there is no reserved field);
+ * piece_offsets that do not start at 0 or decrease (checked on the host); a form out of range.  MDBG_ERANGE: 2^32 pieces or more, 2^32
+ * contigs or more, a contig of 2^32 bases or more.  Timer names: "stitch_plan", "stitch_copy".
+ *
+ * mdbg_sequences_to_fasta_bytes  the exact bytes CreateBaseContigsFunctor hands to gzwrite, uncompressed, in an mdbg_bytes of exactly
+ *                             that size (mdbg_bytes_download, mdbg_bytes_free).  seqs must be in MDBG_SEQ_BITSET form.  names (host, n;
+ *                             NULL: 0, 1, 2 ...) are the contigs' indices, circular (host, n; NULL: all 0) their flags.  A non-empty
+ *                             sequence i gives ">ctg", the decimal digits of names[i], "l" for flag 0 and "c" for flags 1 and 2, '\n',
+ *                             its bases as ACGT decoded from the 2-bit codes (DnaBitset2::to_string: no N, no line wrap), '\n'.  (The
+ *                             functor has an "rc" for flag 2, CONTIG_CIRCULAR_RESCUED, but narrows the flag to `bool isCircular`
+ *                             first, :1487, so that branch is never reached and a rescued contig is written "c": so is it here.)  An empty
+ *                             sequence gives ">ctg<name>l\nA\n" whatever its flag (:1756-1764).  Zero sequences give a buffer of 0 bytes.
+ *                             MDBG_EINVAL: ASCII-form input, a flag above 2, a null argument.  The call returns when the text is
+ *                             complete.  Timer names: "fasta_plan", "fasta_write". */
+typedef struct { uint64_t window; uint32_t part; uint32_t flip; } mdbg_stitch_piece;
+#define MDBG_STITCH_NONE UINT64_MAX
+int  mdbg_spans_stitch(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_spans *spans, const mdbg_stitch_piece *pieces,
+                       const uint64_t *piece_offsets, uint64_t n_contigs, int form, mdbg_sequences **out);
+int  mdbg_reads_stitch_ranges(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg_seq_range *ranges, const uint64_t *piece_offsets,
+                              uint64_t n_contigs, int form, mdbg_sequences **out);
+int  mdbg_sequences_to_fasta_bytes(mdbg_ctx *ctx, const mdbg_sequences *seqs, const uint32_t *names /* optional */,
+                                   const uint8_t *circular /* optional */, mdbg_bytes **out, uint64_t *n_bytes /* optional */);
+
 /* ---- FASTA / FASTQ text taken apart on the device -----------------------------------------------------------------------------------
  * Replaces the host side of ReadParserParallel for a plain file: the kseq loop (KSEQ_INIT(gzFile, gzread), Commons.hpp:82) that
  * ReadParser::parse / ReadParserParallel::parse run over every character (Commons.hpp:5827-5922).  The file's bytes travel as they are

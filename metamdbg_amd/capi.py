@@ -20,6 +20,8 @@ SEQ_ENTIRE, SEQ_LEFT, SEQ_RIGHT = 0, 1, 2   # MDBG_SEQ_*: the parts of a window 
 SEQ_BITSET, SEQ_ASCII = 0, 1                # ... and the forms it writes them in
 SEQ_REQUEST = np.dtype([("window", "<u8"), ("part", "<u4"), ("reserved", "<u4")])                  # mdbg_seq_request
 SEQ_RANGE = np.dtype([("read", "<u4"), ("start", "<u4"), ("length", "<u4"), ("reversed", "<u4")])  # mdbg_seq_range
+STITCH_PIECE = np.dtype([("window", "<u8"), ("part", "<u4"), ("flip", "<u4")])                      # mdbg_stitch_piece
+STITCH_NONE = 0xFFFFFFFFFFFFFFFF            # MDBG_STITCH_NONE: no sequence for this k-min-mer
 
 
 class MdbgError(RuntimeError):
@@ -120,6 +122,9 @@ SIGNATURES = {
     "mdbg_sequences_to_host": (C.c_int, [_P, _P, _P, _P, _P]),
     "mdbg_sequences_device_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "mdbg_sequences_free": (None, [_P]),
+    "mdbg_spans_stitch": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P)]),
+    "mdbg_reads_stitch_ranges": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_int, C.POINTER(_P)]),
+    "mdbg_sequences_to_fasta_bytes": (C.c_int, [_P, _P, _P, _P, C.POINTER(_P), _u64p]),
     "mdbg_row_words": (C.c_uint32, [C.c_uint32]),
     "mdbg_shard_begin": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(_P), _u64p]),
     "mdbg_shard_reduce": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
@@ -431,6 +436,35 @@ class Context:
         h = _P()
         self.check(lib().mdbg_reads_extract_ranges(self.h, reads.h, _ptr(rg), len(rg), form, C.byref(h)))
         return Sequences(self, h)
+
+    def spans_stitch(self, reads: "Reads", spans: "Spans", pieces: np.ndarray, piece_offsets, form: int = SEQ_BITSET) -> "Sequences":
+        """Contig c = the oriented pieces piece_offsets[c] .. piece_offsets[c + 1] one behind the other (mdbg_spans_stitch); pieces is an array
+        of STITCH_PIECE records (stitch_pieces builds it by the reference's rule)."""
+        pc = np.ascontiguousarray(pieces, STITCH_PIECE)
+        off = np.ascontiguousarray(piece_offsets, np.uint64)
+        h = _P()
+        self.check(lib().mdbg_spans_stitch(self.h, reads.h, spans.h, _ptr(pc) if len(pc) else None, _ptr(off), len(off) - 1, form, C.byref(h)))
+        return Sequences(self, h)
+
+    def reads_stitch_ranges(self, reads: "Reads", read, start, length, reversed, piece_offsets, form: int = SEQ_BITSET) -> "Sequences":
+        """... of ranges [start, start + length) of reads, reverse-complemented where `reversed` (mdbg_reads_stitch_ranges)."""
+        rg = np.zeros(len(read), SEQ_RANGE)
+        rg["read"], rg["start"], rg["length"], rg["reversed"] = read, start, length, reversed
+        off = np.ascontiguousarray(piece_offsets, np.uint64)
+        h = _P()
+        self.check(lib().mdbg_reads_stitch_ranges(self.h, reads.h, _ptr(rg) if len(rg) else None, _ptr(off), len(off) - 1, form, C.byref(h)))
+        return Sequences(self, h)
+
+    def sequences_to_fasta_bytes(self, seqs: "Sequences", names=None, circular=None) -> "DeviceBytes":
+        """The text CreateBaseContigsFunctor writes for sequences in SEQ_BITSET form: ">ctg<name><l|c>" and the bases, a line each
+        (mdbg_sequences_to_fasta_bytes).  names: the contigs' indices (None: 0, 1, 2 ...); circular: their flags 0 / 1 / 2 (None: 0; 2 is
+        written "c" like 1, as the reference writes it)."""
+        nm = None if names is None else np.ascontiguousarray(names, np.uint32)
+        fl = None if circular is None else np.ascontiguousarray(circular, np.uint8)
+        h, n = _P(), C.c_uint64()
+        self.check(lib().mdbg_sequences_to_fasta_bytes(self.h, seqs.h, None if nm is None or not len(nm) else _ptr(nm), None if fl is None or not len(fl) else _ptr(fl),
+                                                       C.byref(h), C.byref(n)))
+        return DeviceBytes(self, h, n.value)
 
     def memcpy_device(self, dst_ptr: int, src_ptr: int, nbytes: int) -> None:
         self.check(lib().mdbg_memcpy_device(self.h, C.c_void_p(dst_ptr), C.c_void_p(src_ptr), nbytes))
@@ -909,8 +943,30 @@ class Spans:
             pass
 
 
+def stitch_pieces(contigs, window_offsets=None) -> tuple[np.ndarray, np.ndarray]:
+    """(pieces, piece_offsets) for Context.spans_stitch by the rule of CreateBaseContigsFunctor.  contigs: per contig a list of
+    (window, contig_reversed) -- window a flat window index, or (read, window of the read) when window_offsets is given, or None for a
+    window without a stored sequence (skipped, but it still counts as a position).  Window 0 takes SEQ_ENTIRE, a later window SEQ_RIGHT
+    when the contig's window is forward and SEQ_LEFT when it is reversed; flip is the contig window's orientation."""
+    pieces = np.zeros(sum(len(c) for c in contigs), STITCH_PIECE)
+    offsets = np.zeros(len(contigs) + 1, np.uint64)
+    at = 0
+    for c, contig in enumerate(contigs):
+        for i, (window, rev) in enumerate(contig):
+            if window is None:
+                pieces[at] = (STITCH_NONE, 0, 0)
+            else:
+                if window_offsets is not None:
+                    window = int(window_offsets[window[0]]) + int(window[1])
+                pieces[at] = (window, SEQ_ENTIRE if i == 0 else SEQ_LEFT if rev else SEQ_RIGHT, 1 if rev else 0)
+            at += 1
+        offsets[c + 1] = at
+    return pieces, offsets
+
+
 class Sequences:
-    """Sequences cut out of the reads (mdbg_spans_extract / mdbg_reads_extract_ranges)."""
+    """Sequences cut out of the reads (mdbg_spans_extract / mdbg_reads_extract_ranges) or stitched from them (mdbg_spans_stitch /
+    mdbg_reads_stitch_ranges)."""
 
     def __init__(self, ctx: Context, h):
         self.ctx, self.h = ctx, h

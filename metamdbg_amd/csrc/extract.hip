@@ -15,20 +15,11 @@
 //               by doubling steps from the old one (extract_next_owner).  A contig of 5 Mb and 100 000 ranges of 50 bases cost what their
 //               bytes cost (profiles/kminmer_sequences.txt, which also has the first form: a search and three dependent loads per
 //               word, 8-byte stores, two to three times slower).
-// No LDS, no scratch; every buffer comes from the context's pool.
-#include "common.hpp"
-#include "extract_dev.hpp"
-#include "objects.hpp"
+// No LDS, no scratch; every buffer comes from the context's pool.  The result handle and a plan lane's range and checks are in
+// extract_plan.hpp: stitch.hip, which puts contigs together from such ranges, shares them.
+#include "extract_plan.hpp"
 
 #include <memory>
-
-struct mdbg_sequences {
-    uint64_t n = 0, n_bases = 0, n_bytes = 0;
-    int form = 0;
-    mdbg::DevBuf<uint64_t> d_off;       // n + 1: byte offsets, multiples of 8
-    mdbg::DevBuf<uint32_t> d_len;       // n: bases
-    mdbg::DevBuf<uint8_t> d_bytes;      // n_bytes
-};
 
 namespace mdbg {
 
@@ -55,18 +46,9 @@ __device__ __forceinline__ uint32_t plan_emit(uint64_t i, uint32_t why, ExtractR
     return rg.length;
 }
 
-// the bases of all requests: a lane's sum over its trips, summed over the wave, one atomic a wave
-__device__ __forceinline__ void plan_add_bases(unsigned long long mine, unsigned long long *total) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63u) == 0u && mine) atomicAdd(total, mine);
-}
-
 // (window, part) requests: the window's read by a search over the window offsets, the range by extract_part_range
 __global__ __launch_bounds__(256) void extract_plan_kernel(const mdbg_seq_request *req, uint64_t n, uint32_t form, const uint32_t *read_len, uint32_t n_reads,
-                                                           const uint64_t *woff, uint64_t n_windows, const uint32_t *spans_len, const uint8_t *rev,
-                                                           const uint32_t *ps, const uint32_t *pe, const uint32_t *ls, const uint32_t *le,
-                                                           const uint64_t *word_off, ExtractRec *recs, uint32_t *lengths, uint32_t *words,
+                                                           SpansView sp, const uint64_t *word_off, ExtractRec *recs, uint32_t *lengths, uint32_t *words,
                                                            unsigned long long *status) {
     unsigned long long bases = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
@@ -75,15 +57,7 @@ __global__ __launch_bounds__(256) void extract_plan_kernel(const mdbg_seq_reques
         uint32_t why = 0;
         if (q.part > EXTRACT_RIGHT) why = EXTRACT_BAD_PART;
         else if (q.reserved != 0u) why = EXTRACT_BAD_RESERVED;
-        else if (q.window >= n_windows) why = EXTRACT_BAD_WINDOW;
-        else {
-            rg.read = csr_owner(woff, n_reads, q.window);
-            rg.reversed = rev[q.window] ? 1u : 0u;
-            const uint32_t L = read_len[rg.read];
-            if (spans_len[rg.read] != L) why = EXTRACT_BAD_READ_LENGTH;
-            else why = extract_part_range(ps[q.window], pe[q.window], ls[q.window], le[q.window], rg.reversed != 0u, q.part, rg.start, rg.length);
-            if (!why && (uint64_t)rg.start + rg.length > L) why = EXTRACT_BAD_RANGE;
-        }
+        else why = extract_request_range(q.window, q.part, sp, read_len, n_reads, rg);
         bases += plan_emit(i, why, rg, form, word_off, recs, lengths, words, status);
     }
     plan_add_bases(bases, status + 2);
@@ -97,9 +71,7 @@ __global__ __launch_bounds__(256) void extract_plan_ranges_kernel(const mdbg_seq
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
         const mdbg_seq_range q = in[i];
         const ExtractRange rg{q.read, q.start, q.length, q.reversed ? 1u : 0u};
-        uint32_t why = 0;
-        if (q.read >= n_reads) why = EXTRACT_BAD_READ;
-        else if ((uint64_t)q.start + q.length > read_len[q.read]) why = EXTRACT_BAD_RANGE;
+        const uint32_t why = extract_given_range(q.read, q.start, q.length, read_len, n_reads);
         bases += plan_emit(i, why, rg, form, word_off, recs, lengths, words, status);
     }
     plan_add_bases(bases, status + 2);
@@ -108,6 +80,9 @@ __global__ __launch_bounds__(256) void extract_plan_ranges_kernel(const mdbg_seq
 // word offsets -> byte offsets, in place (n + 1 entries)
 __global__ __launch_bounds__(256) void extract_offsets_kernel(uint64_t *off, uint64_t n1) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * 256u) off[i] *= 8u;
+}
+void extract_offsets_to_bytes(mdbg_ctx *ctx, uint64_t *d_off, uint64_t n1) {
+    hipLaunchKernelGGL(extract_offsets_kernel, dim3(grid_for(n1, 256, (unsigned)ctx->n_cu * 32u)), dim3(256), 0, ctx->stream, d_off, n1);
 }
 
 // The request a lane is inside of: its index, its bytes [lo, hi) of the output, its record.
@@ -164,7 +139,7 @@ const StepKernel *extract_step_kernels(uint32_t *n) {
     return k;
 }
 
-static const char *why_text(uint32_t why) {
+const char *extract_why_text(uint32_t why) {
     switch (why) {
         case EXTRACT_BAD_PART: return "its part is none of MDBG_SEQ_ENTIRE / LEFT / RIGHT";
         case EXTRACT_BAD_RESERVED: return "its reserved field is not 0";
@@ -205,19 +180,18 @@ static int extract_run(mdbg_ctx *ctx, const char *who, const mdbg_reads *reads, 
         LaunchTimer timer(ctx, "extract_plan");
         if (n && req)
             hipLaunchKernelGGL(extract_plan_kernel, dim3(grid_for(n, 256, cap)), dim3(256), 0, ctx->stream, reinterpret_cast<const mdbg_seq_request *>(d_in.p), n,
-                               (uint32_t)form, reads->d_len.p, reads->n_reads, spans->d_woff.p, spans->n_windows, spans->d_len.p, spans->d_rev.p, spans->d_ps.p,
-                               spans->d_pe.p, spans->d_ls.p, spans->d_le.p, reads->d_word_off.p, recs.p, sq->d_len.p, words.p, status.p);
+                               (uint32_t)form, reads->d_len.p, reads->n_reads, spans_view(spans), reads->d_word_off.p, recs.p, sq->d_len.p, words.p, status.p);
         else if (n)
             hipLaunchKernelGGL(extract_plan_ranges_kernel, dim3(grid_for(n, 256, cap)), dim3(256), 0, ctx->stream, reinterpret_cast<const mdbg_seq_range *>(d_in.p), n,
                                (uint32_t)form, reads->d_len.p, reads->n_reads, reads->d_word_off.p, recs.p, sq->d_len.p, words.p, status.p);
         MDBG_TRY(exclusive_scan_u32(ctx, words.p, sq->d_off.p, n));
-        hipLaunchKernelGGL(extract_offsets_kernel, dim3(grid_for(n + 1, 256, cap)), dim3(256), 0, ctx->stream, sq->d_off.p, n + 1);
+        extract_offsets_to_bytes(ctx, sq->d_off.p, n + 1);
     }
     MDBG_HIP_CHECK(ctx, hipMemcpyAsync(status.p + 1, sq->d_off.p + n, 8, hipMemcpyDeviceToDevice, ctx->stream));
     unsigned long long verdict[3] = {0, 0, 0};
     MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, verdict, status.p, 24, hipMemcpyDeviceToHost));
     if (verdict[0] != EXTRACT_FINE)
-        return set_error(ctx, MDBG_EINVAL, "%s: request %llu: %s", who, verdict[0] >> 8, why_text((uint32_t)(verdict[0] & 0xFFu)));
+        return set_error(ctx, MDBG_EINVAL, "%s: request %llu: %s", who, verdict[0] >> 8, extract_why_text((uint32_t)(verdict[0] & 0xFFu)));
     sq->n_bytes = verdict[1];
     sq->n_bases = verdict[2];
 

@@ -141,6 +141,10 @@ int exclusive_scan_u32(mdbg_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, uin
     return exclusive_scan_impl<uint32_t>(ctx, d_in, d_out, n);
 }
 
+int exclusive_scan_u64(mdbg_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint64_t n) {
+    return exclusive_scan_impl<uint64_t>(ctx, d_in, d_out, n);
+}
+
 const StepKernel *prims_step_kernels(uint32_t *n) {
     static const StepKernel k[] = {
         {"prefix_reduce", reinterpret_cast<const void *>(scan_reduce_kernel<uint32_t>), SCAN_THREADS, 1},
