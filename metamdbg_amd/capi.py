@@ -639,7 +639,9 @@ class Context:
         h, d_rows = C.c_void_p(), C.c_void_p()
         counts = np.zeros(n_ranks, dtype=np.uint64)
         self.check(lib().mdbg_shard_begin(self.h, m.h, k, n_ranks, C.byref(h), C.byref(d_rows), counts.ctypes.data_as(_u64p)))
-        return Shard(self, h, k, d_rows.value or 0, counts)
+        sh = Shard(self, h, k, d_rows.value or 0, counts)
+        sh.reads = m                             # mdbg_shard_begin: the reads must stay alive until mdbg_shard_free
+        return sh
 
 
 class Census:
