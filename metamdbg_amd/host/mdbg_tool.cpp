@@ -44,35 +44,19 @@
 #include <vector>
 
 #include "../../include/mdbg_hip.h"
+#include "device_text_feed.hpp"
 #include "fastx.hpp"
 #include "hostfeed.hpp"
+#include "ordered_place.hpp"
 #include "records.hpp"
+#include "tool_base.hpp"
 
 namespace {
-
-// _exit, not exit: with --gpus G a failing rank thread ends the process while its peers may sit inside an RCCL collective
-// waiting for it; exit() would run the static destructors of HIP / RCCL under them and can hang, and the parent
-// (Utils::executeCommand, Commons.hpp:2855) only needs the non-zero status.  Output files are flushed as they are written.
-[[noreturn]] void die(const std::string &msg) {
-    fprintf(stderr, "mdbg_tool: %s\n", msg.c_str());
-    fflush(nullptr);
-    _exit(1);
-}
-
-mdbg_ctx *g_ctx = nullptr;
-std::vector<mdbg_ctx *> g_more_ctx;      // the other consumers' contexts (readSelection)
 
 // Every output file is written and closed: the process ends here.  Tearing the HIP contexts and their memory pools down block by
 // block (mdbg_destroy) took 0.2 s of a 2.6 s run over 50 Gbp; the driver reclaims a process's device memory when it exits.
 [[noreturn]] void finish();
 
-// phase timings on stderr when MDBG_TRACE is set
-struct Trace {
-    double t0;
-    static double now() { struct timeval tv; gettimeofday(&tv, nullptr); return tv.tv_sec + 1e-6 * tv.tv_usec; }
-    Trace() : t0(now()) {}
-    void mark(const char *what) { if (getenv("MDBG_TRACE")) fprintf(stderr, "[mdbg_tool] %8.3f s  %s\n", now() - t0, what); }
-} g_trace;
 // The process the caller waits for is a thin launcher (main): this one -- the worker, its child -- tells it through a pipe that every
 // output file is written and closed, and the launcher exits at once with the status byte.  What the worker still has to do then is
 // die: 0.11 - 0.28 s in which the kernel releases its GPU state (tools/exit_cost.py, profiles/round5_k_tool_exit_cost_*.json: whatever
@@ -111,9 +95,6 @@ void signal_done(int status) {
     }
     signal_done(0);
     _exit(0);
-}
-void check(int rc, const char *what) {
-    if (rc != MDBG_OK) die(std::string(what) + ": " + mdbg_last_error(g_ctx));
 }
 
 // Appends to <parent of tmpDir>/metaMDBG.log, the file Tool::openLogFile points the reference's logger at (Commons.hpp:8070-8086).
@@ -244,25 +225,12 @@ std::vector<std::string> read_input_list(const std::string &inputList) {
     return files;
 }
 
-// Feeds `fn` with batches of reads, in read order, from the files of inputList; at most maxReadsPerFile + 1 reads
+// Feeds batches of reads, in read order, from the files of inputList; at most maxReadsPerFile + 1 reads
 // of each file when maxReadsPerFile > 0 (the reference's `_maxReads` check, Commons.hpp:5873).  Parsing runs on
-// `threads` workers into page-locked buffers (hostfeed.hpp) while fn -- upload, kernels, record writing -- runs here.
-void for_each_batch(const std::string &inputList, size_t batchBases, int threads, uint64_t maxReadsPerFile,
-                    const std::function<void(ReadBatch &)> &fn) {
-    auto alloc = [](size_t n) -> void * { void *p = nullptr; return mdbg_host_alloc(g_ctx, n, &p) == MDBG_OK ? p : nullptr; };
-    auto release = [](void *p) { mdbg_host_free(g_ctx, p); };
-    try {
-        mdbg_host::ReadFeeder feeder(read_input_list(inputList), batchBases, threads, maxReadsPerFile, alloc, release);
-        while (ReadBatch *b = feeder.next()) {
-            fn(*b);
-            feeder.recycle(b);
-        }
-    } catch (const std::exception &e) { die(e.what()); }
-}
-
-// The same one batch ahead: stage(b) starts bringing batch i+1 to the device (an upload that runs beside the kernels) before
-// process(handle, b) works on batch i; the batch's page-locked buffer is recycled after process.  The feeder is taken apart on a thread
-// of its own (un-pinning its buffers and unmapping the input are not worth waiting for).
+// `threads` workers into page-locked buffers (hostfeed.hpp) while upload and kernels run here, one batch ahead: stage(b) starts
+// bringing batch i+1 to the device (an upload that runs beside the kernels) before process(handle, b) works on batch i; the batch's
+// page-locked buffer is recycled after process.  The feeder is taken apart on a thread of its own (un-pinning its buffers and
+// unmapping the input are not worth waiting for).
 template <typename Handle>
 void for_each_batch_ahead(const std::string &inputList, size_t batchBases, int threads, uint64_t maxReadsPerFile,
                           const std::function<Handle(ReadBatch &)> &stage, const std::function<void(Handle, ReadBatch &)> &process) {
@@ -286,10 +254,6 @@ void for_each_batch_ahead(const std::string &inputList, size_t batchBases, int t
 }
 
 // a parsed batch -> reads in HBM: 2-bit words when the feeder packed the chunk, ASCII (packed on the device) otherwise
-void check_on(mdbg_ctx *ctx, int rc, const char *what) {
-    if (rc) die(std::string(what) + ": " + mdbg_last_error(ctx));
-}
-
 mdbg_reads *upload_batch(mdbg_ctx *ctx, ReadBatch &b, bool withQual) {
     mdbg_reads *reads = nullptr;
     if (b.packed) {
@@ -303,243 +267,10 @@ mdbg_reads *upload_batch(mdbg_ctx *ctx, ReadBatch &b, bool withQual) {
     return reads;
 }
 
-// ---- MDBG_TOOL_DEVICE_PARSE=1: plain FASTA / FASTQ files travel as text and are taken apart on the device ------------------------
-// (mdbg_reads_from_fastx_bytes); BGZF files travel compressed and are inflated there first (mdbg_bytes_inflate_bgzf).  The symbols are
-// looked up weakly: a library without them (the CPU tests' double) means the host feed.
-extern "C" int mdbg_reads_from_fastx_bytes(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, mdbg_reads **out, uint64_t info[4])
-    __attribute__((weak));
-extern "C" int mdbg_bytes_inflate_bgzf(mdbg_ctx *ctx, const mdbg_bytes *comp, const mdbg_bgzf_block *blocks, uint64_t n_blocks, mdbg_bytes *text, uint64_t text_at,
-                                       uint64_t *n_text) __attribute__((weak));
-extern "C" int mdbg_bytes_download(mdbg_ctx *ctx, const mdbg_bytes *b, uint64_t at, void *host, uint64_t n) __attribute__((weak));
-extern "C" int mdbg_fastx_whole_records(mdbg_ctx *ctx, const mdbg_bytes *text, uint64_t begin, uint64_t end, uint64_t *cut, int *format) __attribute__((weak));
-// gzip that is not BGZF: cut into chunks at deflate block headers found here (mdbg_host::gzip_find_block) and inflated on the device
-extern "C" int mdbg_gzip_stream_create(mdbg_ctx *ctx, mdbg_gzip_stream **out) __attribute__((weak));
-extern "C" void mdbg_gzip_stream_free(mdbg_gzip_stream *s) __attribute__((weak));
-extern "C" int mdbg_bytes_inflate_gzip(mdbg_ctx *ctx, mdbg_gzip_stream *s, const mdbg_bytes *comp, const mdbg_gzip_chunk *chunks, uint64_t n_chunks, mdbg_bytes *text,
-                                       uint64_t text_at, uint64_t *n_text, uint64_t info[4]) __attribute__((weak));
-extern "C" int mdbg_bytes_copy(mdbg_ctx *ctx, mdbg_bytes *dst, uint64_t dst_at, const mdbg_bytes *src, uint64_t src_at, uint64_t n) __attribute__((weak));
-
 // ---- MDBG_TOOL_DEVICE_RECORDS=1: the record bytes of read_data_init.txt and read_data_corrected.txt are composed on the device --------
 // (mdbg_minimizers_to_record_bytes) and come back ready to be written; without it, or with a library that lacks the symbol (the CPU
 // tests' double), builder threads put them together from the eight arrays of a batch.
 extern "C" int mdbg_minimizers_to_record_bytes(mdbg_ctx *ctx, const mdbg_minimizers *m, int form, mdbg_bytes **out, uint64_t *n_bytes) __attribute__((weak));
-
-struct DeviceParsePlan {
-    // a BGZF file: its mapping, its block table (BgzfReader::index) and the text offset of every block
-    struct Bgzf {
-        std::string path;
-        const unsigned char *addr = nullptr;
-        std::vector<mdbg_host::BgzfReader::Block> blocks;
-        std::vector<uint64_t> cum;
-    };
-    // A gzip file that is not BGZF: worker threads look for one deflate block header per `chunk` bytes of the file (start[k]: the first
-    // header in chunk k, NONE: none found; start[0] is the file's first member header) and run ahead of the consumers, which inflate
-    // groups of chunks on the device (mdbg_bytes_inflate_gzip) and carry the unfinished record from slab to slab.
-    struct Gzip {
-        static constexpr uint64_t NONE = mdbg_host::GZIP_NONE;
-        std::string path;
-        const unsigned char *addr = nullptr;
-        size_t size = 0, chunk = 65536, nChunks = 0;
-        std::vector<uint64_t> start;
-        std::vector<char> known;
-        std::mutex mu;
-        std::condition_variable cv;
-        std::atomic<size_t> nextSearch{0};
-        std::vector<std::thread> workers;
-        // where the consumers stand (under the feed's lock)
-        mdbg_gzip_stream *stream = nullptr;
-        uint64_t atBit = 0;             // the next call's first start
-        size_t nextK = 1;               // the first chunk whose header may lie behind atBit
-        mdbg_bytes *rest = nullptr;     // the unfinished record behind the last slab's cut
-        uint64_t nRest = 0;
-        bool ended = false;
-        uint64_t nCalls = 0, nChunksInflated = 0;
-
-        void search(size_t k) {
-            mdbg_host::InflaterT<uint16_t> probe;
-            std::vector<uint16_t> scratch;
-            const uint64_t found = mdbg_host::gzip_find_block(addr, addr + size, (uint64_t)k * chunk * 8, (uint64_t)(k + 1) * chunk * 8, probe, scratch);
-            std::lock_guard<std::mutex> g(mu);
-            start[k] = found;
-            known[k] = 1;
-            cv.notify_all();
-        }
-        void run_workers(int threads) {
-            for (int t = 0; t < threads; t++)
-                workers.emplace_back([this] {
-                    mdbg_host::InflaterT<uint16_t> probe;
-                    std::vector<uint16_t> scratch;
-                    for (;;) {
-                        const size_t k = nextSearch.fetch_add(1);
-                        if (k >= nChunks) return;
-                        const uint64_t found = mdbg_host::gzip_find_block(addr, addr + size, (uint64_t)k * chunk * 8, (uint64_t)(k + 1) * chunk * 8, probe, scratch);
-                        std::lock_guard<std::mutex> g(mu);
-                        start[k] = found;
-                        known[k] = 1;
-                        cv.notify_all();
-                    }
-                });
-        }
-        uint64_t wait_start(size_t k) {
-            std::unique_lock<std::mutex> g(mu);
-            cv.wait(g, [&] { return known[k] != 0; });
-            return start[k];
-        }
-        void join() { for (auto &t : workers) t.join(); workers.clear(); }
-    };
-    struct Slab { const char *p; size_t n; int file; int bgzf; int gz; };        // bgzf >= 0: the whole of bgzfs[bgzf], gz >= 0: of gzips[gz], cut into slabs as it is inflated
-    std::vector<Slab> slabs;            // whole records each, in read order
-    std::vector<Bgzf> bgzfs;
-    std::vector<std::unique_ptr<Gzip>> gzips;
-    size_t maxSlab = 0;
-    std::vector<std::pair<void *, size_t>> maps;
-
-    // The first blocks of a BGZF file inflated on the host, until 256 records or 1 MB of text: what the plain files' checks look at.
-    // false: a block of the prefix does not inflate
-    static bool bgzf_prefix(const Bgzf &z, std::string &text) {
-        mdbg_host::Inflater inf;
-        std::vector<uint8_t> buf(65536 + 512);            // the decoder wants Inflater::MIN_ROOM bytes of room in front of every symbol
-        size_t lines = 0, headers = 0;
-        for (size_t b = 0; b < z.blocks.size() && text.size() < ((size_t)1 << 20) && headers <= 256 && lines < 4 * 256 + 4; b++) {
-            const auto &blk = z.blocks[b];
-            inf.reset(z.addr + blk.payload, z.addr + blk.payload + blk.csize);
-            size_t produced = 0;
-            if (inf.run(buf.data(), buf.data() + buf.size(), 0, &produced) != mdbg_host::Inflater::STREAM_END || produced != blk.isize) return false;
-            for (size_t i = 0; i < produced; i++) {
-                if (buf[i] == '\n') lines++;
-                if (buf[i] == '>' && (i ? buf[i - 1] == '\n' : text.empty() || text.back() == '\n')) headers++;
-            }
-            text.append((const char *)buf.data(), produced);
-        }
-        return true;
-    }
-
-    // The first member of a gzip file inflated on the host, until 1 MB of text: what the plain files' checks look at.  false: it does not inflate
-    static bool gzip_prefix(const unsigned char *addr, size_t size, std::string &text) {
-        const size_t h = mdbg_host::gzip_header_size(addr, size);
-        if (!h) return false;
-        mdbg_host::Inflater inf;
-        std::vector<uint8_t> buf(((size_t)1 << 20) + 512);
-        inf.reset(addr + h, addr + size);
-        size_t produced = 0;
-        if (inf.run(buf.data(), buf.data() + buf.size(), 0, &produced) == mdbg_host::Inflater::CORRUPT) return false;
-        text.assign((const char *)buf.data(), produced);
-        return true;
-    }
-    // a gzip file that is not BGZF joins the plan; false: `why` says what stands against it
-    bool add_gzip(const std::string &path, const unsigned char *addr, size_t size, int file, int threads, int gpus, std::string &why) {
-        if (!mdbg_bytes_inflate_gzip || !mdbg_gzip_stream_create || !mdbg_gzip_stream_free || !mdbg_bytes_copy) { why = path + " is gzip but not BGZF and the library has no mdbg_bytes_inflate_gzip"; return false; }
-        if (gpus > 1) { why = path + " is gzip but not BGZF: its chunks are inflated on one device, and --gpus is " + std::to_string(gpus); return false; }
-        std::string head;
-        if (!gzip_prefix(addr, size, head)) { why = path + " is gzip but not BGZF and its first member does not inflate"; return false; }
-        if (head.empty()) { why = path + " is gzip but not BGZF and begins with an empty member"; return false; }
-        const bool fastq = head[0] == '@';
-        if (!fastq && head[0] != '>') { why = path + " does not begin with '>' or '@'"; return false; }
-        if (fastq && !mdbg_host::ReadFeeder::fastq_is_four_line(head.data(), head.data() + head.size())) { why = path + " is not four-line FASTQ, which the device parse refuses"; return false; }
-        std::unique_ptr<Gzip> g(new Gzip());
-        g->path = path; g->addr = addr; g->size = size;
-        if (const char *e = getenv("MDBG_TOOL_GZIP_CHUNK_KB")) g->chunk = (size_t)std::max(16, atoi(e)) << 10;
-        g->nChunks = (size + g->chunk - 1) / g->chunk;
-        g->start.assign(g->nChunks, Gzip::NONE);
-        g->known.assign(g->nChunks, 0);
-        g->start[0] = 0; g->known[0] = 1;
-        // a stream of stored blocks has no header the search finds, and would decode on one wave: the host feed takes it
-        if (g->nChunks > 2) {
-            g->search(1); g->search(2);
-            if (g->start[1] == Gzip::NONE && g->start[2] == Gzip::NONE) {
-                why = path + " is gzip but not BGZF, and no deflate block header is to be found in its second and third chunk (stored blocks, or members of one block): it would inflate on one wave of the device";
-                return false;
-            }
-        }
-        // A call of few chunks occupies a fraction of the device's waves and still pays a whole chunk's latency on one lane (DESIGN.md
-        // 4.3c, 6): a file of fewer than 32 chunks is left to the host feed, which has it decoded before the first call would return.
-        if (g->nChunks < 32) {
-            why = path + " is gzip but not BGZF and holds " + std::to_string(g->nChunks) + " chunk(s) of " + std::to_string(g->chunk >> 10) +
-                  " KB: fewer than the 32 from which the device takes a gzip file";
-            return false;
-        }
-        g->nextSearch = g->nChunks > 2 ? 3 : 1;
-        g->run_workers(std::max(1, std::min(threads, 16)));
-        slabs.push_back(Slab{nullptr, 0, file, -1, (int)gzips.size()});
-        gzips.push_back(std::move(g));
-        return true;
-    }
-
-    // true: every file of the list is plain text, pure BGZF or ordinary gzip that begins with '>' or '@' (FASTQ: four lines a record).  Plain files are
-    // mapped and cut at record starts by the feeder's own search into slabs of at most batchBases bytes; a BGZF file is one entry that
-    // the consumers cut as its text appears on the device.  false: `why` says what stands against it
-    bool make(const std::vector<std::string> &files, size_t batchBases, int threads, int gpus, std::string &why) {
-        using mdbg_host::ReadFeeder;
-        if (!mdbg_reads_from_fastx_bytes) { why = "the library has no mdbg_reads_from_fastx_bytes"; return false; }
-        for (size_t f = 0; f < files.size(); f++) {
-            const std::string &path = files[f];
-            const bool gz = ReadFeeder::file_is_gzip(path);
-            if (gz && (!mdbg_bytes_inflate_bgzf || !mdbg_bytes_download || !mdbg_fastx_whole_records)) {
-                why = path + " is compressed and the library has no mdbg_bytes_inflate_bgzf, mdbg_bytes_download or mdbg_fastx_whole_records";
-                return false;
-            }
-            const int fd = open(path.c_str(), O_RDONLY);
-            if (fd < 0) die("File not found: " + path);
-            struct stat st;
-            fstat(fd, &st);
-            if (st.st_size == 0) { close(fd); continue; }
-            const char *addr = (const char *)mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-            close(fd);
-            if (addr == MAP_FAILED) die("mmap failed: " + path);
-            madvise((void *)addr, (size_t)st.st_size, MADV_SEQUENTIAL);
-            maps.emplace_back((void *)addr, (size_t)st.st_size);
-            if (gz) {
-                Bgzf z;
-                z.path = path;
-                z.addr = (const unsigned char *)addr;
-                if (!mdbg_host::BgzfReader::index(z.addr, (size_t)st.st_size, z.blocks)) {
-                    if (!add_gzip(path, z.addr, (size_t)st.st_size, (int)f, threads, gpus, why)) return false;
-                    continue;
-                }
-                z.cum.assign(z.blocks.size() + 1, 0);
-                for (size_t i = 0; i < z.blocks.size(); i++) z.cum[i + 1] = z.cum[i] + z.blocks[i].isize;
-                if (z.cum.back() == 0) continue;                        // nothing but empty blocks: no reads
-                std::string head;
-                if (!bgzf_prefix(z, head)) { why = path + " has a BGZF block among its first that does not inflate"; return false; }
-                const bool fastq = head[0] == '@';
-                if (!fastq && head[0] != '>') { why = path + " does not begin with '>' or '@'"; return false; }
-                if (fastq && !ReadFeeder::fastq_is_four_line(head.data(), head.data() + head.size())) {
-                    why = path + " is not four-line FASTQ, which the device parse refuses";
-                    return false;
-                }
-                slabs.push_back(Slab{nullptr, 0, (int)f, (int)bgzfs.size(), -1});
-                bgzfs.push_back(std::move(z));
-                continue;
-            }
-            const char *end = addr + st.st_size;
-            const bool fastq = *addr == '@';
-            if (!fastq && *addr != '>') { why = path + " does not begin with '>' or '@'"; return false; }
-            if (fastq && !ReadFeeder::fastq_is_four_line(addr, end)) { why = path + " is not four-line FASTQ, which the device parse refuses"; return false; }
-            for (const char *p = addr; p < end;) {
-                const char *q = end;
-                if ((size_t)(end - p) > batchBases) {
-                    q = ReadFeeder::cut_at_record_start(p, p + batchBases, end, fastq);
-                    if (q == p) die("a single read is larger than the batch size; raise --batch-bases");
-                }
-                slabs.push_back(Slab{p, (size_t)(q - p), (int)f, -1, -1});
-                maxSlab = std::max(maxSlab, (size_t)(q - p));
-                p = q;
-            }
-        }
-        return true;
-    }
-    void unmap() {
-        for (auto &g : gzips) {
-            g->nextSearch = g->nChunks;                 // (a plan given up: the searches end with the chunk they are in)
-            g->join();
-            if (g->rest) mdbg_bytes_free(g->rest);
-            if (g->stream) mdbg_gzip_stream_free(g->stream);
-            g->rest = nullptr; g->stream = nullptr;
-        }
-        for (auto &m : maps) munmap(m.first, m.second);
-        maps.clear();
-    }
-};
 
 mdbg_scan_params scan_params(const Parameters &P, float density, const std::vector<uint32_t> &rep, float minQ, bool filters) {
     mdbg_scan_params p{};
@@ -556,241 +287,240 @@ mdbg_scan_params scan_params(const Parameters &P, float density, const std::vect
 [[noreturn]] void graph_main(Args a, const std::string &dir, mdbg_minimizers *resident);
 
 // ---- readSelection --------------------------------------------------------------------------------------------
-// (asmStep = true: `mdbg_tool asmStep <the arguments of readSelection> [--min-abundance M]` -- this command and `graph --firstpass` in ONE
-// process: the reference's pipeline runs them as two children one after the other, pipeline/AssemblyPipeline.hpp:716-740 and :763-792; here the
-// second finds the library context alive and the corrected minimizers still on the device instead of creating one and parsing
-// read_data_corrected.txt back.  Every file of both commands is written as by the two of them.)
-int run_read_selection(int argc, char **argv, bool asmStep = false) {
-    Args a = parse_args(argc, argv, 2);
-    a.thenGraph = asmStep;
-    if (a.pos.size() != 3) die(std::string("usage: mdbg_tool ") + (asmStep ? "asmStep" : "readSelection") + " <tmpDir> <outFile> <inputList> --threads N --min-read-quality F [--skip-correction]" +
-                               (asmStep ? " [--min-abundance M]" : ""));
-    if (asmStep && a.gpus > 1) die("asmStep runs on one device; with --gpus G use the two commands readSelection and graph");
-    const std::string tmpDir = a.pos[0], outFile = a.pos[1], inputList = a.pos[2];
-    Parameters P;
-    P.load(tmpDir + "/parameters.gz");
-    g_log.open(tmpDir);
-    g_log.line("mdbg_tool readSelection (MI355X) " + inputList);
-    check(mdbg_create(0, &g_ctx), "mdbg_create");
-    g_trace.mark("context created");
+// The stages, in the order run_read_selection (below them) goes through them: census_repetitive, the main pass (consumers scan the
+// batches, a RecordSink writes read_data_init.txt and counts), write_read_stats, the PurgePass, hand_over_to_graph.
 
-    // repetitive minimizers (ReadSelection.hpp:497-561): HiFi writes an empty file
+// repetitive minimizers (ReadSelection.hpp:497-561): HiFi writes an empty file.  Returns them
+std::vector<uint32_t> census_repetitive(const Parameters &P, const Args &a, const std::string &tmpDir, const std::string &inputList) {
     std::vector<uint32_t> rep;
-    {
-        std::ofstream repFile(tmpDir + "/repetitiveMinimizers.bin", std::ios::binary);
-        if (!P.hpc) {
-            // every batch's minimizer values are counted where they are (mdbg_census_*): nothing but the pick comes back
-            mdbg_census *census = nullptr;
-            check(mdbg_census_create(g_ctx, &census), "mdbg_census_create");
-            // (the census scan never looks at qualities -- CountMinimizerFunctor, ReadSelection.hpp:565-625 -- so they do not travel)
-            for_each_batch_ahead<mdbg_reads *>(inputList, a.batchBases, a.threads, 1000000,
-                [&](ReadBatch &b) -> mdbg_reads * {
-                    mdbg_reads *reads = nullptr;
-                    if (b.packed) {
-                        check(mdbg_reads_from_packed_async(g_ctx, b.words(), b.wordOff.data(), b.lens.data(), b.n(), &reads), "mdbg_reads_from_packed_async");
-                        if (!b.odd.empty())
-                            check(mdbg_reads_mark_ascii(g_ctx, reads, b.odd.data(), (uint32_t)b.odd.size(), b.oddBases.data(), b.oddOff.data()), "mdbg_reads_mark_ascii");
-                    } else reads = upload_batch(g_ctx, b, false);
-                    return reads;
-                },
-                [&](mdbg_reads *reads, ReadBatch &) {
-                    mdbg_minimizers *mins = nullptr;
-                    mdbg_scan_params p = scan_params(P, P.densityCorrection, {}, 0, false);
-                    check(mdbg_scan(g_ctx, reads, &p, &mins), "mdbg_scan");
-                    check(mdbg_census_add(g_ctx, census, mins), "mdbg_census_add");
-                    mdbg_minimizers_free(mins);
-                    check(mdbg_reads_wait(g_ctx, reads), "mdbg_reads_wait");       // before the batch's buffer is recycled
-                    mdbg_reads_free(reads);
-                });
-            g_trace.mark("census done");
-            uint32_t cap = 1u << 16;
-            rep.resize(cap);
-            check(mdbg_census_top(g_ctx, census, rep.data(), &cap), "mdbg_census_top");
-            rep.resize(cap);
-            mdbg_census_free(census);
-            // test hook: ties among equally frequent minimizers are broken arbitrarily by the reference
-            // (std::sort on counts, ReadSelection.hpp:522-524); a fixture can pin the reference's pick
-            if (const char *forced = getenv("MDBG_TOOL_REPETITIVE")) {
-                std::vector<uint8_t> raw = read_file(forced);
-                rep.assign(raw.size() / 4, 0);
-                if (!raw.empty()) memcpy(rep.data(), raw.data(), rep.size() * 4);
-            }
-            repFile.write((const char *)rep.data(), (std::streamsize)(rep.size() * 4));
+    std::ofstream repFile(tmpDir + "/repetitiveMinimizers.bin", std::ios::binary);
+    if (!P.hpc) {
+        // every batch's minimizer values are counted where they are (mdbg_census_*): nothing but the pick comes back
+        mdbg_census *census = nullptr;
+        check(mdbg_census_create(g_ctx, &census), "mdbg_census_create");
+        // (the census scan never looks at qualities -- CountMinimizerFunctor, ReadSelection.hpp:565-625 -- so they do not travel)
+        for_each_batch_ahead<mdbg_reads *>(inputList, a.batchBases, a.threads, 1000000,
+            [&](ReadBatch &b) -> mdbg_reads * {
+                mdbg_reads *reads = nullptr;
+                if (b.packed) {
+                    check(mdbg_reads_from_packed_async(g_ctx, b.words(), b.wordOff.data(), b.lens.data(), b.n(), &reads), "mdbg_reads_from_packed_async");
+                    if (!b.odd.empty())
+                        check(mdbg_reads_mark_ascii(g_ctx, reads, b.odd.data(), (uint32_t)b.odd.size(), b.oddBases.data(), b.oddOff.data()), "mdbg_reads_mark_ascii");
+                } else reads = upload_batch(g_ctx, b, false);
+                return reads;
+            },
+            [&](mdbg_reads *reads, ReadBatch &) {
+                mdbg_minimizers *mins = nullptr;
+                mdbg_scan_params p = scan_params(P, P.densityCorrection, {}, 0, false);
+                check(mdbg_scan(g_ctx, reads, &p, &mins), "mdbg_scan");
+                check(mdbg_census_add(g_ctx, census, mins), "mdbg_census_add");
+                mdbg_minimizers_free(mins);
+                check(mdbg_reads_wait(g_ctx, reads), "mdbg_reads_wait");       // before the batch's buffer is recycled
+                mdbg_reads_free(reads);
+            });
+        g_trace.mark("census done");
+        uint32_t cap = 1u << 16;
+        rep.resize(cap);
+        check(mdbg_census_top(g_ctx, census, rep.data(), &cap), "mdbg_census_top");
+        rep.resize(cap);
+        mdbg_census_free(census);
+        // test hook: ties among equally frequent minimizers are broken arbitrarily by the reference
+        // (std::sort on counts, ReadSelection.hpp:522-524); a fixture can pin the reference's pick
+        if (const char *forced = getenv("MDBG_TOOL_REPETITIVE")) {
+            std::vector<uint8_t> raw = read_file(forced);
+            rep.assign(raw.size() / 4, 0);
+            if (!raw.empty()) memcpy(rep.data(), raw.data(), rep.size() * 4);
         }
-        repFile.close();
-        if (!repFile) die("writing " + tmpDir + "/repetitiveMinimizers.bin failed");
+        repFile.write((const char *)rep.data(), (std::streamsize)(rep.size() * 4));
     }
+    repFile.close();
+    if (!repFile) die("writing " + tmpDir + "/repetitiveMinimizers.bin failed");
+    return rep;
+}
 
-    // main pass: read_data_init.txt in read order (ReadSelection.hpp:386-491)
-    const int outFd = open(outFile.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    if (outFd < 0) die("cannot write " + outFile);
-    std::vector<uint32_t> allReadSizes;
-    uint64_t nbKmers = 0, nbBases = 0, nbSelected = 0;
-    long double qualitySum = 0, qualityN = 0;
-    const bool needCorrected = P.hpc || a.skipCorrection;
-    if (a.thenGraph && !needCorrected) die("asmStep: without --skip-correction an ONT read set goes through the reference's read correction before `graph` (not part of this tool)");
-    std::vector<std::pair<size_t, mdbg_minimizers *>> purgedResident;     // asmStep: the purged groups, by the number of their first batch (guarded by fifoMu)
-    // Batches are turned into host arrays by consumer threads, each with its own library context (stream, pool), so the
-    // upload of one batch can overlap the scan and the download of another; a writer thread builds the records and
-    // writes them in batch order while later batches are on the device.  One consumer is the default: at 28 GB/s of
-    // FASTA the pass is bound by the parser workers and the page-locked buffers, and a second consumer measured no
-    // faster (profiles/r01f_tool_consumers.json); MDBG_TOOL_CONSUMERS=2..4 is there for slower-to-scan inputs.
-    // the arrays of one batch in ONE page-locked slab (the download is plain DMA, nothing is zero-filled); slabs go round between
-    // the consumers and the writer
-    struct HostBatch {
-        uint64_t seq = 0;
-        uint32_t n = 0; uint64_t t = 0;
-        char *slab = nullptr; size_t cap = 0;
-        uint64_t *off = nullptr; uint32_t *m = nullptr, *pos = nullptr, *len = nullptr; uint8_t *dir = nullptr, *qual = nullptr, *flags = nullptr; float *meanQ = nullptr;
-        char *rec = nullptr;                     // device records: the batch's (the group's) record bytes as they go to the file; m, pos, dir, qual are absent then
-        void room(size_t need) {
-            if (need <= cap) return;
-            if (slab) mdbg_host_free(g_ctx, slab);
-            cap = need + need / 4;
-            void *p = nullptr;
-            check(mdbg_host_alloc(g_ctx, cap, &p), "mdbg_host_alloc");
-            slab = (char *)p;
-        }
-        // device records, main pass: the per-read arrays the statistics need and `bytes` of records
-        void shape_init_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
-            n = n_; t = t_;
-            room(((size_t)n + 1) * 8 + (size_t)n * 8 + (((size_t)n + 7) & ~(size_t)7) + bytes + 64);
-            char *q = slab;
-            off = (uint64_t *)q; q += ((size_t)n + 1) * 8;
-            len = (uint32_t *)q; q += (size_t)n * 4;
-            meanQ = (float *)q; q += (size_t)n * 4;
-            flags = (uint8_t *)q; q += ((size_t)n + 7) & ~(size_t)7;
-            rec = q;
-            m = pos = nullptr; dir = qual = nullptr;
-        }
-        // device records, purge pass: offsets and `bytes` of records
-        void shape_plain_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
-            n = n_; t = t_;
-            room(((size_t)n + 1) * 8 + bytes + 64);
-            off = (uint64_t *)slab;
-            rec = slab + ((size_t)n + 1) * 8;
-            m = pos = len = nullptr; dir = qual = flags = nullptr; meanQ = nullptr;
-        }
-        void shape(uint32_t n_, uint64_t t_) {
-            n = n_; t = t_; rec = nullptr;
-            const size_t need = ((size_t)n + 1) * 8 + t * 8 + (size_t)n * 8 + ((t + 7) & ~(size_t)7) * 2 + (((size_t)n + 7) & ~(size_t)7) + 64;
-            if (need > cap) {
-                if (slab) mdbg_host_free(g_ctx, slab);
-                cap = need + need / 4;
-                void *p = nullptr;
-                check(mdbg_host_alloc(g_ctx, cap, &p), "mdbg_host_alloc");
-                slab = (char *)p;
-            }
-            char *q = slab;
-            off = (uint64_t *)q; q += ((size_t)n + 1) * 8;
-            m = (uint32_t *)q; q += t * 4;
-            pos = (uint32_t *)q; q += t * 4;
-            len = (uint32_t *)q; q += (size_t)n * 4;
-            meanQ = (float *)q; q += (size_t)n * 4;
-            dir = (uint8_t *)q; q += (t + 7) & ~(size_t)7;
-            qual = (uint8_t *)q; q += (t + 7) & ~(size_t)7;
-            flags = (uint8_t *)q;
-        }
-        // offsets and values only (the purge pass)
-        void shape_values(uint32_t n_, uint64_t t_) {
-            n = n_; t = t_; rec = nullptr;
-            const size_t need = ((size_t)n + 1) * 8 + t * 4 + 64;
-            if (need > cap) {
-                if (slab) mdbg_host_free(g_ctx, slab);
-                cap = need + need / 4;
-                void *p = nullptr;
-                check(mdbg_host_alloc(g_ctx, cap, &p), "mdbg_host_alloc");
-                slab = (char *)p;
-            }
-            off = (uint64_t *)slab;
-            m = (uint32_t *)(slab + ((size_t)n + 1) * 8);
-            pos = len = nullptr; dir = qual = flags = nullptr; meanQ = nullptr;
-        }
-    };
-    std::vector<HostBatch *> spareBatches;        // guarded by fifoMu
+// the arrays of one batch in ONE page-locked slab (the download is plain DMA, nothing is zero-filled); slabs go round between
+// the consumers and the writer
+struct HostBatch {
+    uint64_t seq = 0;
+    uint32_t n = 0; uint64_t t = 0;
+    char *slab = nullptr; size_t cap = 0;
+    uint64_t *off = nullptr; uint32_t *m = nullptr, *pos = nullptr, *len = nullptr; uint8_t *dir = nullptr, *qual = nullptr, *flags = nullptr; float *meanQ = nullptr;
+    char *rec = nullptr;                     // device records: the batch's (the group's) record bytes as they go to the file; m, pos, dir, qual are absent then
+    void room(size_t need) {
+        if (need <= cap) return;
+        if (slab) mdbg_host_free(g_ctx, slab);
+        cap = need + need / 4;
+        void *p = nullptr;
+        check(mdbg_host_alloc(g_ctx, cap, &p), "mdbg_host_alloc");
+        slab = (char *)p;
+    }
+    // device records, main pass: the per-read arrays the statistics need and `bytes` of records
+    void shape_init_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
+        n = n_; t = t_;
+        room(((size_t)n + 1) * 8 + (size_t)n * 8 + (((size_t)n + 7) & ~(size_t)7) + bytes + 64);
+        char *q = slab;
+        off = (uint64_t *)q; q += ((size_t)n + 1) * 8;
+        len = (uint32_t *)q; q += (size_t)n * 4;
+        meanQ = (float *)q; q += (size_t)n * 4;
+        flags = (uint8_t *)q; q += ((size_t)n + 7) & ~(size_t)7;
+        rec = q;
+        m = pos = nullptr; dir = qual = nullptr;
+    }
+    // device records, purge pass: offsets and `bytes` of records
+    void shape_plain_records(uint32_t n_, uint64_t t_, uint64_t bytes) {
+        n = n_; t = t_;
+        room(((size_t)n + 1) * 8 + bytes + 64);
+        off = (uint64_t *)slab;
+        rec = slab + ((size_t)n + 1) * 8;
+        m = pos = len = nullptr; dir = qual = flags = nullptr; meanQ = nullptr;
+    }
+    void shape(uint32_t n_, uint64_t t_) {
+        n = n_; t = t_; rec = nullptr;
+        room(((size_t)n + 1) * 8 + t * 8 + (size_t)n * 8 + ((t + 7) & ~(size_t)7) * 2 + (((size_t)n + 7) & ~(size_t)7) + 64);
+        char *q = slab;
+        off = (uint64_t *)q; q += ((size_t)n + 1) * 8;
+        m = (uint32_t *)q; q += t * 4;
+        pos = (uint32_t *)q; q += t * 4;
+        len = (uint32_t *)q; q += (size_t)n * 4;
+        meanQ = (float *)q; q += (size_t)n * 4;
+        dir = (uint8_t *)q; q += (t + 7) & ~(size_t)7;
+        qual = (uint8_t *)q; q += (t + 7) & ~(size_t)7;
+        flags = (uint8_t *)q;
+    }
+    // offsets and values only (the purge pass)
+    void shape_values(uint32_t n_, uint64_t t_) {
+        n = n_; t = t_; rec = nullptr;
+        room(((size_t)n + 1) * 8 + t * 4 + 64);
+        off = (uint64_t *)slab;
+        m = (uint32_t *)(slab + ((size_t)n + 1) * 8);
+        pos = len = nullptr; dir = qual = flags = nullptr; meanQ = nullptr;
+    }
+};
+
+// the purge pass works on groups of so many consecutive batches (see PurgePass)
+constexpr size_t GROUP = 32;
+
+// What the stages of readSelection share.  ONE lock and ONE condition variable serve every thread of the command -- consumers, record
+// builders, the statistics thread, the group-slab helper, purgers and the second pass's writers; whoever changes what another thread may
+// be waiting for (here, in the RecordSink or in the PurgePass, whose queues `mu` guards too) notifies all.
+struct SelectionShared {
+    // settled before the first thread starts
+    std::vector<mdbg_ctx *> ctxs;                 // one per consumer; the purge pass purges a batch where it was scanned
+    int nConsumers = 1;
+    bool deviceRecords = false;                   // MDBG_TOOL_DEVICE_RECORDS and a library that can
+    bool needCorrected = false;                   // HiFi or --skip-correction: read_data_corrected.txt is written here
+    size_t groupSlabsWanted = 0;
+
+    std::mutex mu;
+    std::condition_variable cv;
+    // guarded by mu
+    std::vector<HostBatch *> spareBatches;        // slabs that went through the statistics thread and serve a later batch
+    std::vector<HostBatch *> groupSlabs;
+    struct Kept { uint64_t seq; mdbg_ctx *ctx; mdbg_minimizers *mins; };
+    std::vector<Kept> kept;                       // device-resident minimizer reads, purged once N50 is known
+    std::vector<std::pair<size_t, mdbg_minimizers *>> purgedResident;     // asmStep: the purged groups, by the number of their first batch
+
     // The purge pass copies GROUPS of batches back (see there), each into one slab several times a batch's: taking the main pass's slabs
     // and growing them on the way (free + allocate page-locked memory, 2 - 4 ms a time) was 0.11 s of the 0.19 s the pass took over 50 Gbp.
-    // A helper allocates them beside the main pass, as soon as the first batch has shown how large a batch is.
-    constexpr size_t GROUP = 32;
-    std::vector<HostBatch *> groupSlabs;          // guarded by fifoMu
+    // A helper allocates them beside the main pass, as soon as the first batch has shown how large a batch is (bn reads, bt minimizers).
     std::atomic<bool> groupSlabsStop{false};
     std::thread groupSlabHelper;
     std::once_flag groupSlabOnce;
-    struct Kept { uint64_t seq; mdbg_ctx *ctx; mdbg_minimizers *mins; };
-    std::vector<Kept> kept;                 // device-resident minimizer reads, purged once N50 is known
-    // --gpus G: one consumer per device; batches go to the consumers in turn, every batch is scanned (and later purged) where it
-    // landed, and the ordered writer, N50 and read_stats.txt see the batches in read order whatever device produced them
-    // (contiguous read ranges, stats reduced on the host).
-    // two consumers per device by default: with the parsers packing on 12 threads it is the consumer -- upload, scan, download, hand-over,
-    // per batch of a few thousand reads -- that a 50 Gbp pass waits for (round 3: the parsers were idle 60 % of the time)
-    int nConsumers = std::max(1, a.gpus) * (a.threads >= 8 ? 2 : 1);
-    if (const char *e = getenv("MDBG_TOOL_CONSUMERS")) nConsumers = std::max(std::max(1, a.gpus), std::min(4 * std::max(1, a.gpus), atoi(e)));
-    // how many: what the purge pass can have in flight (six groups' pieces waiting for the writers, one being filled, per consumer) --
-    // of a long input.  A short one (10 Gbp: ten groups) gets a third of its groups' worth: pinning 200 MB beside a main pass of
-    // 0.25 s measured no faster than growing slabs on the way (0.53 against 0.50 s inside the tool, ten runs each, noise as large)
-    size_t groupSlabsWanted = 0;
-    {
-        uint64_t inputBytes = 0;
-        for (const std::string &f : read_input_list(inputList)) { struct stat st; if (stat(f.c_str(), &st) == 0) inputBytes += (uint64_t)st.st_size; }
-        const uint64_t groups = inputBytes / ((uint64_t)std::max<size_t>(1, a.batchBases) * GROUP);
-        groupSlabsWanted = (size_t)std::min<uint64_t>(7 * (uint64_t)nConsumers + 2, groups * (uint64_t)nConsumers / 3);
+    void start_group_slab_helper(uint32_t bn, uint64_t bt) {
+        std::call_once(groupSlabOnce, [this, bn, bt] {
+            // a consumer's share of a group (batches are handed out as consumers come free: a little more than GROUP / consumers)
+            const size_t share = GROUP / (size_t)nConsumers + 2;
+            const uint64_t rn = (uint64_t)share * bn, rt = (uint64_t)share * bt;
+            groupSlabHelper = std::thread([this, rn, rt] {
+                for (size_t i = 0; i < groupSlabsWanted && !groupSlabsStop.load(); i++) {
+                    HostBatch *g = new HostBatch();
+                    if (deviceRecords) g->shape_plain_records((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt, 5 * std::min<uint64_t>(rn, 0xFFFFFFFFu) + 4 * rt);
+                    else g->shape_values((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt);
+                    std::lock_guard<std::mutex> lk(mu);
+                    groupSlabs.push_back(g);
+                }
+            });
+        });
     }
-    bool deviceRecords = false;
-    if (const char *e = getenv("MDBG_TOOL_DEVICE_RECORDS")) {
-        if (atoi(e) != 0) {
-            deviceRecords = mdbg_minimizers_to_record_bytes && mdbg_bytes_download;
-            g_trace.mark(deviceRecords ? "device records: the records of read_data_init.txt and read_data_corrected.txt are composed on the device (mdbg_minimizers_to_record_bytes)"
-                                       : "device records: falling back to the host builders: the library has no mdbg_minimizers_to_record_bytes or mdbg_bytes_download");
+};
+
+// Where the main pass's batches go once they are on the host: read_data_init.txt in read order (ReadSelection.hpp:386-491) and the sums
+// of read_stats.txt.
+// The record bytes of a batch -- `u32 n; u8 circ; u32 m[n]; u32 pos[n]; u8 dir[n]; u8 qual[n]; f32 meanQ; u32 len` per read -- are
+// built by a few builder threads and written where they belong in the file (pwrite: the size of every earlier batch is known as
+// soon as it has been scanned); one thread writing 1.9 GB of a 50 Gbp read set alone finished 0.45 s behind the consumers.  The
+// statistics (long-double sums: order matters) are accumulated by one thread in read order behind the builders.
+// With MDBG_TOOL_DEVICE_RECORDS=1 the consumers bring the bytes back ready-made (mdbg_minimizers_to_record_bytes) and a builder only
+// writes them; placement, the window of batches in flight and the order of the statistics are the same.
+struct RecordSink {
+    SelectionShared &S;
+    const int outFd;
+    const std::string outFile;
+    const size_t minimizerSize;
+    // guarded by S.mu
+    std::map<uint64_t, HostBatch *> buildQ;             // by batch number: a builder takes the lowest one whose place in the file is known
+    mdbg_host::OrderedPlace place;                      // batch -> record bytes, until its file offset is known
+    std::map<uint64_t, uint64_t> offOf;                 // batch -> file offset, until a builder takes it
+    std::map<uint64_t, HostBatch *> pending;            // finished batches waiting for their turn at the statistics thread
+    uint64_t nextWrite = 0;
+    bool buildDone = false, fifoDone = false;
+    size_t inFlight = 0;                                // batches between the consumers and the statistics thread
+    const uint64_t inFlightWindow;
+    // the statistics thread's own until it has been joined
+    std::vector<uint32_t> allReadSizes;
+    uint64_t nbKmers = 0, nbBases = 0, nbSelected = 0;
+    long double qualitySum = 0, qualityN = 0;
+
+    std::vector<std::thread> builders;
+    std::thread statistics, watchdog;
+    std::atomic<bool> watchStop{false};
+
+    RecordSink(SelectionShared &S_, int outFd_, const std::string &outFile_, size_t minimizerSize_)
+        : S(S_), outFd(outFd_), outFile(outFile_), minimizerSize(minimizerSize_), inFlightWindow(12 + 2 * (uint64_t)S_.nConsumers) {}
+
+    void start(int threads) {
+        for (int i = 0, nb = std::max(1, std::min(4, threads / 4)); i < nb; i++) builders.emplace_back([this] { build(); });
+        if (const char *e = getenv("MDBG_TOOL_WATCHDOG_S")) {        // debugging aid: the state of the pipeline every so many seconds
+            const int every = std::max(1, atoi(e));
+            watchdog = std::thread([this, every] { watch(every); });
         }
-    }
-    std::vector<mdbg_ctx *> ctxs{g_ctx};
-    for (int i = 1; i < nConsumers; i++) {
-        mdbg_ctx *c = nullptr;
-        if (mdbg_create(i % std::max(1, a.gpus), &c) != MDBG_OK) die(std::string("mdbg_create(device ") + std::to_string(i % a.gpus) + "): " + mdbg_last_error(nullptr));
-        ctxs.push_back(c);
-        g_more_ctx.push_back(c);
+        statistics = std::thread([this] { count(); });
     }
 
-    std::map<uint64_t, HostBatch *> pending;     // finished batches waiting for their turn at the writer
-    uint64_t nextWrite = 0;
-    std::mutex fifoMu;
-    std::condition_variable fifoCv;
-    bool fifoDone = false;
-    // The record bytes of a batch -- `u32 n; u8 circ; u32 m[n]; u32 pos[n]; u8 dir[n]; u8 qual[n]; f32 meanQ; u32 len` per read -- are
-    // built by a few builder threads and written where they belong in the file (pwrite: the size of every earlier batch is known as
-    // soon as it has been scanned); one thread writing 1.9 GB of a 50 Gbp read set alone finished 0.45 s behind the consumers.  The
-    // statistics (long-double sums: order matters) are accumulated by one thread in read order behind the builders.
-    // With MDBG_TOOL_DEVICE_RECORDS=1 the consumers bring the bytes back ready-made (mdbg_minimizers_to_record_bytes) and a builder only
-    // writes them; placement, the window of batches in flight and the order of the statistics are the same.
-    std::map<uint64_t, HostBatch *> buildQ;             // by batch number: a builder takes the lowest one whose place in the file is known
-    std::map<uint64_t, uint64_t> sizeOf, offOf;         // batch -> record bytes / file offset
-    uint64_t prefSeq = 0, prefOff = 0;
-    bool buildDone = false;
-    size_t inFlight = 0;                                // batches between the consumers and the statistics thread
-    const uint64_t inFlightWindow = 12 + 2 * (uint64_t)nConsumers;
-    auto register_size = [&](uint64_t seq, uint64_t bytes) {     // fifoMu held
-        sizeOf[seq] = bytes;
-        for (auto it = sizeOf.find(prefSeq); it != sizeOf.end(); it = sizeOf.find(prefSeq)) {
-            offOf[prefSeq] = prefOff;
-            prefOff += it->second;
-            sizeOf.erase(it);
-            prefSeq++;
+    // a consumer's batch `seq`, scanned and downloaded into hb; its minimizers stay on the device for the purge pass when one follows
+    void hand_over(uint64_t seq, HostBatch *hb, mdbg_ctx *ctx, mdbg_minimizers *mins) {
+        {
+            std::unique_lock<std::mutex> lk(S.mu);
+            if (S.needCorrected) S.kept.push_back(SelectionShared::Kept{seq, ctx, mins});
+            place.add(seq, hb->t * 10 + (uint64_t)hb->n * 13, [this](uint64_t s, uint64_t at) { offOf[s] = at; });
+            S.cv.notify_all();          // builders may be waiting for exactly this size to learn their offsets (and this thread may
+                                        // be about to wait itself: a wake-up left for after the wait below never comes)
+            // Bounded by a WINDOW OF BATCH NUMBERS above the one the statistics thread is waiting for, not by a count (round-3
+            // ADVICE: with three or more consumers, twelve later batches could fill the count while batch `nextWrite` sat
+            // staged-ahead and unscanned with a consumer parked right here).  A consumer's staged batch always comes after the one
+            // it is holding, so whoever holds batch nextWrite -- scanned or staged -- is never the one waiting: no cycle.
+            S.cv.wait(lk, [&] { return seq < nextWrite + inFlightWindow; });
+            inFlight++;
+            buildQ.emplace(seq, hb);
         }
-    };
-    auto build = [&] {
+        if (!S.needCorrected) mdbg_minimizers_free(mins);
+        S.cv.notify_all();
+    }
+
+    void build() {
         std::vector<char> rec;
         for (;;) {
             HostBatch *hb = nullptr;
             uint64_t at = 0;
             {
-                std::unique_lock<std::mutex> lk(fifoMu);
+                std::unique_lock<std::mutex> lk(S.mu);
                 // never hold a batch while waiting for its offset (round-3 ADVICE): the offset needs the sizes of all earlier batches, and
                 // with every builder parked on a later batch the one the statistics thread is waiting for sat in the queue unbuilt
                 auto placed = [&]() -> std::map<uint64_t, HostBatch *>::iterator {
                     for (auto it = buildQ.begin(); it != buildQ.end(); ++it) if (offOf.count(it->first)) return it;
                     return buildQ.end();
                 };
-                fifoCv.wait(lk, [&] { return placed() != buildQ.end() || (buildDone && buildQ.empty()); });
+                S.cv.wait(lk, [&] { return placed() != buildQ.end() || (buildDone && buildQ.empty()); });
                 auto it = placed();
                 if (it == buildQ.end()) return;
                 hb = it->second;
@@ -813,672 +543,549 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
                     memcpy(dst, &hb->meanQ[r], 4); memcpy(dst + 4, &hb->len[r], 4); dst += 8;
                 }
             }
-            const char *from = hb->rec ? hb->rec : rec.data();       // (device records: the slab holds the bytes as they came off the device)
-            for (size_t done = 0; done < recBytes;) {
-                const ssize_t w = pwrite(outFd, from + done, recBytes - done, (off_t)(at + done));
-                if (w < 0) { if (errno == EINTR) continue; die("write to " + outFile + " failed"); }
-                done += (size_t)w;
-            }
+            // (device records: the slab holds the bytes as they came off the device)
+            if (!mdbg_host::pwrite_all(outFd, hb->rec ? hb->rec : rec.data(), recBytes, at)) die("write to " + outFile + " failed");
             {
-                std::lock_guard<std::mutex> lk(fifoMu);
+                std::lock_guard<std::mutex> lk(S.mu);
                 pending.emplace(hb->seq, hb);
             }
-            fifoCv.notify_all();
+            S.cv.notify_all();
         }
-    };
-    std::vector<std::thread> builders;
-    for (int i = 0, nb = std::max(1, std::min(4, a.threads / 4)); i < nb; i++) builders.emplace_back(build);
-    std::thread watchdog;
-    std::atomic<bool> watchStop{false};
-    if (const char *e = getenv("MDBG_TOOL_WATCHDOG_S")) {        // debugging aid: the state of the pipeline every so many seconds
-        const int every = std::max(1, atoi(e));
-        watchdog = std::thread([&, every] {
-            for (int t = 0; !watchStop.load(); t++) {
-                std::this_thread::sleep_for(std::chrono::milliseconds(100));
-                if (t % (10 * every) != 10 * every - 1) continue;
-                std::lock_guard<std::mutex> lk(fifoMu);
-                fprintf(stderr, "[mdbg_tool watchdog] buildQ %zu pending %zu inFlight %zu nextWrite %llu prefSeq %llu sizeOf %zu offOf %zu spare %zu\n", buildQ.size(),
-                        pending.size(), inFlight, (unsigned long long)nextWrite, (unsigned long long)prefSeq, sizeOf.size(), offOf.size(), spareBatches.size());
-                if (!sizeOf.empty()) fprintf(stderr, "    first registered-but-unplaced batch %llu\n", (unsigned long long)sizeOf.begin()->first);
-                if (!buildQ.empty()) fprintf(stderr, "    buildQ front %llu\n", (unsigned long long)buildQ.begin()->first);
-            }
-        });
     }
-    std::thread writer([&] {
+
+    // the statistics thread: the batches in read order behind the builders
+    void count() {
         for (;;) {
             HostBatch *hb = nullptr;
             {
-                std::unique_lock<std::mutex> lk(fifoMu);
-                fifoCv.wait(lk, [&] { return pending.count(nextWrite) || (fifoDone && pending.empty()); });
+                std::unique_lock<std::mutex> lk(S.mu);
+                S.cv.wait(lk, [&] { return pending.count(nextWrite) || (fifoDone && pending.empty()); });
                 auto it = pending.find(nextWrite);
                 if (it == pending.end()) return;
                 hb = it->second;
                 pending.erase(it);
                 nextWrite++;
             }
-            fifoCv.notify_all();
+            S.cv.notify_all();
             for (uint32_t r = 0; r < hb->n; r++) {
                 const uint32_t k = (uint32_t)(hb->off[r + 1] - hb->off[r]);
                 allReadSizes.push_back(hb->len[r]);
                 nbSelected += k;
-                nbKmers += (uint64_t)((size_t)hb->len[r] - P.minimizerSize + 1);   // size_t arithmetic as in :480
+                nbKmers += (uint64_t)((size_t)hb->len[r] - minimizerSize + 1);   // size_t arithmetic as in :480
                 nbBases += hb->len[r];
                 if (!(hb->flags[r] & MDBG_READ_LOW_QUALITY)) { qualitySum += hb->meanQ[r]; qualityN += 1; }   // :911-914
             }
             {
-                std::lock_guard<std::mutex> lk(fifoMu);
-                spareBatches.push_back(hb);                  // its slab serves a later batch
+                std::lock_guard<std::mutex> lk(S.mu);
+                S.spareBatches.push_back(hb);                // its slab serves a later batch
                 inFlight--;
             }
-            fifoCv.notify_all();
+            S.cv.notify_all();
         }
-    });
-
-    double tUpload = 0, tScan = 0, tDownload = 0, tQueue = 0, tWait = 0;
-    uint64_t nBatches = 0;
-    {
-        // (nullptr on failure: the feeder's workers -- many threads, page-locking side by side -- throw into its error path; `check` would
-        // have them all write the shared context's error string and _exit at once)
-        auto alloc = [](size_t n) -> void * { void *p = nullptr; return mdbg_host_alloc(g_ctx, n, &p) == MDBG_OK ? p : nullptr; };
-        auto release = [](void *p) { mdbg_host_free(g_ctx, p); };
-        std::unique_ptr<mdbg_host::ReadFeeder> feeder;
-        // MDBG_TOOL_DEVICE_PARSE=1 (this pass has no per-file read cap): the files' text goes to the device slab by slab and is parsed there
-        DeviceParsePlan devParse;
-        bool deviceParse = false;
-        if (const char *e = getenv("MDBG_TOOL_DEVICE_PARSE")) {
-            if (atoi(e) != 0 && getenv("MDBG_TOOL_PARSE_ON_HOST")) g_trace.mark("device parse: MDBG_TOOL_PARSE_ON_HOST is set: the host feed");
-            else if (atoi(e) != 0) {
-                std::string why;
-                deviceParse = devParse.make(read_input_list(inputList), std::max<size_t>(1, a.batchBases), a.threads, std::max(1, a.gpus), why);
-                if (deviceParse && !devParse.gzips.empty())
-                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size() - devParse.bgzfs.size() - devParse.gzips.size()) +
-                                  " slab(s) of plain text, " + std::to_string(devParse.bgzfs.size()) + " BGZF file(s) and " + std::to_string(devParse.gzips.size()) +
-                                  " gzip file(s) cut into chunks at deflate block headers, inflated there and cut into slabs").c_str());
-                else if (deviceParse && devParse.bgzfs.empty())
-                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size()) + " slab(s)").c_str());
-                else if (deviceParse)
-                    g_trace.mark(("device parse: the text of every input file is taken apart on the device, " + std::to_string(devParse.slabs.size() - devParse.bgzfs.size()) +
-                                  " slab(s) of plain text and " + std::to_string(devParse.bgzfs.size()) + " BGZF file(s) cut into slabs as they are inflated there").c_str());
-                else { devParse.unmap(); g_trace.mark(("device parse: falling back to the host feed: " + why).c_str()); }
-            }
-        }
-        if (!deviceParse) {
-            try { feeder.reset(new mdbg_host::ReadFeeder(read_input_list(inputList), a.batchBases, a.threads, 0, alloc, release, nConsumers)); }
-            catch (const std::exception &e) { die(e.what()); }
-        }
-        std::mutex feedMu, statMu;
-        uint64_t nextSeq = 0;
-        size_t nextSlab = 0;
-        // where the BGZF file at slabs[nextSlab] stands (under feedMu): its next slab begins `bgzfBegin` bytes into the text of block `bgzfBlock`
-        size_t bgzfBlock = 0;
-        uint64_t bgzfBegin = 0;
-        uint64_t bgzfSlabs = 0, bgzfInflated = 0, bgzfBlocks = 0;
-        // gzip files are inflated by a context of their own (under feedMu): a stream belongs to one context, the consumers take turns
-        mdbg_ctx *gzCtx = nullptr;
-        uint64_t gzSlabs = 0, gzChunks = 0, gzCalls = 0;
-        const size_t batchText = std::max<size_t>(1, a.batchBases);
-        auto consume = [&](int ci) {
-            mdbg_ctx *ctx = ctxs[(size_t)ci];
-            double up = 0, sc = 0, dn = 0, qu = 0, wt = 0;
-            uint64_t nb = 0;
-            // One batch ahead: the upload of batch i+1 is queued (mdbg_reads_from_packed_async: the context's upload stream, a copy
-            // engine) before batch i is scanned and its minimizers come back, so the link carries reads in one direction and
-            // minimizers in the other while the kernels run.  Packed chunks take this route, with or without qualities; chunks
-            // delivered as ASCII (a character with bit 3 set) are uploaded synchronously as before.
-            struct Staged { ReadBatch *b = nullptr; uint64_t seq = 0; mdbg_reads *reads = nullptr; bool live = false; };
-            void *textSlab = nullptr;             // device parse: this consumer's page-locked slab
-            auto parse_failed = [&](uint64_t seq) {
-                die(std::string("mdbg_reads_from_fastx_bytes (slab ") + std::to_string(seq) + " of the input, MDBG_TOOL_DEVICE_PARSE): " + mdbg_last_error(ctx) +
-                    " -- run without MDBG_TOOL_DEVICE_PARSE for the host feed");
-            };
-            // The next slab of the BGZF file `z` (feedMu held: where a slab ends is known only when its text is on the device, and the next
-            // begins there).  A slab is a run of blocks of at most batchText bytes of text, and one block more when it begins inside its first
-            // block; its compressed bytes go up from the mapping and are inflated to offset 0 of *text.  All but the file's last slab end
-            // behind their last whole record (mdbg_fastx_whole_records); the next slab begins with the block that holds that place, inflated a
-            // second time.  Returns false when the file has no text left; otherwise [*begin, *end) of *text is to be parsed.
-            // A block that does not inflate ends the run with the library's message: the reads in front of it are already on their way.
-            auto next_bgzf_slab = [&](const DeviceParsePlan::Bgzf &z, mdbg_bytes **text, uint64_t *begin, uint64_t *end) -> bool {
-                const size_t nb = z.blocks.size();
-                while (bgzfBlock < nb && z.blocks[bgzfBlock].isize == 0 && bgzfBegin == 0) bgzfBlock++;
-                if (bgzfBlock >= nb) return false;
-                const size_t b0 = bgzfBlock;
-                size_t b1 = b0;
-                uint64_t sum = 0;
-                while (b1 < nb && (b1 == b0 || sum + z.blocks[b1].isize <= batchText)) sum += z.blocks[b1++].isize;
-                if (bgzfBegin && b1 < nb) sum += z.blocks[b1++].isize;           // a cut is pending: the first block is mostly the last slab's
-                std::vector<mdbg_bgzf_block> table;
-                for (;;) {
-                    const uint64_t base = z.blocks[b0].payload, top = z.blocks[b1 - 1].payload + z.blocks[b1 - 1].csize;
-                    table.resize(b1 - b0);
-                    for (size_t i = b0; i < b1; i++) table[i - b0] = mdbg_bgzf_block{z.blocks[i].payload - base, z.blocks[i].csize, z.blocks[i].isize, z.blocks[i].crc, 0};
-                    mdbg_bytes *comp = nullptr;
-                    check_on(ctx, mdbg_bytes_create(ctx, top - base, &comp), "mdbg_bytes_create");
-                    check_on(ctx, mdbg_bytes_create(ctx, std::max<uint64_t>(1, sum), text), "mdbg_bytes_create");
-                    check_on(ctx, mdbg_bytes_upload_async(ctx, comp, 0, z.addr + base, top - base, nullptr), "mdbg_bytes_upload_async");
-                    uint64_t n_text = 0;
-                    const int rc = mdbg_bytes_inflate_bgzf(ctx, comp, table.data(), table.size(), *text, 0, &n_text);
-                    mdbg_bytes_free(comp);
-                    if (rc != MDBG_OK)
-                        die(z.path + ": " + mdbg_last_error(ctx) + " (the table of this call begins with block " + std::to_string(b0) + " of the file, MDBG_TOOL_DEVICE_PARSE)");
-                    bgzfInflated += b1 - b0;
-                    *begin = bgzfBegin;
-                    *end = n_text;
-                    if (b1 == nb) {                                              // the file's last slab is parsed whole
-                        bgzfBlock = nb;
-                        bgzfBegin = 0;
-                        if (*begin >= n_text) { mdbg_bytes_free(*text); *text = nullptr; return false; }
-                        return true;
-                    }
-                    uint64_t cut = *begin;
-                    int format = 0;
-                    if (*begin < n_text) check_on(ctx, mdbg_fastx_whole_records(ctx, *text, *begin, n_text, &cut, &format), "mdbg_fastx_whole_records");
-                    if (cut > *begin) {
-                        *end = cut;
-                        const uint64_t at = z.cum[b0] + cut;                     // in the file's text
-                        if (at == z.cum[b1]) { bgzfBlock = b1; bgzfBegin = 0; }
-                        else {
-                            bgzfBlock = (size_t)(std::upper_bound(z.cum.begin(), z.cum.end(), at) - z.cum.begin()) - 1;
-                            bgzfBegin = at - z.cum[bgzfBlock];
-                        }
-                        return true;
-                    }
-                    // not one whole record yet: more blocks, up to a batch of them
-                    mdbg_bytes_free(*text);
-                    *text = nullptr;
-                    if (sum > batchText) die("a single read is larger than the batch size; raise --batch-bases");
-                    const uint64_t upto = std::max<uint64_t>(2 * sum, 65536);
-                    do sum += z.blocks[b1++].isize; while (b1 < nb && sum < upto && sum + z.blocks[b1].isize <= batchText);
-                }
-            };
-            // The next slab of the gzip file `G` (feedMu held).  A group of chunks -- about a quarter of batchText in compressed bytes, one
-            // chunk at the least -- goes up from the mapping and is inflated behind the unfinished record the last slab left
-            // (mdbg_bytes_copy); all but the file's last slab end behind their last whole record (mdbg_fastx_whole_records).  The text
-            // buffer is sized by a guess; MDBG_ERANGE names the room needed and leaves the stream where it was.  A start the search
-            // guessed wrong ends the run with the device's message: nothing is guessed silently.
-            auto next_gzip_slab = [&](DeviceParsePlan::Gzip &G, mdbg_bytes **text, uint64_t *begin, uint64_t *end) -> bool {
-                using Gz = DeviceParsePlan::Gzip;
-                auto gz_die = [&](const std::string &what) {
-                    die(G.path + ": " + what + " -- set MDBG_TOOL_PARSE_ON_HOST=1 (or run without MDBG_TOOL_DEVICE_PARSE) for the host feed");
-                };
-                if (!gzCtx) {
-                    if (mdbg_create(0, &gzCtx) != MDBG_OK) die(std::string("mdbg_create (gzip inflation): ") + mdbg_last_error(nullptr));
-                    g_more_ctx.push_back(gzCtx);
-                }
-                if (!G.stream) check_on(gzCtx, mdbg_gzip_stream_create(gzCtx, &G.stream), "mdbg_gzip_stream_create");
-                for (;;) {
-                    if (G.ended) {
-                        if (G.rest) { mdbg_bytes_free(G.rest); G.rest = nullptr; }
-                        if (G.nRest) gz_die("the file ends inside a record");      // (the last slab is parsed whole: nothing is left behind it)
-                        return false;
-                    }
-                    const uint64_t target = std::max<uint64_t>(G.chunk, batchText / 4);
-                    std::vector<mdbg_gzip_chunk> table;
-                    uint64_t cur = G.atBit;
-                    size_t k = G.nextK;
-                    for (;;) {
-                        uint64_t s = Gz::NONE;
-                        while (k < G.nChunks && s == Gz::NONE) {
-                            const uint64_t f = G.wait_start(k++);
-                            if (f != Gz::NONE && f > cur) s = f;
-                        }
-                        if (s == Gz::NONE) { table.push_back(mdbg_gzip_chunk{cur, MDBG_GZIP_TO_END}); break; }
-                        table.push_back(mdbg_gzip_chunk{cur, s});
-                        cur = s;
-                        if ((s >> 3) - (G.atBit >> 3) >= target) break;
-                    }
-                    const uint64_t stop = table.back().stop_bit;
-                    const uint64_t base = G.atBit >> 3, top = stop == MDBG_GZIP_TO_END ? G.size : (stop + 7) / 8;
-                    for (mdbg_gzip_chunk &c : table) {
-                        if (((c.stop_bit == MDBG_GZIP_TO_END ? G.size : (c.stop_bit + 7) / 8) - (c.start_bit >> 3)) > ((uint64_t)1 << 21))
-                            gz_die("no deflate block header was found in 2 MB behind bit " + std::to_string(c.start_bit));
-                        c.start_bit -= base * 8;
-                        if (c.stop_bit != MDBG_GZIP_TO_END) c.stop_bit -= base * 8;
-                    }
-                    mdbg_bytes *comp = nullptr;
-                    check_on(gzCtx, mdbg_bytes_create(gzCtx, top - base, &comp), "mdbg_bytes_create");
-                    check_on(gzCtx, mdbg_bytes_upload_async(gzCtx, comp, 0, G.addr + base, top - base, nullptr), "mdbg_bytes_upload_async");
-                    uint64_t room = G.nRest + 5 * (top - base) + 65536, n_text = 0, info[4] = {0, 0, 0, 0};
-                    for (int attempt = 0;; attempt++) {
-                        check_on(gzCtx, mdbg_bytes_create(gzCtx, room, text), "mdbg_bytes_create");
-                        if (G.nRest) check_on(gzCtx, mdbg_bytes_copy(gzCtx, *text, 0, G.rest, 0, G.nRest), "mdbg_bytes_copy");
-                        const int rc = mdbg_bytes_inflate_gzip(gzCtx, G.stream, comp, table.data(), table.size(), *text, G.nRest, &n_text, info);
-                        if (rc == MDBG_OK) break;
-                        mdbg_bytes_free(*text);
-                        *text = nullptr;
-                        if (rc != MDBG_ERANGE || attempt) {
-                            mdbg_bytes_free(comp);
-                            gz_die(std::string(mdbg_last_error(gzCtx)) + " (the chunks of this call begin at bit " + std::to_string(G.atBit) + " of the file; a chunk start is a guess of the header search)");
-                        }
-                        room = G.nRest + n_text;
-                    }
-                    mdbg_bytes_free(comp);
-                    G.nCalls++; G.nChunksInflated += table.size();
-                    gzCalls++; gzChunks += table.size();
-                    const uint64_t n = G.nRest + n_text;
-                    if (G.rest) { mdbg_bytes_free(G.rest); G.rest = nullptr; }
-                    G.nRest = 0;
-                    G.atBit = base * 8 + info[3];
-                    G.nextK = k;
-                    *begin = 0;
-                    *end = n;
-                    if (info[2]) {                                               // the file's last slab is parsed whole
-                        G.ended = true;
-                        if (n == 0) { mdbg_bytes_free(*text); *text = nullptr; return false; }
-                        return true;
-                    }
-                    if (stop == MDBG_GZIP_TO_END) gz_die("the device stopped in front of the file's end");
-                    uint64_t cut = 0;
-                    int format = 0;
-                    if (n) check_on(gzCtx, mdbg_fastx_whole_records(gzCtx, *text, 0, n, &cut, &format), "mdbg_fastx_whole_records");
-                    if (cut < n) {                                               // the unfinished record goes in front of the next text
-                        check_on(gzCtx, mdbg_bytes_create(gzCtx, n - cut, &G.rest), "mdbg_bytes_create");
-                        check_on(gzCtx, mdbg_bytes_copy(gzCtx, G.rest, 0, *text, cut, n - cut), "mdbg_bytes_copy");
-                        G.nRest = n - cut;
-                    }
-                    if (cut > 0) { *end = cut; return true; }
-                    // not one whole record yet: more chunks
-                    mdbg_bytes_free(*text);
-                    *text = nullptr;
-                    if (n > batchText) die("a single read is larger than the batch size; raise --batch-bases");
-                }
-            };
-            auto stage_text = [&]() -> Staged {
-                Staged st;
-                size_t idx;
-                mdbg_bytes *text = nullptr;
-                uint64_t begin = 0, end = 0;
-                {
-                    std::lock_guard<std::mutex> g(feedMu);       // slabs are handed out in read order
-                    for (;;) {
-                        idx = nextSlab;
-                        if (idx >= devParse.slabs.size()) return st;
-                        const int zi = devParse.slabs[idx].bgzf, gi = devParse.slabs[idx].gz;
-                        if (gi >= 0) {
-                            const double t0 = g_trace.now();
-                            const bool got = next_gzip_slab(*devParse.gzips[(size_t)gi], &text, &begin, &end);
-                            up += g_trace.now() - t0;
-                            if (got) { gzSlabs++; break; }
-                            nextSlab++;                          // this file is done
-                            continue;
-                        }
-                        if (zi < 0) { nextSlab++; break; }
-                        const double t0 = g_trace.now();
-                        const bool got = next_bgzf_slab(devParse.bgzfs[(size_t)zi], &text, &begin, &end);
-                        up += g_trace.now() - t0;
-                        if (got) { bgzfSlabs++; break; }
-                        bgzfBlocks += devParse.bgzfs[(size_t)zi].blocks.size();
-                        nextSlab++;                              // this file is done
-                        bgzfBlock = 0;
-                        bgzfBegin = 0;
-                    }
-                    st.seq = nextSeq++;
-                }
-                st.live = true;
-                const double t0 = g_trace.now();
-                if (text) {                                      // a slab of a BGZF file, inflated above
-                    if (st.seq == 0) g_trace.mark("first slab inflated");
-                    const int rc = mdbg_reads_from_fastx_bytes(ctx, text, begin, end, &st.reads, nullptr);
-                    mdbg_bytes_free(text);
-                    if (rc != MDBG_OK) parse_failed(st.seq);
-                    up += g_trace.now() - t0;
-                    return st;
-                }
-                const DeviceParsePlan::Slab &sl = devParse.slabs[idx];
-                if (!textSlab) check_on(ctx, mdbg_host_alloc(ctx, devParse.maxSlab + 64, &textSlab), "mdbg_host_alloc");
-                memcpy(textSlab, sl.p, sl.n);
-                if (st.seq == 0) g_trace.mark("first slab copied");
-                check_on(ctx, mdbg_bytes_create(ctx, sl.n, &text), "mdbg_bytes_create");
-                check_on(ctx, mdbg_bytes_upload_async(ctx, text, 0, textSlab, sl.n, nullptr), "mdbg_bytes_upload_async");
-                // (the call returns when its kernels have run, so behind the upload: the slab is free for the next piece of text)
-                const int rc = mdbg_reads_from_fastx_bytes(ctx, text, 0, sl.n, &st.reads, nullptr);
-                mdbg_bytes_free(text);
-                if (rc != MDBG_OK) parse_failed(st.seq);
-                up += g_trace.now() - t0;
-                return st;
-            };
-            auto stage = [&]() -> Staged {
-                if (deviceParse) return stage_text();
-                Staged st;
-                const double tw = g_trace.now();
-                try {
-                    std::lock_guard<std::mutex> g(feedMu);       // batches leave the feeder in read order
-                    st.b = feeder->next();
-                    st.seq = nextSeq++;
-                } catch (const std::exception &e) { die(e.what()); }
-                if (!st.b) return st;
-                st.live = true;
-                if (st.seq == 0) g_trace.mark("first batch parsed");
-                const double t0 = g_trace.now();
-                if (st.b->packed) {
-                    check_on(ctx, mdbg_reads_from_packed_async(ctx, st.b->words(), st.b->wordOff.data(), st.b->lens.data(), st.b->n(), &st.reads),
-                             "mdbg_reads_from_packed_async");
-                    if (st.b->hasQual)
-                        check_on(ctx, mdbg_reads_attach_qualities_async(ctx, st.reads, st.b->quals, st.b->offsets.data()), "mdbg_reads_attach_qualities_async");
-                    if (!st.b->odd.empty())         // the few reads with an N or lower case, again as characters (a small synchronous copy)
-                        check_on(ctx, mdbg_reads_mark_ascii(ctx, st.reads, st.b->odd.data(), (uint32_t)st.b->odd.size(), st.b->oddBases.data(),
-                                                            st.b->oddOff.data()), "mdbg_reads_mark_ascii");
-                } else {
-                    st.reads = upload_batch(ctx, *st.b, true);
-                    feeder->recycle(st.b);                       // the page-locked buffer is free again once the upload is done
-                    st.b = nullptr;
-                }
-                wt += t0 - tw; up += g_trace.now() - t0;
-                return st;
-            };
-            Staged next = stage();
-            while (next.live) {
-                Staged cur = next;
-                next = stage();
-                const uint64_t seq = cur.seq;
-                const double t1 = g_trace.now();
-                mdbg_minimizers *mins = nullptr;
-                mdbg_scan_params p = scan_params(P, P.densityAssembly, rep, a.minReadQuality, true);
-                check_on(ctx, mdbg_scan(ctx, cur.reads, &p, &mins), "mdbg_scan");
-                if (cur.b) {                                     // the scan has read the words: the upload is long done
-                    check_on(ctx, mdbg_reads_wait(ctx, cur.reads), "mdbg_reads_wait");
-                    feeder->recycle(cur.b);
-                }
-                mdbg_reads_free(cur.reads);
-                const double t2 = g_trace.now();
-                HostBatch *hb = nullptr;
-                {
-                    std::lock_guard<std::mutex> lk(fifoMu);
-                    if (!spareBatches.empty()) { hb = spareBatches.back(); spareBatches.pop_back(); }
-                }
-                if (!hb) hb = new HostBatch();
-                hb->seq = seq;
-                {
-                    uint32_t bn; uint64_t bt;
-                    mdbg_minimizers_info(mins, &bn, &bt);
-                    if (deviceRecords) hb->shape_init_records(bn, bt, bt * 10 + (uint64_t)bn * 13);
-                    else hb->shape(bn, bt);
-                    if (needCorrected && groupSlabsWanted && !getenv("MDBG_TOOL_NO_GROUP_SLABS"))       // (the variable: A/B of the helper)
-                        std::call_once(groupSlabOnce, [&, bn, bt] {
-                            // a consumer's share of a group (batches are handed out as consumers come free: a little more than GROUP / consumers)
-                            const size_t share = GROUP / (size_t)nConsumers + 2;
-                            const uint64_t rn = (uint64_t)share * bn, rt = (uint64_t)share * bt;
-                            groupSlabHelper = std::thread([&, rn, rt] {
-                                for (size_t i = 0; i < groupSlabsWanted && !groupSlabsStop.load(); i++) {
-                                    HostBatch *g = new HostBatch();
-                                    if (deviceRecords) g->shape_plain_records((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt, 5 * std::min<uint64_t>(rn, 0xFFFFFFFFu) + 4 * rt);
-                                    else g->shape_values((uint32_t)std::min<uint64_t>(rn, 0xFFFFFFFFu), rt);
-                                    std::lock_guard<std::mutex> lk(fifoMu);
-                                    groupSlabs.push_back(g);
-                                }
-                            });
-                        });
-                }
-                if (deviceRecords) {
-                    // the serialisation is queued, the per-read arrays the statistics thread reads come back behind it, then the record bytes
-                    mdbg_bytes *rb = nullptr;
-                    uint64_t nb_rec = 0;
-                    check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, mins, MDBG_RECORDS_INIT, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
-                    if (nb_rec != hb->t * 10 + (uint64_t)hb->n * 13) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a batch");
-                    check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, nullptr, nullptr, nullptr, nullptr, hb->len, hb->meanQ, hb->flags), "to_host");
-                    check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
-                    mdbg_bytes_free(rb);
-                } else {
-                    check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, hb->m, hb->pos, hb->dir, hb->qual, hb->len, hb->meanQ, hb->flags), "to_host");
-                }
-                const double t3 = g_trace.now();
-                {
-                    std::unique_lock<std::mutex> lk(fifoMu);
-                    if (needCorrected) kept.push_back(Kept{seq, ctx, mins});
-                    register_size(seq, hb->t * 10 + (uint64_t)hb->n * 13);
-                    fifoCv.notify_all();        // builders may be waiting for exactly this size to learn their offsets (and this thread may
-                                                // be about to wait itself: a wake-up left for after the wait below never comes)
-                    // Bounded by a WINDOW OF BATCH NUMBERS above the one the statistics thread is waiting for, not by a count (round-3
-                    // ADVICE: with three or more consumers, twelve later batches could fill the count while batch `nextWrite` sat
-                    // staged-ahead and unscanned with a consumer parked right here).  A consumer's staged batch always comes after the one
-                    // it is holding, so whoever holds batch nextWrite -- scanned or staged -- is never the one waiting: no cycle.
-                    fifoCv.wait(lk, [&] { return seq < nextWrite + inFlightWindow; });
-                    inFlight++;
-                    buildQ.emplace(seq, hb);
-                }
-                if (!needCorrected) mdbg_minimizers_free(mins);
-                fifoCv.notify_all();
-                const double t4 = g_trace.now();
-                sc += t2 - t1; dn += t3 - t2; qu += t4 - t3; nb++;
-            }
-            if (textSlab) mdbg_host_free(ctx, textSlab);
-            std::lock_guard<std::mutex> g(statMu);
-            tWait += wt; tUpload += up; tScan += sc; tDownload += dn; tQueue += qu; nBatches += nb;
-        };
-        g_trace.mark("feeder started");
-        std::vector<std::thread> consumers;
-        for (int i = 1; i < nConsumers; i++) consumers.emplace_back(consume, i);
-        consume(0);
-        for (auto &t : consumers) t.join();
-        g_trace.mark("last batch scanned and handed to the writer");
-        devParse.unmap();                       // every slab has been copied and parsed
-        if (!devParse.gzips.empty() && getenv("MDBG_TRACE"))
-            fprintf(stderr, "[mdbg_tool] device parse: %llu chunk(s) of %zu gzip file(s) inflated on the device in %llu call(s), %llu slab(s)\n", (unsigned long long)gzChunks,
-                    devParse.gzips.size(), (unsigned long long)gzCalls, (unsigned long long)gzSlabs);
-        if (!devParse.bgzfs.empty() && getenv("MDBG_TRACE"))
-            fprintf(stderr, "[mdbg_tool] device parse: %llu BGZF block(s) of %zu file(s) inflated on the device in %llu slab(s) (%llu block inflations: a slab's first block may "
-                            "be the one its predecessor ended in)\n", (unsigned long long)bgzfBlocks, devParse.bgzfs.size(), (unsigned long long)bgzfSlabs,
-                    (unsigned long long)bgzfInflated);
-        // the feeder is taken apart behind the purge pass, not in front of it: un-pinning its 27 buffers and unmapping the input cost
-        // 0.45 s of a 1.85 s run when it sat here (and as much under the process's exit when it was simply left to the system)
-        std::thread([f = feeder.release()] { delete f; }).detach();
     }
+
+    void watch(int every) {
+        for (int t = 0; !watchStop.load(); t++) {
+            std::this_thread::sleep_for(std::chrono::milliseconds(100));
+            if (t % (10 * every) != 10 * every - 1) continue;
+            std::lock_guard<std::mutex> lk(S.mu);
+            fprintf(stderr, "[mdbg_tool watchdog] buildQ %zu pending %zu inFlight %zu nextWrite %llu prefSeq %llu sizeOf %zu offOf %zu spare %zu\n", buildQ.size(),
+                    pending.size(), inFlight, (unsigned long long)nextWrite, (unsigned long long)place.next_seq(), place.waiting(), offOf.size(), S.spareBatches.size());
+            if (place.waiting()) fprintf(stderr, "    first registered-but-unplaced batch %llu\n", (unsigned long long)place.first_waiting());
+            if (!buildQ.empty()) fprintf(stderr, "    buildQ front %llu\n", (unsigned long long)buildQ.begin()->first);
+        }
+    }
+
+    // every consumer has handed over its last batch: the builders run dry first, the statistics thread behind them
+    void finish() {
+        {
+            std::lock_guard<std::mutex> lk(S.mu);
+            buildDone = true;
+        }
+        S.cv.notify_all();
+        for (auto &t : builders) t.join();
+        {
+            std::lock_guard<std::mutex> lk(S.mu);
+            fifoDone = true;
+        }
+        S.cv.notify_all();
+        statistics.join();
+        watchStop = true;
+        if (watchdog.joinable()) watchdog.join();
+        if (close(outFd) != 0) die("closing " + outFile + " failed");
+    }
+};
+
+// One consumer thread of the main pass, with a library context (stream, pool) of its own, so the upload of one batch can overlap the
+// scan and the download of another: it takes batches from the host feeder -- or slabs of text from the DeviceTextFeed, feeder == null --
+// scans them, brings the minimizers to the host and hands them to the sink while later batches are on the device.
+// One batch ahead: the upload of batch i+1 is queued (mdbg_reads_from_packed_async: the context's upload stream, a copy
+// engine) before batch i is scanned and its minimizers come back, so the link carries reads in one direction and
+// minimizers in the other while the kernels run.  Packed chunks take this route, with or without qualities; chunks
+// delivered as ASCII (a character with bit 3 set) are uploaded synchronously as before.
+struct Consumer {
+    // MDBG_TRACE: where the consumers' time went, summed over them
+    struct Totals { std::mutex mu; double wait = 0, upload = 0, scan = 0, download = 0, queue = 0; uint64_t batches = 0; };
+    SelectionShared &S;
+    RecordSink &sink;
+    DeviceTextFeed &feed;
+    mdbg_host::ReadFeeder *feeder;
+    const Parameters &P;
+    const std::vector<uint32_t> &rep;
+    const float minReadQuality;
+    Totals &totals;
+    mdbg_ctx *ctx;
+    double up = 0, sc = 0, dn = 0, qu = 0, wt = 0;
+    uint64_t nb = 0;
+    void *textSlab = nullptr;             // device parse: this consumer's page-locked slab
+
+    struct Staged { ReadBatch *b = nullptr; uint64_t seq = 0; mdbg_reads *reads = nullptr; bool live = false; };
+
+    void parse_failed(uint64_t seq) {
+        die(std::string("mdbg_reads_from_fastx_bytes (slab ") + std::to_string(seq) + " of the input, MDBG_TOOL_DEVICE_PARSE): " + mdbg_last_error(ctx) +
+            " -- run without MDBG_TOOL_DEVICE_PARSE for the host feed");
+    }
+    Staged stage_text() {
+        Staged st;
+        DeviceTextFeed::Handed h;
+        if (!feed.next(ctx, h, &up)) return st;
+        st.seq = h.seq;
+        st.live = true;
+        const double t0 = g_trace.now();
+        mdbg_bytes *text = h.text;
+        if (text) {                                      // a slab of a BGZF or gzip file, inflated by the feed
+            if (st.seq == 0) g_trace.mark("first slab inflated");
+            const int rc = mdbg_reads_from_fastx_bytes(ctx, text, h.begin, h.end, &st.reads, nullptr);
+            mdbg_bytes_free(text);
+            if (rc != MDBG_OK) parse_failed(st.seq);
+            up += g_trace.now() - t0;
+            return st;
+        }
+        const DeviceParsePlan::Slab &sl = feed.plan.slabs[h.idx];
+        if (!textSlab) check_on(ctx, mdbg_host_alloc(ctx, feed.plan.maxSlab + 64, &textSlab), "mdbg_host_alloc");
+        memcpy(textSlab, sl.p, sl.n);
+        if (st.seq == 0) g_trace.mark("first slab copied");
+        check_on(ctx, mdbg_bytes_create(ctx, sl.n, &text), "mdbg_bytes_create");
+        check_on(ctx, mdbg_bytes_upload_async(ctx, text, 0, textSlab, sl.n, nullptr), "mdbg_bytes_upload_async");
+        // (the call returns when its kernels have run, so behind the upload: the slab is free for the next piece of text)
+        const int rc = mdbg_reads_from_fastx_bytes(ctx, text, 0, sl.n, &st.reads, nullptr);
+        mdbg_bytes_free(text);
+        if (rc != MDBG_OK) parse_failed(st.seq);
+        up += g_trace.now() - t0;
+        return st;
+    }
+    Staged stage() {
+        if (!feeder) return stage_text();
+        Staged st;
+        const double tw = g_trace.now();
+        try {
+            std::lock_guard<std::mutex> g(feed.mu);      // batches leave the feeder in read order
+            st.b = feeder->next();
+            st.seq = feed.nextSeq++;
+        } catch (const std::exception &e) { die(e.what()); }
+        if (!st.b) return st;
+        st.live = true;
+        if (st.seq == 0) g_trace.mark("first batch parsed");
+        const double t0 = g_trace.now();
+        if (st.b->packed) {
+            check_on(ctx, mdbg_reads_from_packed_async(ctx, st.b->words(), st.b->wordOff.data(), st.b->lens.data(), st.b->n(), &st.reads),
+                     "mdbg_reads_from_packed_async");
+            if (st.b->hasQual)
+                check_on(ctx, mdbg_reads_attach_qualities_async(ctx, st.reads, st.b->quals, st.b->offsets.data()), "mdbg_reads_attach_qualities_async");
+            if (!st.b->odd.empty())         // the few reads with an N or lower case, again as characters (a small synchronous copy)
+                check_on(ctx, mdbg_reads_mark_ascii(ctx, st.reads, st.b->odd.data(), (uint32_t)st.b->odd.size(), st.b->oddBases.data(),
+                                                    st.b->oddOff.data()), "mdbg_reads_mark_ascii");
+        } else {
+            st.reads = upload_batch(ctx, *st.b, true);
+            feeder->recycle(st.b);                       // the page-locked buffer is free again once the upload is done
+            st.b = nullptr;
+        }
+        wt += t0 - tw; up += g_trace.now() - t0;
+        return st;
+    }
+    // the minimizers of batch `seq` into a page-locked slab: the arrays the builders make records of, or the records themselves
+    HostBatch *download(uint64_t seq, mdbg_minimizers *mins) {
+        HostBatch *hb = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(S.mu);
+            if (!S.spareBatches.empty()) { hb = S.spareBatches.back(); S.spareBatches.pop_back(); }
+        }
+        if (!hb) hb = new HostBatch();
+        hb->seq = seq;
+        uint32_t bn; uint64_t bt;
+        mdbg_minimizers_info(mins, &bn, &bt);
+        if (S.deviceRecords) hb->shape_init_records(bn, bt, bt * 10 + (uint64_t)bn * 13);
+        else hb->shape(bn, bt);
+        if (S.needCorrected && S.groupSlabsWanted && !getenv("MDBG_TOOL_NO_GROUP_SLABS"))       // (the variable: A/B of the helper)
+            S.start_group_slab_helper(bn, bt);
+        if (S.deviceRecords) {
+            // the serialisation is queued, the per-read arrays the statistics thread reads come back behind it, then the record bytes
+            mdbg_bytes *rb = nullptr;
+            uint64_t nb_rec = 0;
+            check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, mins, MDBG_RECORDS_INIT, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
+            if (nb_rec != hb->t * 10 + (uint64_t)hb->n * 13) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a batch");
+            check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, nullptr, nullptr, nullptr, nullptr, hb->len, hb->meanQ, hb->flags), "to_host");
+            check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
+            mdbg_bytes_free(rb);
+        } else {
+            check_on(ctx, mdbg_minimizers_to_host(ctx, mins, hb->off, hb->m, hb->pos, hb->dir, hb->qual, hb->len, hb->meanQ, hb->flags), "to_host");
+        }
+        return hb;
+    }
+    void run() {
+        Staged next = stage();
+        while (next.live) {
+            Staged cur = next;
+            next = stage();
+            const double t1 = g_trace.now();
+            mdbg_minimizers *mins = nullptr;
+            mdbg_scan_params p = scan_params(P, P.densityAssembly, rep, minReadQuality, true);
+            check_on(ctx, mdbg_scan(ctx, cur.reads, &p, &mins), "mdbg_scan");
+            if (cur.b) {                                     // the scan has read the words: the upload is long done
+                check_on(ctx, mdbg_reads_wait(ctx, cur.reads), "mdbg_reads_wait");
+                feeder->recycle(cur.b);
+            }
+            mdbg_reads_free(cur.reads);
+            const double t2 = g_trace.now();
+            HostBatch *hb = download(cur.seq, mins);
+            const double t3 = g_trace.now();
+            sink.hand_over(cur.seq, hb, ctx, mins);
+            const double t4 = g_trace.now();
+            sc += t2 - t1; dn += t3 - t2; qu += t4 - t3; nb++;
+        }
+        if (textSlab) mdbg_host_free(ctx, textSlab);
+        std::lock_guard<std::mutex> g(totals.mu);
+        totals.wait += wt; totals.upload += up; totals.scan += sc; totals.download += dn; totals.queue += qu; totals.batches += nb;
+    }
+};
+
+// MDBG_TOOL_DEVICE_PARSE=1 (the main pass has no per-file read cap): the files' text goes to the device slab by slab and is parsed there.
+// true: feed.plan stands; false: the host feed, and the trace says why when the variable asked for the device
+bool plan_device_parse(DeviceTextFeed &feed, const std::string &inputList, const Args &a) {
+    const char *e = getenv("MDBG_TOOL_DEVICE_PARSE");
+    if (!e || atoi(e) == 0) return false;
+    if (getenv("MDBG_TOOL_PARSE_ON_HOST")) { g_trace.mark("device parse: MDBG_TOOL_PARSE_ON_HOST is set: the host feed"); return false; }
+    std::string why;
+    feed.batchText = std::max<size_t>(1, a.batchBases);
+    if (feed.plan.make(read_input_list(inputList), feed.batchText, a.threads, std::max(1, a.gpus), why)) { g_trace.mark(feed.plan.describe()); return true; }
+    feed.plan.unmap();
+    g_trace.mark("device parse: falling back to the host feed: " + why);
+    return false;
+}
+
+// The main pass's scanning side: S.nConsumers consumers (the calling thread is one) until the input is at its end.
+// Batches are turned into host arrays by consumer threads, each with its own library context; the sink builds the records and
+// writes them in batch order while later batches are on the device.
+void scan_all_batches(SelectionShared &S, RecordSink &sink, const Parameters &P, const std::vector<uint32_t> &rep, const Args &a, const std::string &inputList) {
+    // (nullptr on failure: the feeder's workers -- many threads, page-locking side by side -- throw into its error path; `check` would
+    // have them all write the shared context's error string and _exit at once)
+    auto alloc = [](size_t n) -> void * { void *p = nullptr; return mdbg_host_alloc(g_ctx, n, &p) == MDBG_OK ? p : nullptr; };
+    auto release = [](void *p) { mdbg_host_free(g_ctx, p); };
+    std::unique_ptr<mdbg_host::ReadFeeder> feeder;
+    DeviceTextFeed feed;
+    if (!plan_device_parse(feed, inputList, a)) {
+        try { feeder.reset(new mdbg_host::ReadFeeder(read_input_list(inputList), a.batchBases, a.threads, 0, alloc, release, S.nConsumers)); }
+        catch (const std::exception &e) { die(e.what()); }
+    }
+    Consumer::Totals totals;
+    std::vector<std::unique_ptr<Consumer>> cs;
+    for (int i = 0; i < S.nConsumers; i++) cs.emplace_back(new Consumer{S, sink, feed, feeder.get(), P, rep, a.minReadQuality, totals, S.ctxs[(size_t)i]});
+    g_trace.mark("feeder started");
+    std::vector<std::thread> threads;
+    for (int i = 1; i < S.nConsumers; i++) threads.emplace_back([&cs, i] { cs[(size_t)i]->run(); });
+    cs[0]->run();
+    for (auto &t : threads) t.join();
+    g_trace.mark("last batch scanned and handed to the writer");
+    feed.plan.unmap();                      // every slab has been copied and parsed
+    feed.trace_totals();
+    // the feeder is taken apart behind the purge pass, not in front of it: un-pinning its 27 buffers and unmapping the input cost
+    // 0.45 s of a 1.85 s run when it sat here (and as much under the process's exit when it was simply left to the system)
+    std::thread([f = feeder.release()] { delete f; }).detach();
     if (getenv("MDBG_TRACE"))
         fprintf(stderr, "[mdbg_tool] %llu batches on %d consumer(s), summed over them: waiting for the feeder %.3f s, upload (queued ahead when packed) %.3f s, scan %.3f s, "
-                        "download %.3f s, writer queue %.3f s\n", (unsigned long long)nBatches, nConsumers, tWait, tUpload, tScan, tDownload, tQueue);
-    {
-        std::lock_guard<std::mutex> lk(fifoMu);
-        buildDone = true;
-    }
-    fifoCv.notify_all();
-    for (auto &t : builders) t.join();
-    {
-        std::lock_guard<std::mutex> lk(fifoMu);
-        fifoDone = true;
-    }
-    fifoCv.notify_all();
-    writer.join();
-    watchStop = true;
-    if (watchdog.joinable()) watchdog.join();
-    if (close(outFd) != 0) die("closing " + outFile + " failed");
-    g_trace.mark("main pass done (parse + scan + read_data_init.txt)");
+                        "download %.3f s, writer queue %.3f s\n", (unsigned long long)totals.batches, S.nConsumers, totals.wait, totals.upload, totals.scan, totals.download, totals.queue);
+}
 
-    // read_stats.txt (ReadSelection.hpp:305-384)
-    const uint64_t nbReads = allReadSizes.size();
-    const uint32_t n50 = compute_n50(allReadSizes);
-    const uint32_t meanLen = nbReads ? compute_mean_length(allReadSizes) : 0;
-    {
-        float density = (float)((long double)nbSelected / (long double)nbKmers);
-        float avgQ = (float)(qualitySum / qualityN);
-        std::ofstream st(tmpDir + "/read_stats.txt", std::ios::binary);
-        st.write((const char *)&nbReads, 8); st.write((const char *)&n50, 4); st.write((const char *)&density, 4);
-        st.write((const char *)&nbBases, 8); st.write((const char *)&avgQ, 4); st.write((const char *)&meanLen, 4);
-        st.write((const char *)&nbSelected, 8);
-        st.close();
-        if (!st) die("writing " + tmpDir + "/read_stats.txt failed");
-    }
-
-    g_log.line("\tNb reads: " + std::to_string(nbReads) + "  bases: " + std::to_string(nbBases) + "  minimizers: " + std::to_string(nbSelected) +
+// read_stats.txt (ReadSelection.hpp:305-384) and the log's line, from what the statistics thread counted.  Returns the N50
+uint32_t write_read_stats(const RecordSink &sink, const std::string &tmpDir) {
+    const uint64_t nbReads = sink.allReadSizes.size();
+    const uint32_t n50 = compute_n50(sink.allReadSizes);
+    const uint32_t meanLen = nbReads ? compute_mean_length(sink.allReadSizes) : 0;
+    float density = (float)((long double)sink.nbSelected / (long double)sink.nbKmers);
+    float avgQ = (float)(sink.qualitySum / sink.qualityN);
+    std::ofstream st(tmpDir + "/read_stats.txt", std::ios::binary);
+    st.write((const char *)&nbReads, 8); st.write((const char *)&n50, 4); st.write((const char *)&density, 4);
+    st.write((const char *)&sink.nbBases, 8); st.write((const char *)&avgQ, 4); st.write((const char *)&meanLen, 4);
+    st.write((const char *)&sink.nbSelected, 8);
+    st.close();
+    if (!st) die("writing " + tmpDir + "/read_stats.txt failed");
+    g_log.line("\tNb reads: " + std::to_string(nbReads) + "  bases: " + std::to_string(sink.nbBases) + "  minimizers: " + std::to_string(sink.nbSelected) +
                "  N50: " + std::to_string(n50));
-    // purgePalindromes (ReadSelection.hpp:1374-1431): lastK from the N50, --max-k ignored
-    if (needCorrected) {
-        const int lastK = compute_last_k(P.densityAssembly, n50, P.firstK, 0);
-        std::sort(kept.begin(), kept.end(), [](const Kept &x, const Kept &y) { return x.seq < y.seq; });
-        // A second pass shaped like the first, on GROUPS of batches: a batch is a few thousand reads and 16 k minimizers, and purging them
-        // one by one -- two kernels, three waits and two copies each -- was 0.39 ms a batch, 0.18 to 0.23 s of a 50 Gbp FASTA / 20 Gbp FASTQ
-        // run.  Every consumer appends the batches its context holds of a group of 32 consecutive ones on the device
-        // (mdbg_minimizers_concat), purges them with one call, copies values and offsets back into one page-locked slab, and the writer
-        // builds the `u32 n; u8 circular = 0; u32 m[n]` records batch by batch in read order from the slabs of both.
-        struct Piece { HostBatch *hb; uint64_t firstRead; uint32_t nReads; std::atomic<int> *left; uint64_t bytes; };    // batch i = reads [firstRead, +nReads) of hb
-        // Where a batch's records go in the file is known once every earlier batch has been purged (their sizes add up); from then on
-        // any thread may build them and write them in place.  (One thread writing the 0.8 GB of a 50 Gbp read set through a stream was
-        // what the pass took: 0.19 s, whatever the purging cost.)
-        const int corrFd = open((tmpDir + "/read_data_corrected.txt").c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
-        if (corrFd < 0) die("cannot write " + tmpDir + "/read_data_corrected.txt");
-        std::map<uint64_t, Piece> placed2;              // purged, not yet given its place: position in read order -> piece
-        std::deque<std::pair<Piece, uint64_t>> ready2;  // placed: piece, file offset
-        uint64_t prefSeq2 = 0, prefOff2 = 0;            // batches [0, prefSeq2) have their place; the file is prefOff2 bytes so far
-        size_t outstanding2 = 0;                        // pieces purged and not yet written
-        bool done2 = false;
-        auto write2 = [&] {
-            std::string rec;
-            for (;;) {
-                Piece pc{};
-                uint64_t at = 0;
-                {
-                    std::unique_lock<std::mutex> lk(fifoMu);
-                    fifoCv.wait(lk, [&] { return !ready2.empty() || (done2 && outstanding2 == 0); });
-                    if (ready2.empty()) return;
-                    pc = ready2.front().first; at = ready2.front().second;
-                    ready2.pop_front();
-                }
-                const HostBatch *hb = pc.hb;
-                const uint64_t r0 = pc.firstRead, r1 = r0 + pc.nReads;
-                // (device records: piece j is the bytes [5 f + 4 off[f], 5 (f + c) + 4 off[f + c]) of the group's slab, f its first read, c its reads)
-                const char *from = hb->rec ? hb->rec + 5 * r0 + 4 * hb->off[r0] : nullptr;
-                if (!from) {
-                    rec.resize((size_t)pc.bytes);
-                    char *dst = &rec[0];
-                    for (uint64_t r = r0; r < r1; r++) {
-                        const uint32_t k = (uint32_t)(hb->off[r + 1] - hb->off[r]);
-                        memcpy(dst, &k, 4); dst[4] = 0;
-                        memcpy(dst + 5, hb->m + hb->off[r], (size_t)k * 4);
-                        dst += 5 + (size_t)k * 4;
-                    }
-                    from = rec.data();
-                }
-                for (size_t done = 0; done < (size_t)pc.bytes;) {
-                    const ssize_t w = pwrite(corrFd, from + done, (size_t)pc.bytes - done, (off_t)(at + done));
-                    if (w < 0) { if (errno == EINTR) continue; die("write to " + tmpDir + "/read_data_corrected.txt failed"); }
-                    done += (size_t)w;
-                }
-                const bool last = pc.left->fetch_sub(1) == 1;           // the slab's last batch
-                if (last) delete pc.left;
-                {
-                    std::lock_guard<std::mutex> lk(fifoMu);
-                    if (last) groupSlabs.push_back(pc.hb);
-                    outstanding2--;
-                }
-                fifoCv.notify_all();
+    return n50;
+}
+
+// purgePalindromes (ReadSelection.hpp:1374-1431) over the minimizers the main pass kept on the device; writes read_data_corrected.txt.
+// A second pass shaped like the first, on GROUPS of batches: a batch is a few thousand reads and 16 k minimizers, and purging them
+// one by one -- two kernels, three waits and two copies each -- was 0.39 ms a batch, 0.18 to 0.23 s of a 50 Gbp FASTA / 20 Gbp FASTQ
+// run.  Every consumer appends the batches its context holds of a group of 32 consecutive ones on the device
+// (mdbg_minimizers_concat), purges them with one call, copies values and offsets back into one page-locked slab, and the writers
+// build the `u32 n; u8 circular = 0; u32 m[n]` records batch by batch in read order from the slabs of both.
+// Where a batch's records go in the file is known once every earlier batch has been purged (their sizes add up); from then on
+// any thread may build them and write them in place.  (One thread writing the 0.8 GB of a 50 Gbp read set through a stream was
+// what the pass took: 0.19 s, whatever the purging cost.)
+struct PurgePass {
+    struct Piece { HostBatch *hb; uint64_t firstRead; uint32_t nReads; std::atomic<int> *left; uint64_t bytes; };    // batch i = reads [firstRead, +nReads) of hb
+    SelectionShared &S;
+    const uint32_t firstK, lastK;
+    const bool keepResident;                        // asmStep: the purged groups stay on the device (S.purgedResident)
+    const std::string path;
+    int fd = -1;
+    // guarded by S.mu
+    std::map<uint64_t, Piece> purged;               // purged, not yet given its place: position in read order -> piece
+    mdbg_host::OrderedPlace place;                  // batches [0, place.next_seq()) have their place
+    std::deque<std::pair<Piece, uint64_t>> ready;   // placed: piece, file offset
+    size_t outstanding = 0;                         // pieces purged and not yet written
+    bool done = false;
+    double pConcat = 0, pPurge = 0, pFree = 0, pSlab = 0, pCopy = 0, pPlace = 0;      // MDBG_TRACE: where the purging threads' time goes
+
+    void write() {
+        std::string rec;
+        for (;;) {
+            Piece pc{};
+            uint64_t at = 0;
+            {
+                std::unique_lock<std::mutex> lk(S.mu);
+                S.cv.wait(lk, [&] { return !ready.empty() || (done && outstanding == 0); });
+                if (ready.empty()) return;
+                pc = ready.front().first; at = ready.front().second;
+                ready.pop_front();
             }
-        };
-        groupSlabsStop = true;
-        if (groupSlabHelper.joinable()) groupSlabHelper.join();
-        if (getenv("MDBG_TRACE")) fprintf(stderr, "[mdbg_tool] %zu of %zu group slabs were allocated beside the main pass\n", groupSlabs.size(), groupSlabsWanted);
+            const HostBatch *hb = pc.hb;
+            const uint64_t r0 = pc.firstRead, r1 = r0 + pc.nReads;
+            // (device records: piece j is the bytes [5 f + 4 off[f], 5 (f + c) + 4 off[f + c]) of the group's slab, f its first read, c its reads)
+            const char *from = hb->rec ? hb->rec + 5 * r0 + 4 * hb->off[r0] : nullptr;
+            if (!from) {
+                rec.resize((size_t)pc.bytes);
+                char *dst = &rec[0];
+                for (uint64_t r = r0; r < r1; r++) {
+                    const uint32_t k = (uint32_t)(hb->off[r + 1] - hb->off[r]);
+                    memcpy(dst, &k, 4); dst[4] = 0;
+                    memcpy(dst + 5, hb->m + hb->off[r], (size_t)k * 4);
+                    dst += 5 + (size_t)k * 4;
+                }
+                from = rec.data();
+            }
+            if (!mdbg_host::pwrite_all(fd, from, (size_t)pc.bytes, at)) die("write to " + path + " failed");
+            const bool last = pc.left->fetch_sub(1) == 1;           // the slab's last batch
+            if (last) delete pc.left;
+            {
+                std::lock_guard<std::mutex> lk(S.mu);
+                if (last) S.groupSlabs.push_back(pc.hb);
+                outstanding--;
+            }
+            S.cv.notify_all();
+        }
+    }
+
+    // consumer ci's share of every group: the batches its context holds
+    void purge_own(int ci) {
+        mdbg_ctx *ctx = S.ctxs[(size_t)ci];
+        std::vector<SelectionShared::Kept> &kept = S.kept;
+        std::vector<const mdbg_minimizers *> parts;
+        std::vector<size_t> idx;
+        std::vector<uint32_t> nReadsOf;
+        double tc = 0, tp = 0, tf = 0, ts = 0, ty = 0, tl = 0;
+        struct Sum { double &a, &b, &c, &d, &e, &f, &A, &B, &C, &D, &E, &F; std::mutex &mu;
+                     ~Sum() { std::lock_guard<std::mutex> g(mu); A += a; B += b; C += c; D += d; E += e; F += f; } }
+            sum{tc, tp, tf, ts, ty, tl, pConcat, pPurge, pFree, pSlab, pCopy, pPlace, S.mu};
+        for (size_t g0 = 0; g0 < kept.size(); g0 += GROUP) {
+            parts.clear(); idx.clear(); nReadsOf.clear();
+            for (size_t i = g0; i < std::min(kept.size(), g0 + GROUP); i++) {
+                if (kept[i].ctx != ctx) continue;
+                uint32_t bn = 0;
+                mdbg_minimizers_info(kept[i].mins, &bn, nullptr);
+                parts.push_back(kept[i].mins); idx.push_back(i); nReadsOf.push_back(bn);
+            }
+            if (parts.empty()) continue;
+            const double t0 = g_trace.now();
+            mdbg_minimizers *all = nullptr, *pur = nullptr;
+            if (parts.size() > 1) check_on(ctx, mdbg_minimizers_concat(ctx, parts.data(), (uint32_t)parts.size(), &all), "mdbg_minimizers_concat");
+            const double t1 = g_trace.now();
+            check_on(ctx, mdbg_purge_palindromes(ctx, all ? all : parts[0], firstK, lastK, &pur), "mdbg_purge_palindromes");
+            const double t2 = g_trace.now();
+            if (all) mdbg_minimizers_free(all);
+            for (size_t i : idx) mdbg_minimizers_free(kept[i].mins);
+            const double t3 = g_trace.now();
+            HostBatch *hb = nullptr;
+            {
+                std::lock_guard<std::mutex> lk(S.mu);
+                if (!S.groupSlabs.empty()) { hb = S.groupSlabs.back(); S.groupSlabs.pop_back(); }
+                else if (!S.spareBatches.empty()) { hb = S.spareBatches.back(); S.spareBatches.pop_back(); }
+            }
+            if (!hb) hb = new HostBatch();
+            uint32_t bn; uint64_t bt;
+            mdbg_minimizers_info(pur, &bn, &bt);
+            if (S.deviceRecords) hb->shape_plain_records(bn, bt, 5 * (uint64_t)bn + 4 * bt);
+            else hb->shape_values(bn, bt);
+            const double t4 = g_trace.now();
+            if (S.deviceRecords) {
+                mdbg_bytes *rb = nullptr;
+                uint64_t nb_rec = 0;
+                check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, pur, MDBG_RECORDS_PLAIN, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
+                if (nb_rec != 5 * (uint64_t)bn + 4 * bt) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a group");
+                check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
+                check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
+                mdbg_bytes_free(rb);
+            } else {
+                check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, hb->m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
+            }
+            if (keepResident) { std::lock_guard<std::mutex> lk(S.mu); S.purgedResident.emplace_back(idx[0], pur); }
+            else mdbg_minimizers_free(pur);
+            const double t5 = g_trace.now();
+            std::atomic<int> *left = new std::atomic<int>((int)idx.size());
+            {
+                std::unique_lock<std::mutex> lk(S.mu);
+                // bounded -- but the group that holds the next batch to be placed always gets in
+                S.cv.wait(lk, [&] { return outstanding < 6 * GROUP || place.next_seq() / GROUP == g0 / GROUP; });
+                uint64_t first = 0;
+                for (size_t j = 0; j < idx.size(); j++) {
+                    const uint64_t bytes = (hb->off[first + nReadsOf[j]] - hb->off[first]) * 4 + (uint64_t)nReadsOf[j] * 5;
+                    purged.emplace((uint64_t)idx[j], Piece{hb, first, nReadsOf[j], left, bytes});
+                    place.add((uint64_t)idx[j], bytes, [this](uint64_t s, uint64_t at) {
+                        auto it = purged.find(s);
+                        ready.emplace_back(it->second, at);
+                        purged.erase(it);
+                    });
+                    first += nReadsOf[j];
+                }
+                outstanding += idx.size();
+            }
+            S.cv.notify_all();
+            tc += t1 - t0; tp += t2 - t1; tf += t3 - t2; ts += t4 - t3; ty += t5 - t4; tl += g_trace.now() - t5;
+        }
+    }
+
+    void run(int threads) {
+        std::sort(S.kept.begin(), S.kept.end(), [](const SelectionShared::Kept &x, const SelectionShared::Kept &y) { return x.seq < y.seq; });
+        fd = open(path.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+        if (fd < 0) die("cannot write " + path);
+        S.groupSlabsStop = true;
+        if (S.groupSlabHelper.joinable()) S.groupSlabHelper.join();
+        if (getenv("MDBG_TRACE")) fprintf(stderr, "[mdbg_tool] %zu of %zu group slabs were allocated beside the main pass\n", S.groupSlabs.size(), S.groupSlabsWanted);
         // (eight, not four: over 50 Gbp the last record was written 0.16 s after the last group had been purged)
-        std::vector<std::thread> writers2;
-        for (int i = 0, nw = std::max(1, std::min(8, a.threads / 4)); i < nw; i++) writers2.emplace_back(write2);
-        double pConcat = 0, pPurge = 0, pFree = 0, pSlab = 0, pCopy = 0, pPlace = 0;      // MDBG_TRACE: where the purging threads' time goes
-        auto purge_own = [&](int ci) {
-            mdbg_ctx *ctx = ctxs[(size_t)ci];
-            std::vector<const mdbg_minimizers *> parts;
-            std::vector<size_t> idx;
-            std::vector<uint32_t> nReadsOf;
-            double tc = 0, tp = 0, tf = 0, ts = 0, ty = 0, tl = 0;
-            struct Sum { double &a, &b, &c, &d, &e, &f, &A, &B, &C, &D, &E, &F; std::mutex &mu;
-                         ~Sum() { std::lock_guard<std::mutex> g(mu); A += a; B += b; C += c; D += d; E += e; F += f; } }
-                sum{tc, tp, tf, ts, ty, tl, pConcat, pPurge, pFree, pSlab, pCopy, pPlace, fifoMu};
-            for (size_t g0 = 0; g0 < kept.size(); g0 += GROUP) {
-                parts.clear(); idx.clear(); nReadsOf.clear();
-                for (size_t i = g0; i < std::min(kept.size(), g0 + GROUP); i++) {
-                    if (kept[i].ctx != ctx) continue;
-                    uint32_t bn = 0;
-                    mdbg_minimizers_info(kept[i].mins, &bn, nullptr);
-                    parts.push_back(kept[i].mins); idx.push_back(i); nReadsOf.push_back(bn);
-                }
-                if (parts.empty()) continue;
-                const double t0 = g_trace.now();
-                mdbg_minimizers *all = nullptr, *pur = nullptr;
-                if (parts.size() > 1) check_on(ctx, mdbg_minimizers_concat(ctx, parts.data(), (uint32_t)parts.size(), &all), "mdbg_minimizers_concat");
-                const double t1 = g_trace.now();
-                check_on(ctx, mdbg_purge_palindromes(ctx, all ? all : parts[0], (uint32_t)P.firstK, (uint32_t)lastK, &pur), "mdbg_purge_palindromes");
-                const double t2 = g_trace.now();
-                if (all) mdbg_minimizers_free(all);
-                for (size_t i : idx) mdbg_minimizers_free(kept[i].mins);
-                const double t3 = g_trace.now();
-                HostBatch *hb = nullptr;
-                {
-                    std::lock_guard<std::mutex> lk(fifoMu);
-                    if (!groupSlabs.empty()) { hb = groupSlabs.back(); groupSlabs.pop_back(); }
-                    else if (!spareBatches.empty()) { hb = spareBatches.back(); spareBatches.pop_back(); }
-                }
-                if (!hb) hb = new HostBatch();
-                uint32_t bn; uint64_t bt;
-                mdbg_minimizers_info(pur, &bn, &bt);
-                if (deviceRecords) hb->shape_plain_records(bn, bt, 5 * (uint64_t)bn + 4 * bt);
-                else hb->shape_values(bn, bt);
-                const double t4 = g_trace.now();
-                if (deviceRecords) {
-                    mdbg_bytes *rb = nullptr;
-                    uint64_t nb_rec = 0;
-                    check_on(ctx, mdbg_minimizers_to_record_bytes(ctx, pur, MDBG_RECORDS_PLAIN, &rb, &nb_rec), "mdbg_minimizers_to_record_bytes");
-                    if (nb_rec != 5 * (uint64_t)bn + 4 * bt) die("internal error: mdbg_minimizers_to_record_bytes made " + std::to_string(nb_rec) + " bytes of a group");
-                    check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
-                    check_on(ctx, mdbg_bytes_download(ctx, rb, 0, hb->rec, nb_rec), "mdbg_bytes_download");
-                    mdbg_bytes_free(rb);
-                } else {
-                    check_on(ctx, mdbg_minimizers_to_host(ctx, pur, hb->off, hb->m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "to_host");
-                }
-                if (a.thenGraph) { std::lock_guard<std::mutex> lk(fifoMu); purgedResident.emplace_back(idx[0], pur); }
-                else mdbg_minimizers_free(pur);
-                const double t5 = g_trace.now();
-                std::atomic<int> *left = new std::atomic<int>((int)idx.size());
-                {
-                    std::unique_lock<std::mutex> lk(fifoMu);
-                    // bounded -- but the group that holds the next batch to be placed always gets in
-                    fifoCv.wait(lk, [&] { return outstanding2 < 6 * GROUP || prefSeq2 / GROUP == g0 / GROUP; });
-                    uint64_t first = 0;
-                    for (size_t j = 0; j < idx.size(); j++) {
-                        const uint64_t bytes = (hb->off[first + nReadsOf[j]] - hb->off[first]) * 4 + (uint64_t)nReadsOf[j] * 5;
-                        placed2.emplace((uint64_t)idx[j], Piece{hb, first, nReadsOf[j], left, bytes});
-                        first += nReadsOf[j];
-                    }
-                    outstanding2 += idx.size();
-                    for (auto it = placed2.find(prefSeq2); it != placed2.end(); it = placed2.find(prefSeq2)) {
-                        ready2.emplace_back(it->second, prefOff2);
-                        prefOff2 += it->second.bytes;
-                        placed2.erase(it);
-                        prefSeq2++;
-                    }
-                }
-                fifoCv.notify_all();
-                tc += t1 - t0; tp += t2 - t1; tf += t3 - t2; ts += t4 - t3; ty += t5 - t4; tl += g_trace.now() - t5;
-            }
-        };
+        std::vector<std::thread> writers;
+        for (int i = 0, nw = std::max(1, std::min(8, threads / 4)); i < nw; i++) writers.emplace_back([this] { write(); });
         std::vector<std::thread> purgers;
-        for (int i = 1; i < nConsumers; i++) purgers.emplace_back(purge_own, i);
+        for (int i = 1; i < S.nConsumers; i++) purgers.emplace_back([this, i] { purge_own(i); });
         purge_own(0);
         for (auto &t : purgers) t.join();
         {
-            std::lock_guard<std::mutex> lk(fifoMu);
-            done2 = true;
+            std::lock_guard<std::mutex> lk(S.mu);
+            done = true;
         }
-        fifoCv.notify_all();
+        S.cv.notify_all();
         g_trace.mark("purge pass: every batch purged");
-        for (auto &t : writers2) t.join();
+        for (auto &t : writers) t.join();
         if (getenv("MDBG_TRACE"))
             fprintf(stderr, "[mdbg_tool] purge pass, summed over the %d purging thread(s): appending the batches of a group %.3f s, purging %.3f s, freeing %.3f s, "
-                            "page-locked slab %.3f s, copy back %.3f s, waiting for a place %.3f s\n", nConsumers, pConcat, pPurge, pFree, pSlab, pCopy, pPlace);
-        if (prefSeq2 != kept.size()) die("internal error: a purged batch was never placed");
-        if (close(corrFd) != 0) die("closing " + tmpDir + "/read_data_corrected.txt failed");
+                            "page-locked slab %.3f s, copy back %.3f s, waiting for a place %.3f s\n", S.nConsumers, pConcat, pPurge, pFree, pSlab, pCopy, pPlace);
+        if (place.next_seq() != S.kept.size()) die("internal error: a purged batch was never placed");
+        if (close(fd) != 0) die("closing " + path + " failed");
+    }
+};
+
+// asmStep: `graph --firstpass` follows in this process on the corrected reads as they sit on the device, in the order of the file (what
+// order they are counted in changes nothing: the tables are multisets; it is kept all the same)
+[[noreturn]] void hand_over_to_graph(SelectionShared &S, Args a, const std::string &tmpDir) {
+    std::sort(S.purgedResident.begin(), S.purgedResident.end());
+    std::vector<const mdbg_minimizers *> parts;
+    for (auto &pr : S.purgedResident) parts.push_back(pr.second);
+    mdbg_minimizers *all = nullptr;
+    if (parts.size() == 1) all = S.purgedResident[0].second;
+    else if (parts.size() > 1) {
+        check(mdbg_minimizers_concat(g_ctx, parts.data(), (uint32_t)parts.size(), &all), "mdbg_minimizers_concat");
+        for (auto &pr : S.purgedResident) mdbg_minimizers_free(pr.second);
+    }
+    g_trace.mark("asmStep: the corrected reads appended on the device");
+    a.firstPass = true;
+    a.pos = {tmpDir};
+    graph_main(a, tmpDir, all);        // (all == null: no read at all -- the file path handles that like the reference does)
+}
+
+// How many consumers, with which contexts, and what the environment asks of them.
+// --gpus G: one consumer per device; batches go to the consumers in turn, every batch is scanned (and later purged) where it
+// landed, and the ordered writer, N50 and read_stats.txt see the batches in read order whatever device produced them
+// (contiguous read ranges, stats reduced on the host).
+// two consumers per device by default: with the parsers packing on 12 threads it is the consumer -- upload, scan, download, hand-over,
+// per batch of a few thousand reads -- that a 50 Gbp pass waits for (round 3: the parsers were idle 60 % of the time);
+// MDBG_TOOL_CONSUMERS=1..4 per device is there for other inputs (profiles/r01f_tool_consumers.json).
+void set_up_consumers(SelectionShared &S, const Args &a, const std::string &inputList) {
+    S.nConsumers = std::max(1, a.gpus) * (a.threads >= 8 ? 2 : 1);
+    if (const char *e = getenv("MDBG_TOOL_CONSUMERS")) S.nConsumers = std::max(std::max(1, a.gpus), std::min(4 * std::max(1, a.gpus), atoi(e)));
+    // how many group slabs: what the purge pass can have in flight (six groups' pieces waiting for the writers, one being filled, per
+    // consumer) -- of a long input.  A short one (10 Gbp: ten groups) gets a third of its groups' worth: pinning 200 MB beside a main pass
+    // of 0.25 s measured no faster than growing slabs on the way (0.53 against 0.50 s inside the tool, ten runs each, noise as large)
+    uint64_t inputBytes = 0;
+    for (const std::string &f : read_input_list(inputList)) { struct stat st; if (stat(f.c_str(), &st) == 0) inputBytes += (uint64_t)st.st_size; }
+    const uint64_t groups = inputBytes / ((uint64_t)std::max<size_t>(1, a.batchBases) * GROUP);
+    S.groupSlabsWanted = (size_t)std::min<uint64_t>(7 * (uint64_t)S.nConsumers + 2, groups * (uint64_t)S.nConsumers / 3);
+    if (const char *e = getenv("MDBG_TOOL_DEVICE_RECORDS")) {
+        if (atoi(e) != 0) {
+            S.deviceRecords = mdbg_minimizers_to_record_bytes && mdbg_bytes_download;
+            g_trace.mark(S.deviceRecords ? "device records: the records of read_data_init.txt and read_data_corrected.txt are composed on the device (mdbg_minimizers_to_record_bytes)"
+                                         : "device records: falling back to the host builders: the library has no mdbg_minimizers_to_record_bytes or mdbg_bytes_download");
+        }
+    }
+    S.ctxs.assign(1, g_ctx);
+    for (int i = 1; i < S.nConsumers; i++) {
+        mdbg_ctx *c = nullptr;
+        if (mdbg_create(i % std::max(1, a.gpus), &c) != MDBG_OK) die(std::string("mdbg_create(device ") + std::to_string(i % a.gpus) + "): " + mdbg_last_error(nullptr));
+        S.ctxs.push_back(c);
+        g_more_ctx.push_back(c);
+    }
+}
+
+// (asmStep = true: `mdbg_tool asmStep <the arguments of readSelection> [--min-abundance M]` -- this command and `graph --firstpass` in ONE
+// process: the reference's pipeline runs them as two children one after the other, pipeline/AssemblyPipeline.hpp:716-740 and :763-792; here the
+// second finds the library context alive and the corrected minimizers still on the device instead of creating one and parsing
+// read_data_corrected.txt back.  Every file of both commands is written as by the two of them.)
+int run_read_selection(int argc, char **argv, bool asmStep = false) {
+    Args a = parse_args(argc, argv, 2);
+    a.thenGraph = asmStep;
+    if (a.pos.size() != 3) die(std::string("usage: mdbg_tool ") + (asmStep ? "asmStep" : "readSelection") + " <tmpDir> <outFile> <inputList> --threads N --min-read-quality F [--skip-correction]" +
+                               (asmStep ? " [--min-abundance M]" : ""));
+    if (asmStep && a.gpus > 1) die("asmStep runs on one device; with --gpus G use the two commands readSelection and graph");
+    const std::string tmpDir = a.pos[0], outFile = a.pos[1], inputList = a.pos[2];
+    Parameters P;
+    P.load(tmpDir + "/parameters.gz");
+    g_log.open(tmpDir);
+    g_log.line("mdbg_tool readSelection (MI355X) " + inputList);
+    check(mdbg_create(0, &g_ctx), "mdbg_create");
+    g_trace.mark("context created");
+
+    const std::vector<uint32_t> rep = census_repetitive(P, a, tmpDir, inputList);
+
+    // main pass: read_data_init.txt in read order (ReadSelection.hpp:386-491)
+    const int outFd = open(outFile.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (outFd < 0) die("cannot write " + outFile);
+    SelectionShared S;
+    S.needCorrected = P.hpc || a.skipCorrection;
+    if (a.thenGraph && !S.needCorrected) die("asmStep: without --skip-correction an ONT read set goes through the reference's read correction before `graph` (not part of this tool)");
+    set_up_consumers(S, a, inputList);
+    RecordSink sink(S, outFd, outFile, P.minimizerSize);
+    sink.start(a.threads);
+    scan_all_batches(S, sink, P, rep, a, inputList);
+    sink.finish();
+    g_trace.mark("main pass done (parse + scan + read_data_init.txt)");
+
+    const uint32_t n50 = write_read_stats(sink, tmpDir);
+    if (S.needCorrected) {
+        // lastK from the N50, --max-k ignored
+        PurgePass purge{S, (uint32_t)P.firstK, (uint32_t)compute_last_k(P.densityAssembly, n50, P.firstK, 0), a.thenGraph, tmpDir + "/read_data_corrected.txt"};
+        purge.run(a.threads);
     }
     g_trace.mark("read_data_corrected.txt written");
-    if (a.thenGraph) {
-        // the corrected reads as they sit on the device, in the order of the file (what order they are counted in changes nothing: the
-        // tables are multisets; it is kept all the same)
-        std::sort(purgedResident.begin(), purgedResident.end());
-        std::vector<const mdbg_minimizers *> parts;
-        for (auto &pr : purgedResident) parts.push_back(pr.second);
-        mdbg_minimizers *all = nullptr;
-        if (parts.size() == 1) all = purgedResident[0].second;
-        else if (parts.size() > 1) {
-            check(mdbg_minimizers_concat(g_ctx, parts.data(), (uint32_t)parts.size(), &all), "mdbg_minimizers_concat");
-            for (auto &pr : purgedResident) mdbg_minimizers_free(pr.second);
-        }
-        g_trace.mark("asmStep: the corrected reads appended on the device");
-        a.firstPass = true;
-        a.pos = {tmpDir};
-        graph_main(a, tmpDir, all);        // (all == null: no read at all -- the file path handles that like the reference does)
-    }
+    if (a.thenGraph) hand_over_to_graph(S, a, tmpDir);
     write_perf(tmpDir);
     g_trace.mark("done");
     finish();
@@ -1818,13 +1425,7 @@ void stream_table_to_files(mdbg_ctx *ctx, mdbg_table *table, uint32_t k, const s
         check_on(ctx, mdbg_host_alloc(ctx, std::min(n, piece) * 20, &p), "mdbg_host_alloc"); b.rec = (uint8_t *)p;
         if (vec) { check_on(ctx, mdbg_host_alloc(ctx, std::min(n, piece) * k * 4, &p), "mdbg_host_alloc"); b.vec = (uint32_t *)p; }
     }
-    auto put = [](int fd, const void *data, size_t bytes, uint64_t at) {
-        for (size_t done = 0; done < bytes;) {
-            const ssize_t w = pwrite(fd, (const char *)data + done, bytes - done, (off_t)(at + done));
-            if (w < 0) { if (errno == EINTR) continue; die("writing a table file failed"); }
-            done += (size_t)w;
-        }
-    };
+    auto put = [](int fd, const void *data, size_t bytes, uint64_t at) { if (!mdbg_host::pwrite_all(fd, data, bytes, at)) die("writing a table file failed"); };
     std::vector<std::thread> writers;           // of the piece before the one coming down
     for (uint64_t first = 0, i = 0; first < n; first += piece, i++) {
         const uint64_t cnt = std::min(piece, n - first);
