@@ -370,7 +370,14 @@ int  mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]);
  * "scan_lds_reserve" > 0 whose last block-kernel scan was a persistent launch ("scan_persistent"): those workgroups never retire to let an eight-wave block
  * in, and beside them the four-wave forms measured faster.  Results never depend on it.
  * mdbg_first_pass_form tells which form the context's last split kernels took: form[0] = threads per block, [1] = records per tile,
- * [2] and [3] = 0.
+ * [2] = the wave priority the context's last purge, first-pass or prefix-scan kernel was launched with (below), [3] = 0.
+ * "table_wave_priority" (MDBG_TABLE_WAVE_PRIORITY sets it for new contexts): the hardware issue priority, 0 .. 3 (other values are
+ * clamped, as for "scan_wave_priority", which does the same for the scan's waves), that the waves of every kernel a step launches
+ * outside the scan raise themselves to on entry: mdbg_purge_palindromes, the partitioned mdbg_kminmer_count_first / mdbg_shard_begin
+ * and the prefix scans they use.  These kernels wait on memory; beside another context's scan, whose waves are bound by instruction
+ * issue and are the oldest on their SIMD for a whole launch, they otherwise get the issue slots the scan leaves, and crawl
+ * (DESIGN.md 4.4).  Where the option was never set a context takes 1 if it shares its device ("scan_lds_reserve" > 0) and 0 if not;
+ * setting it, to 0 too, overrides that.  Results never depend on it.
  * mdbg_first_pass_slot_fall_backs: the instances of the last partitioned first pass whose LDS slot the bucket count looked up a second
  * time.  Counting a bucket walks its records twice (count, then a byte per instance of a rare key); the form without a slot list keeps
  * the slots of a bucket's first 8192 records in registers between the walks, the form with one those of its first 8000 (4096 beside 2048

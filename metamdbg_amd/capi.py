@@ -243,6 +243,13 @@ class Context:
         self.check(lib().mdbg_first_pass_form(self.h, a))
         return {"split_threads": int(a[0]), "split_tile": int(a[1])}
 
+    def table_wave_priority(self) -> int:
+        """The wave priority this context's last purge, first-pass or prefix-scan kernel was launched with ("table_wave_priority";
+        mdbg_first_pass_form, form[2])."""
+        a = (C.c_uint64 * 4)()
+        self.check(lib().mdbg_first_pass_form(self.h, a))
+        return int(a[2])
+
     def first_pass_slot_fall_backs(self) -> int:
         """Instances of the last partitioned first pass whose LDS slot the bucket count looked up a second time
         (mdbg_first_pass_slot_fall_backs)."""

@@ -143,6 +143,8 @@ struct mdbg_ctx {
     unsigned scan_reads_per_wave = 0;                      // reads a scan wave processes before it retires (mdbg_set_option); 0 = each kernel's own: 2 for the
                                                            // four-wave and the general kernels, up to 32 by the batch's size for the pre-filtered variant (scan.hip)
     uint32_t scan_wave_priority = 0;        // s_setprio level of the block-structured scan's waves (mdbg_set_option)
+    uint32_t table_wave_priority = 0;       // "table_wave_priority": s_setprio level of the purge's, the first pass's and the prefix scans' waves (raise_wave_priority),
+    bool table_wave_priority_set = false;   // once set by option or MDBG_TABLE_WAVE_PRIORITY; until then the context's own default (mdbg::table_priority)
     int test_exchange_fail_phase = 0;       // tests: this rank fails in phase 1 (before the counts) / 2 (buffers) / 3 (reduction) of the next exchange
     bool test_corrupt_replies = false;      // tests: the next exchange hands back one reply with a wrong count (the job's self-check must see it)
     uint32_t scan_cand_slack = 0;           // tests: widens the candidate test of the block-structured scan (see span_step)
@@ -193,7 +195,8 @@ struct mdbg_ctx {
     uint32_t part_tile = 0;                 // 2048: the scatter regroups tiles of 2048 records (24 KB of LDS instead of 43), else 4096
     uint32_t part_threads = 0;              // threads per block of the split kernels: 0 or 512 = eight waves; 256 = four waves, tiles of 1024 records (fits beside a
                                             // 16-wave scan workgroup by registers, measured slower there: DESIGN.md 4.4; for that comparison and for tests)
-    uint64_t part_form[4] = {0};            // mdbg_first_pass_form: [0] threads per block, [1] records per tile of the split kernels last launched
+    uint64_t part_form[4] = {0};            // mdbg_first_pass_form: [0] threads per block, [1] records per tile of the split kernels last launched,
+                                            // [2] the wave priority the context's last purge / first-pass / prefix-scan kernel was launched with
     uint64_t part_fell_back = 0;            // last partitioned first pass: instances whose LDS slot bucket_count looked up a second time (mdbg_first_pass_slot_fall_backs)
     uint32_t part_slot_list = 1;            // 0: bucket_count keeps no slot list (24 KB of LDS per 1024-slot bucket instead of 40)
     uint32_t scan_lds_pad = 0;              // bytes of unused dynamic LDS per block of the block-structured scan: caps its blocks per CU and so
@@ -329,9 +332,30 @@ inline unsigned grid_for(uint64_t items, unsigned per_block, unsigned max_blocks
     return (unsigned)b;
 }
 
+// The wave priority the kernels outside the scan are launched with: the option's where it was set; otherwise TABLE_WAVE_PRIORITY_SHARED in a
+// context that shares its device ("scan_lds_reserve" > 0, the condition of the four-wave split kernels) and 0 in every other.  Every launch
+// asks here, so part_form[2] is the level that ran.  1: one above the scan's own 0 is all it takes -- 1, 2 and 3 measured alike, + 13 % of the
+// benchmark's step each (profiles/table_priority_bench_alternating.txt) -- and leaves two levels above it free.
+constexpr uint32_t TABLE_WAVE_PRIORITY_SHARED = 1;
+inline uint32_t table_priority(mdbg_ctx *ctx) {
+    const uint32_t level = ctx->table_wave_priority_set ? ctx->table_wave_priority : (ctx->scan_lds_reserve ? TABLE_WAVE_PRIORITY_SHARED : 0u);
+    ctx->part_form[2] = level;
+    return level;
+}
+
 // ---- device-side wave64 helpers -----------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ unsigned lane_id() { return __lane_id(); }
+
+// Raises the calling wave's issue priority ("table_wave_priority"): at the entry of the kernels a step launches outside the scan, which wait
+// on memory beside another context's issue-bound scan waves.  `level` is a kernel argument, the same for every lane, so each
+// test is a scalar branch round one s_setprio with a constant; the instruction ignores the lane mask and must not sit behind a condition that
+// differs between lanes.  Only for kernels that run to completion by themselves: none of them waits for what another wave writes.
+__device__ __forceinline__ void raise_wave_priority(uint32_t level) {
+    if (level == 1u) __builtin_amdgcn_s_setprio(1);
+    else if (level == 2u) __builtin_amdgcn_s_setprio(2);
+    else if (level >= 3u) __builtin_amdgcn_s_setprio(3);
+}
 
 // Order LDS traffic between the lanes of ONE wavefront (waves of a block run independent reads,
 // so __syncthreads() is not usable inside the per-read loops).

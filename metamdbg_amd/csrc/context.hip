@@ -64,6 +64,7 @@ extern "C" int mdbg_create(int device, mdbg_ctx **out) try {
     // defaults of the per-context options from the environment (mdbg_set_option changes them later)
     if (const char *e = getenv("MDBG_TABLE_BLOCKS_PER_CU")) if (atoi(e) > 0) ctx->table_blocks_per_cu = (unsigned)atoi(e);
     if (const char *e = getenv("MDBG_SCAN_WAVE_PRIORITY")) ctx->scan_wave_priority = (uint32_t)std::max(0, std::min(3, atoi(e)));
+    if (const char *e = getenv("MDBG_TABLE_WAVE_PRIORITY")) { ctx->table_wave_priority = (uint32_t)std::max(0, std::min(3, atoi(e))); ctx->table_wave_priority_set = true; }
     if (const char *e = getenv("MDBG_SCAN_READS_PER_WAVE")) if (atoi(e) > 0) ctx->scan_reads_per_wave = (unsigned)atoi(e);
     if (const char *e = getenv("MDBG_SCAN_LDS_RESERVE")) ctx->scan_lds_reserve = (uint32_t)std::max(0, std::min(131072, atoi(e)));
     if (const char *e = getenv("MDBG_SCAN_PREFILTER")) ctx->scan_prefilter = atoi(e) != 0;
@@ -190,6 +191,7 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
     if (n == "table_grid_blocks") { ctx->table_grid_blocks = value > 0 ? (unsigned)std::min<int64_t>(value, 1 << 20) : 0u; return MDBG_OK; }
     if (n == "table_blocks_per_cu") { ctx->table_blocks_per_cu = value > 0 ? (unsigned)std::min<int64_t>(value, 1024) : 1024u; return MDBG_OK; }
     if (n == "scan_wave_priority") { ctx->scan_wave_priority = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(3, value)); return MDBG_OK; }
+    if (n == "table_wave_priority") { ctx->table_wave_priority = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(3, value)); ctx->table_wave_priority_set = true; return MDBG_OK; }
     if (n == "scan_candidate_slack") { ctx->scan_cand_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 1 << 24) : 0u; return MDBG_OK; }
     if (n == "scan_guard_slack") { ctx->scan_guard_slack = value > 0 ? (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll - 68) : 0u; return MDBG_OK; }
     if (n == "scan_prefilter") { ctx->scan_prefilter = value != 0; return MDBG_OK; }

@@ -32,7 +32,8 @@ struct ReadSpans {
 };
 
 __global__ __launch_bounds__(256) void purge_detect_kernel(ReadSpans sp, uint32_t n_reads, const uint32_t *mins,
-                                                           uint32_t *new_count, uint32_t *list, uint32_t *n_list) {
+                                                           uint32_t *new_count, uint32_t *list, uint32_t *n_list, uint32_t prio) {
+    raise_wave_priority(prio);
     const unsigned sub = threadIdx.x & 15u;
     const unsigned gshift = (threadIdx.x & 63u) & ~15u;           // first lane of this 16-lane group in the wave
     const uint64_t group = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -109,7 +110,8 @@ constexpr uint32_t PURGE_FIX_THREADS = 16;
 // `fixed`: `work` holds nothing else (round 4: it used to be a copy of the whole input, 1.5 GB and 2.3 ms per 10 M reads, made for the
 // hundred thousand reads this kernel looks at).
 __global__ __launch_bounds__(PURGE_FIX_THREADS) void purge_fix_kernel(ReadSpans sp, const uint32_t *list, uint32_t n_list, const uint32_t *src, uint32_t *work,
-                                                                      uint8_t *fixed, uint32_t first_k, uint32_t last_k, uint32_t *new_count) {
+                                                                      uint8_t *fixed, uint32_t first_k, uint32_t last_k, uint32_t *new_count, uint32_t prio) {
+    raise_wave_priority(prio);
     __shared__ uint32_t stage[PURGE_FIX_THREADS][PURGE_LDS_MAX + 1];
     uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n_list) return;
@@ -133,7 +135,8 @@ __global__ __launch_bounds__(PURGE_FIX_THREADS) void purge_fix_kernel(ReadSpans 
 // 16 lanes per read: a chain of dependent loads per read, so reads in flight are what it runs on
 // (fixed, alt: the reads marked in `fixed` come from `alt` -- the purged rows -- instead of `src`; both null: all from `src`)
 __global__ __launch_bounds__(256) void gather_prefix_kernel(const uint64_t *src_off, const uint64_t *dst_off, uint32_t n_reads,
-                                                            const uint32_t *src, uint32_t *dst, const uint8_t *fixed = nullptr, const uint32_t *alt = nullptr) {
+                                                            const uint32_t *src, uint32_t *dst, uint32_t prio, const uint8_t *fixed = nullptr, const uint32_t *alt = nullptr) {
+    raise_wave_priority(prio);
     const unsigned lane = threadIdx.x & 15u;
     const uint64_t group = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) >> 4;
@@ -725,10 +728,11 @@ extern "C" int mdbg_purge_palindromes(mdbg_ctx *ctx, const mdbg_minimizers *in, 
     // the input as it is: CSR, or the scattered rows of a fresh scan output (which this step then puts in CSR order: the copy it
     // makes anyway is a gather)
     const ReadSpans sp = in->scattered ? ReadSpans{in->d_begin.p, nullptr, in->d_cnt.p} : ReadSpans{in->d_off.p, in->d_off.p + 1, nullptr};
+    const uint32_t prio = table_priority(ctx);
     if (n) {
         LaunchTimer timer(ctx, "purge_palindromes");
         unsigned blocks = grid_for((uint64_t)n * 16, 256, (unsigned)ctx->n_cu * 16u);
-        hipLaunchKernelGGL(purge_detect_kernel, dim3(blocks), dim3(256), 0, ctx->stream, sp, n, in->d_min.p, cnt.p, list.p, n_list.p);
+        hipLaunchKernelGGL(purge_detect_kernel, dim3(blocks), dim3(256), 0, ctx->stream, sp, n, in->d_min.p, cnt.p, list.p, n_list.p, prio);
     }
     uint32_t n_suspect = 0;
     hipError_t e = memcpy_sync(ctx, &n_suspect, n_list.p, 4, hipMemcpyDeviceToHost);
@@ -741,7 +745,7 @@ extern "C" int mdbg_purge_palindromes(mdbg_ctx *ctx, const mdbg_minimizers *in, 
         if (in->scattered) {
             if ((rc = exclusive_scan_u32(ctx, cnt.p, m->d_off.p, n))) return fail(rc);
             LaunchTimer timer(ctx, "purge_palindromes");
-            if (n) hipLaunchKernelGGL(gather_prefix_kernel, dim3(gblocks), dim3(256), 0, ctx->stream, in->d_begin.p, m->d_off.p, n, in->d_min.p, m->d_min.p);
+            if (n) hipLaunchKernelGGL(gather_prefix_kernel, dim3(gblocks), dim3(256), 0, ctx->stream, in->d_begin.p, m->d_off.p, n, in->d_min.p, m->d_min.p, prio);
         } else {
             LaunchTimer timer(ctx, "purge_palindromes");
             e = hipMemcpyAsync(m->d_off.p, in->d_off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream);
@@ -760,7 +764,7 @@ extern "C" int mdbg_purge_palindromes(mdbg_ctx *ctx, const mdbg_minimizers *in, 
             e = hipMemsetAsync(fixed.p, 0, n, ctx->stream);
             if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "purge memset failed: %s", hipGetErrorString(e)));
             hipLaunchKernelGGL(purge_fix_kernel, dim3(grid_for(n_suspect, PURGE_FIX_THREADS)), dim3(PURGE_FIX_THREADS), 0, ctx->stream, sp, list.p, n_suspect,
-                               in->d_min.p, work.p, fixed.p, first_k, last_k, cnt.p);
+                               in->d_min.p, work.p, fixed.p, first_k, last_k, cnt.p, prio);
         }
         if ((rc = exclusive_scan_u32(ctx, cnt.p, m->d_off.p, n))) return fail(rc);
         e = memcpy_sync(ctx, &m->n_min, m->d_off.p + n, 8, hipMemcpyDeviceToHost);
@@ -770,7 +774,7 @@ extern "C" int mdbg_purge_palindromes(mdbg_ctx *ctx, const mdbg_minimizers *in, 
         if ((rc = m->d_min.alloc(ctx, m->n_min))) return fail(rc);
         {
             LaunchTimer timer(ctx, "purge_palindromes");
-            hipLaunchKernelGGL(gather_prefix_kernel, dim3(gblocks), dim3(256), 0, ctx->stream, sp.begin, m->d_off.p, n, in->d_min.p, m->d_min.p, fixed.p, work.p);
+            hipLaunchKernelGGL(gather_prefix_kernel, dim3(gblocks), dim3(256), 0, ctx->stream, sp.begin, m->d_off.p, n, in->d_min.p, m->d_min.p, prio, fixed.p, work.p);
         }
         e = hipStreamSynchronize(ctx->stream);   // `work` goes back to the pool on return
         if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "purge failed: %s", hipGetErrorString(e)));

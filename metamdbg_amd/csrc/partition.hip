@@ -75,6 +75,7 @@ struct SplitArgs {
     uint32_t shift, ways;                              // digit = (hash_lo >> shift) & (ways - 1); level 1: the top bits of window_mix
     uint32_t mix_bits;                                 // level 1: log2(ways) (digit = window_mix >> (64 - mix_bits); 0 bits: one way)
     uint8_t *hll;                                      // level-1 histogram: HLL_M registers per block, see hll_estimate (null: not wanted)
+    uint32_t prio;                                     // wave priority of the split kernels ("table_wave_priority": raise_wave_priority)
 };
 
 // How many distinct keys are there?  The plan (buckets so that a bucket's keys fit its LDS table) needs to know before the first
@@ -83,7 +84,8 @@ struct SplitArgs {
 // the mix, value = position of the first set bit of 56 others; one LDS atomic max per instance): 2048 registers, standard error 2.3 %.
 constexpr uint32_t HLL_P = 11, HLL_M = 1u << HLL_P;
 
-__global__ __launch_bounds__(256) void mark_starts_kernel(const uint64_t *off, uint32_t n_reads, uint32_t *bits) {
+__global__ __launch_bounds__(256) void mark_starts_kernel(const uint64_t *off, uint32_t n_reads, uint32_t *bits, uint32_t prio) {
+    raise_wave_priority(prio);
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_reads) return;                           // off[n_reads] = n_min: the end is a start, too
     const uint64_t p = off[r];
@@ -144,6 +146,7 @@ __device__ __forceinline__ void split_range(const SplitArgs &a, uint32_t &seg, u
 // and entry (seg * ways + digit) * blocks_per_seg the start of bucket seg * ways + digit
 template <bool FROM_MINS, uint32_t NT>
 __global__ __launch_bounds__(NT) void split_hist_kernel(SplitArgs a, uint32_t *hist) {
+    raise_wave_priority(a.prio);
     __shared__ uint32_t h[PART_MAXW];
     __shared__ uint32_t sketch[FROM_MINS ? HLL_M : 1];
     const bool sketching = FROM_MINS && a.hll != nullptr;
@@ -187,7 +190,8 @@ __global__ __launch_bounds__(NT) void split_hist_kernel(SplitArgs a, uint32_t *h
 }
 
 // (64 slices of the blocks per register, merged by atomic max: one thread per register walking all 2048 blocks took 0.8 ms)
-__global__ __launch_bounds__(256) void hll_merge_kernel(const uint8_t *per_block, uint32_t n_blocks, uint32_t *merged) {
+__global__ __launch_bounds__(256) void hll_merge_kernel(const uint8_t *per_block, uint32_t n_blocks, uint32_t *merged, uint32_t prio) {
+    raise_wave_priority(prio);
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= HLL_M) return;
     uint32_t m = 0;
@@ -199,6 +203,7 @@ __global__ __launch_bounds__(256) void hll_merge_kernel(const uint8_t *per_block
 // itself, 4 (24 KB of LDS instead of 43) when it is to fit beside another context's scan blocks (mdbg_set_option "partition_tile")
 template <bool FROM_MINS, uint32_t E, uint32_t NT>
 __global__ __launch_bounds__(NT) void split_scatter_kernel(SplitArgs a, const uint64_t *place, RecView out) {
+    raise_wave_priority(a.prio);
     constexpr uint32_t TILE = NT * E;
     __shared__ unsigned long long stage[TILE];         // one field of the tile's records at a time, grouped by digit
     __shared__ uint8_t stage_digit[TILE];
@@ -350,7 +355,7 @@ constexpr uint32_t BC_KEEP_TRIPS = 4;
 template <uint32_t C, uint32_t LIST>
 __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const uint64_t *pos, uint32_t stride, uint32_t min_abundance, uint32_t clip,
                                                            int keep_all, RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept,
-                                                           uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow, uint32_t *fell_back) {
+                                                           uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow, uint32_t *fell_back, uint32_t prio) {
     __shared__ LdsTable<C> t;
     constexpr uint32_t PART_SLOTLIST = LIST;           // 0: none (24 bytes of LDS per slot and nothing else: fits beside a scan)
     constexpr uint32_t KEEP_TRIPS = LIST ? 0u : BC_KEEP_TRIPS;
@@ -361,6 +366,9 @@ __global__ __launch_bounds__(BC_NT) void bucket_count_kernel(RecView in, const u
     const uint64_t n = s1 - s0;
     for (uint32_t s = tid; s < C; s += BC_NT) { t.lo[s] = 0ull; t.hi[s] = 0ull; t.cnt[s] = 0u; }
     if (tid == 0) { kept = 0; occupied = 0; }
+    // (here, not in front of the table's zeroing: as the first statement it cost the kernel four vector registers -- 50 for 46, 56 allocated, and
+    // two waves a SIMD of those do not fit the 96 a scan workgroup leaves)
+    raise_wave_priority(prio);
     __syncthreads();
     // a pass in which some bucket outgrew its table is void and will be repeated: the rest of it is not worth running (a full table
     // costs every further record a walk over all its slots: 115 ms once for a pass of 4)
@@ -480,10 +488,11 @@ __device__ __forceinline__ void store_vector(const uint32_t *m, uint32_t k, bool
 
 // rows of the kept keys, bucket by bucket
 __global__ __launch_bounds__(256) void emit_bucket_rows_kernel(RecView keys, const uint32_t *kcnt, const uint64_t *pos, uint32_t stride,
-                                                               const uint32_t *n_kept, const uint64_t *row_of, const uint32_t *mins, RowOut o, uint64_t row_base) {
+                                                               const uint32_t *n_kept, const uint64_t *row_of, const uint32_t *mins, RowOut o, uint64_t row_base, uint32_t prio) {
     const uint64_t s0 = pos[(uint64_t)blockIdx.x * stride];
     const uint32_t n = n_kept[blockIdx.x];
     const uint64_t r0 = row_base + row_of[blockIdx.x];
+    raise_wave_priority(prio);                                 // (behind the three scalar loads: in front of them it cost six vector registers)
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
         const uint64_t row = r0 + i;
         o.lo[row] = keys.lo[s0 + i]; o.hi[row] = keys.hi[s0 + i]; o.ab[row] = kcnt[s0 + i];
@@ -508,7 +517,8 @@ __global__ __launch_bounds__(256) void emit_bucket_rows_kernel(RecView keys, con
 // One lane per read, its windows' bytes four at a time: the sixteen-lanes-a-read form of the one-table pass spent 270 M vector
 // instructions on cross-lane sums for 10 M reads (rocprofv3, round 4) -- instructions another batch's scan would have used.
 __global__ __launch_bounds__(256) void rescue_count_p_kernel(const uint64_t *off, uint32_t n_reads, uint32_t k, const uint8_t *cnt8,
-                                                             uint32_t m_star, uint32_t *resc_cnt) {
+                                                             uint32_t m_star, uint32_t *resc_cnt, uint32_t prio) {
+    raise_wave_priority(prio);
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
     const uint64_t f = off[r];
@@ -539,7 +549,8 @@ __global__ __launch_bounds__(256) void rescue_count_p_kernel(const uint64_t *off
 
 // rows of the rescued reads' count-1 instances, in read order then window order (abundance 1, :4630-4636)
 __global__ __launch_bounds__(256) void emit_rescued_p_kernel(const uint64_t *off, const uint32_t *mins, uint32_t n_reads, uint32_t k, const uint8_t *cnt8,
-                                                             const uint32_t *resc_cnt, const uint64_t *resc_pos, RowOut o, uint64_t row_base) {
+                                                             const uint32_t *resc_cnt, const uint64_t *resc_pos, RowOut o, uint64_t row_base, uint32_t prio) {
+    raise_wave_priority(prio);
     const unsigned sub = threadIdx.x & 15u, gshift = (threadIdx.x & 63u) & ~15u;
     const uint64_t group = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint64_t ngroups = ((uint64_t)gridDim.x * blockDim.x) >> 4;
@@ -755,7 +766,7 @@ static void launch_bucket_count(mdbg_ctx *ctx, uint64_t n_buckets, RecView in, c
                                 RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept, uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow,
                                 uint32_t *fell_back) {
     hipLaunchKernelGGL((bucket_count_kernel<C, LIST>), dim3((unsigned)n_buckets), dim3(BC_NT), 0, ctx->stream, in, pos, stride, min_abundance, clip, keep_all, keys, kcnt,
-                       n_keys, n_kept, cnt8, cnt8_default, overflow, fell_back);
+                       n_keys, n_kept, cnt8, cnt8_default, overflow, fell_back, table_priority(ctx));
 }
 
 // the rows of one group of keys, kept aside while the next group reuses the record buffers (several groups only)
@@ -847,7 +858,7 @@ struct PartRun {
         {
             LaunchTimer timer(ctx, "kminmer_split");
             MDBG_HIP_CHECK(ctx, hipMemsetAsync(start_bits.p, 0, n_words * 4, ctx->stream));
-            hipLaunchKernelGGL(mark_starts_kernel, dim3(grid_for((uint64_t)n_reads + 1, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, start_bits.p);
+            hipLaunchKernelGGL(mark_starts_kernel, dim3(grid_for((uint64_t)n_reads + 1, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, start_bits.p, table_priority(ctx));
         }
         I_est = std::max<uint64_t>(M / 8 + 1, M > (uint64_t)(k - 1) * n_reads ? M - (uint64_t)(k - 1) * n_reads : 0);
         const uint64_t max_records = ctx->part_max_records ? ctx->part_max_records : std::max<uint64_t>(1ull << 24, (uint64_t)((double)ctx->hbm_bytes * 0.25 / 44.0));
@@ -878,6 +889,7 @@ struct PartRun {
         a.mins = reads->d_min.p; a.start_bits = start_bits.p; a.n_min = M; a.k = k;
         a.group_bits = group_bits; a.group = g;
         a.tile = tile;
+        a.prio = table_priority(ctx);
         // level 1: histogram, scan, the group's instance count, scatter
         uint64_t entries = 0;
         for (;;) {
@@ -896,7 +908,7 @@ struct PartRun {
             {
                 LaunchTimer timer(ctx, "kminmer_split");
                 launch_split_hist(ctx, true, form, lv[0].blocks_per_seg, a, hist.p);
-                if (a.hll) hipLaunchKernelGGL(hll_merge_kernel, dim3(HLL_M / 256, 64), dim3(256), 0, ctx->stream, hll_blocks.p, lv[0].blocks_per_seg, hll_merged.p);
+                if (a.hll) hipLaunchKernelGGL(hll_merge_kernel, dim3(HLL_M / 256, 64), dim3(256), 0, ctx->stream, hll_blocks.p, lv[0].blocks_per_seg, hll_merged.p, a.prio);
             }
             MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[0].p, entries));
             uint32_t regs[HLL_M];
@@ -931,7 +943,7 @@ struct PartRun {
             SplitArgs d{};
             d.in = buf[cur].view();
             d.seg_pos = place[l - 1].p; d.seg_stride = lv[l - 1].blocks_per_seg; d.blocks_per_seg = lv[l].blocks_per_seg;
-            d.shift = lv[l].shift; d.ways = lv[l].ways; d.n_min = 0; d.tile = tile;
+            d.shift = lv[l].shift; d.ways = lv[l].ways; d.n_min = 0; d.tile = tile; d.prio = a.prio;
             entries = n_seg * lv[l].ways * lv[l].blocks_per_seg;
             MDBG_TRY(hist.alloc(ctx, entries));
             MDBG_TRY(place[l].alloc(ctx, entries + 1));
@@ -1050,7 +1062,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             RowOut ro{gr.lo.p, gr.hi.p, gr.ab.p, gr.vec.p, k};
             LaunchTimer timer(ctx, "kminmer_emit");
             hipLaunchKernelGGL(emit_bucket_rows_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.pos, run.stride, run.n_kept.p,
-                               run.row_of.p, reads->d_min.p, ro, (uint64_t)0);
+                               run.row_of.p, reads->d_min.p, ro, (uint64_t)0, table_priority(ctx));
         }
 
         // rescue decision per read, row positions
@@ -1061,7 +1073,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             MDBG_TRY(resc_pos.alloc(ctx, (size_t)n_reads + 1));
             {
                 LaunchTimer timer(ctx, "kminmer_rescue");
-                hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p);
+                hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p, table_priority(ctx));
             }
             MDBG_TRY(exclusive_scan_u32(ctx, resc_cnt.p, resc_pos.p, n_reads));
             MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&n_resc, resc_pos.p + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1093,7 +1105,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             LaunchTimer timer(ctx, "kminmer_emit");
             if (n_groups == 1) {
                 hipLaunchKernelGGL(emit_bucket_rows_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.pos, run.stride,
-                                   run.n_kept.p, run.row_of.p, reads->d_min.p, ro, (uint64_t)0);
+                                   run.n_kept.p, run.row_of.p, reads->d_min.p, ro, (uint64_t)0, table_priority(ctx));
             } else {
                 uint64_t at = 0;
                 for (GroupRows &gr : group_rows) {
@@ -1109,7 +1121,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             if (n_resc) {
                 const unsigned blocks = grid_for((uint64_t)n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
                 hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, n_reads, k, cnt8.p, resc_cnt.p,
-                                   resc_pos.p, ro, total_solid);
+                                   resc_pos.p, ro, total_solid, table_priority(ctx));
             }
         }
         hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -1214,7 +1226,7 @@ int part_local_finish(mdbg_ctx *ctx, PartLocal *pl, const uint32_t *gcount, cons
         MDBG_TRY(resc_pos.alloc(ctx, (size_t)n_reads + 1));
         {
             LaunchTimer timer(ctx, "kminmer_rescue");
-            hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p);
+            hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p, table_priority(ctx));
         }
         MDBG_TRY(exclusive_scan_u32(ctx, resc_cnt.p, resc_pos.p, n_reads));
         MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&n_resc, resc_pos.p + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1232,7 +1244,7 @@ int part_local_finish(mdbg_ctx *ctx, PartLocal *pl, const uint32_t *gcount, cons
                                   reads->d_min.p, ro);
         if (n_resc) {
             const unsigned blocks = grid_for((uint64_t)n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
-            hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, n_reads, k, cnt8.p, resc_cnt.p, resc_pos.p, ro, n_solid);
+            hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, n_reads, k, cnt8.p, resc_cnt.p, resc_pos.p, ro, n_solid, table_priority(ctx));
         }
     }
     hipError_t e = hipStreamSynchronize(ctx->stream);

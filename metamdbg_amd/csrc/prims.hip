@@ -48,7 +48,8 @@ __device__ __forceinline__ void load_vec(const Tin *in, uint64_t idx, uint64_t n
 }
 
 template <typename Tin>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const Tin *in, uint64_t n, uint64_t *block_sums) {
+__global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const Tin *in, uint64_t n, uint64_t *block_sums, uint32_t prio) {
+    raise_wave_priority(prio);
     __shared__ uint64_t lds[4];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
     uint64_t s = 0;
@@ -64,7 +65,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const Tin *in
 }
 
 // single block: exclusive scan of m <= arbitrary values, sequential over tiles
-__global__ __launch_bounds__(SCAN_THREADS) void scan_small_kernel(uint64_t *vals, uint64_t m) {
+__global__ __launch_bounds__(SCAN_THREADS) void scan_small_kernel(uint64_t *vals, uint64_t m, uint32_t prio) {
+    raise_wave_priority(prio);
     __shared__ uint64_t lds[4];
     uint64_t carry = 0;
     for (uint64_t base = 0; base < m; base += SCAN_THREADS) {
@@ -80,7 +82,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_small_kernel(uint64_t *vals
 
 template <typename Tin>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(const Tin *in, uint64_t n, const uint64_t *block_offsets,
-                                                                  uint64_t *out) {
+                                                                  uint64_t *out, uint32_t prio) {
+    raise_wave_priority(prio);
     __shared__ uint64_t lds[4];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
     uint64_t carry = block_offsets[blockIdx.x];
@@ -119,9 +122,10 @@ static int exclusive_scan_impl(mdbg_ctx *ctx, const Tin *d_in, uint64_t *d_out, 
     DevBuf<uint64_t> sums;
     MDBG_TRY(sums.alloc(ctx, nblocks + 1));
     LaunchTimer timer(ctx, "prefix_scan");
-    hipLaunchKernelGGL(scan_reduce_kernel<Tin>, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n, sums.p);
+    const uint32_t prio = table_priority(ctx);
+    hipLaunchKernelGGL(scan_reduce_kernel<Tin>, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n, sums.p, prio);
     if (nblocks <= 64 * 1024) {
-        hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, sums.p, nblocks);
+        hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, sums.p, nblocks, prio);
     } else {
         // two-level: scan the block sums recursively (u64 input)
         DevBuf<uint64_t> tmp;
@@ -130,7 +134,7 @@ static int exclusive_scan_impl(mdbg_ctx *ctx, const Tin *d_in, uint64_t *d_out, 
         MDBG_HIP_CHECK(ctx, hipMemcpyAsync(sums.p, tmp.p, (nblocks + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
         MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    hipLaunchKernelGGL(scan_apply_kernel<Tin>, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n, sums.p, d_out);
+    hipLaunchKernelGGL(scan_apply_kernel<Tin>, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n, sums.p, d_out, prio);
     MDBG_HIP_CHECK(ctx, hipGetLastError());
     // no synchronisation: `sums` returns to the context's pool, whose blocks are only ever handed to later work on
     // the same stream, i.e. after the kernels above
