@@ -116,6 +116,9 @@ int  mdbg_device_clock_khz(mdbg_ctx *ctx, int *clock_khz);   /* peak engine cloc
  *                           MDBG_SCAN_GRAB_READS sets the default of new contexts
  *   "scan_persistent_blocks"  tests only: at most this many workgroups in a persistent launch (0 = no cap), so that the waves of a small
  *                           batch draw many runs.  Results never depend on it
+ *   "prefix_small_limit"    tests only: the block sums (one per 4096 items) up to which one workgroup scans the middle level of a prefix scan; more are
+ *                           scanned recursively (1 .. 65536, larger values are 65536; 0 or a negative value restores the default, 65536: above
+ *                           2^28 items).  Results never depend on it
  *   "scan_segments"         long reads, contigs and unitigs cut into segments that the block-structured scan takes one wave each: a plain read
  *                           (no N, no case flip) of more than one segment is scanned as several views -- each owns the windows that start
  *                           in its segment and reads one 2048-base tile on behind it -- and the views' rows are joined in read order.
@@ -725,6 +728,13 @@ void mdbg_gzip_stream_free(mdbg_gzip_stream *s);
 int  mdbg_bytes_inflate_gzip(mdbg_ctx *ctx, mdbg_gzip_stream *s, const mdbg_bytes *comp, const mdbg_gzip_chunk *chunks, uint64_t n_chunks,
                              mdbg_bytes *text, uint64_t text_at, uint64_t *n_text, uint64_t info[4]);
 int  mdbg_bytes_copy(mdbg_ctx *ctx, mdbg_bytes *dst, uint64_t dst_at, const mdbg_bytes *src, uint64_t src_at, uint64_t n);
+/* Exclusive prefix sums of n unsigned values of `width` bytes (4 or 8) that start at byte in_at of `in`:
+   n + 1 uint64 values (the last one the total) written from byte out_at of `out`.  The library's own device-wide scan (every CSR offset
+   array, every flags -> rows compaction) on caller-chosen values, sizes and alignments; queued on the context's stream behind the uploads of
+   both objects, not waited for.  n == 0 writes the single total 0.  MDBG_EINVAL: a null argument, a width other than 4 or 8, in_at not a
+   multiple of width, out_at not a multiple of 8, a range that leaves its object, `in` and `out` one object with overlapping ranges. */
+int  mdbg_bytes_prefix_sum(mdbg_ctx *ctx, const mdbg_bytes *in, uint64_t in_at, int width, uint64_t n,
+                           mdbg_bytes *out, uint64_t out_at);
 
 /* Page-locked host memory for read batches handed to mdbg_reads_from_ascii / _from_packed: uploads from it
  * run at PCIe rate instead of through the driver's staging copies.  Release with mdbg_host_free. */

@@ -159,6 +159,7 @@ SIGNATURES = {
     "mdbg_bytes_inflate_gzip": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _u64p, _u64p]),
     "mdbg_bytes_copy": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64]),
     "mdbg_fastx_whole_records": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _u64p, C.POINTER(C.c_int)]),
+    "mdbg_bytes_prefix_sum": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64]),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
@@ -586,6 +587,11 @@ class Context:
     def bytes_copy(self, dst: "DeviceBytes", dst_at: int, src: "DeviceBytes", src_at: int, n: int) -> None:
         """src[src_at, +n) to dst[dst_at, +n) on the device, in stream order (mdbg_bytes_copy)."""
         self.check(lib().mdbg_bytes_copy(self.h, dst.h, dst_at, src.h, src_at, n))
+
+    def bytes_prefix_sum(self, src: "DeviceBytes", src_at: int, width: int, n: int, dst: "DeviceBytes", dst_at: int) -> None:
+        """Exclusive prefix sums of the n values of ``width`` bytes at src[src_at ...): n + 1 uint64 at dst[dst_at ...), the last one the
+        total; queued in stream order, not waited for (mdbg_bytes_prefix_sum)."""
+        self.check(lib().mdbg_bytes_prefix_sum(self.h, src.h if src is not None else None, src_at, width, n, dst.h if dst is not None else None, dst_at))
 
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""

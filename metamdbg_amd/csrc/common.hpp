@@ -177,6 +177,7 @@ struct mdbg_ctx {
     uint32_t scan_persistent = 1;           // "scan_persistent": 1 = taken unless "scan_reads_per_wave" names the chunked form (default), 0 = the chunked form (mdbg_set_option, MDBG_SCAN_PERSISTENT)
     uint32_t scan_grab_reads = 0;           // "scan_grab_reads": consecutive items a wave draws at a time; 0 = the default (PERSISTENT_GRAB_READS)
     uint32_t scan_persistent_blocks = 0;    // tests: caps the persistent grid, so that the waves of a small batch draw many runs
+    uint32_t prefix_small_limit = 65536;    // "prefix_small_limit": block sums up to which one block scans the middle level of a prefix scan (prims.hip); tests lower it
     static constexpr uint32_t SCAN_COUNTER_SLOTS = 16;
     unsigned long long *scan_counters = nullptr;    // device: SCAN_COUNTER_SLOTS counters, one per pre-filtered launch of a call (the batch's, its views'), taken
     uint32_t scan_counter_next = 0;         // in turn; each is zeroed on its launch's stream in front of the launch

@@ -199,6 +199,7 @@ extern "C" int mdbg_set_option(mdbg_ctx *ctx, const char *name, int64_t value) {
     if (n == "scan_persistent") { ctx->scan_persistent = value != 0; return MDBG_OK; }
     if (n == "scan_grab_reads") { ctx->scan_grab_reads = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 16, value)); return MDBG_OK; }
     if (n == "scan_persistent_blocks") { ctx->scan_persistent_blocks = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(1 << 20, value)); return MDBG_OK; }
+    if (n == "prefix_small_limit") { ctx->prefix_small_limit = value > 0 ? (uint32_t)std::min<int64_t>(value, 65536) : 65536u; return MDBG_OK; }
     if (n == "scan_confirm_table_log2_buckets") {
         if (value != 0 && (value < 10 || value > 16)) return set_error(ctx, MDBG_EINVAL, "scan_confirm_table_log2_buckets: 0 (the kernel's own) or 10 .. 16");
         ctx->scan_confirm_table_log2_buckets = (uint32_t)value; return MDBG_OK;

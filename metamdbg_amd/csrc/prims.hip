@@ -1,6 +1,7 @@
 // prims.hip -- small device-wide primitives: exclusive scan (reduce / scan / apply).
 // Used for CSR offsets (minimizers per read, instances per read, flags -> output rows).
 #include "common.hpp"
+#include "objects.hpp"
 
 namespace mdbg {
 
@@ -124,7 +125,7 @@ static int exclusive_scan_impl(mdbg_ctx *ctx, const Tin *d_in, uint64_t *d_out, 
     LaunchTimer timer(ctx, "prefix_scan");
     const uint32_t prio = table_priority(ctx);
     hipLaunchKernelGGL(scan_reduce_kernel<Tin>, dim3((unsigned)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, d_in, n, sums.p, prio);
-    if (nblocks <= 64 * 1024) {
+    if (nblocks <= ctx->prefix_small_limit) {                // 65536 unless a test lowered it ("prefix_small_limit")
         hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, sums.p, nblocks, prio);
     } else {
         // two-level: scan the block sums recursively (u64 input)
@@ -159,4 +160,31 @@ const StepKernel *prims_step_kernels(uint32_t *n) {
     return k;
 }
 
+int bytes_ready_on(mdbg_ctx *ctx, const mdbg_bytes *b);      // minimizers.hip
+
 }  // namespace mdbg
+
+using namespace mdbg;
+
+extern "C" int mdbg_bytes_prefix_sum(mdbg_ctx *ctx, const mdbg_bytes *in, uint64_t in_at, int width, uint64_t n, mdbg_bytes *out, uint64_t out_at) try {
+    if (!ctx || !in || !out) return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: null argument");
+    if (width != 4 && width != 8) return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: width %d is neither 4 nor 8", width);
+    const uint64_t w = (uint64_t)width;
+    if (in_at % w) return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: in_at %llu is no multiple of the width %d", (unsigned long long)in_at, width);
+    if (out_at % 8) return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: out_at %llu is no multiple of 8", (unsigned long long)out_at);
+    if (in_at > in->n || n > (in->n - in_at) / w)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: %llu values of %d bytes from %llu lie outside the %llu bytes of the input", (unsigned long long)n, width,
+                         (unsigned long long)in_at, (unsigned long long)in->n);
+    if (out_at > out->n || (out->n - out_at) / 8 < 1 || n > (out->n - out_at) / 8 - 1)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: %llu + 1 sums from %llu lie outside the %llu bytes of the output", (unsigned long long)n,
+                         (unsigned long long)out_at, (unsigned long long)out->n);
+    if (in == out && n && in_at < out_at + 8 * (n + 1) && out_at < in_at + w * n)
+        return set_error(ctx, MDBG_EINVAL, "mdbg_bytes_prefix_sum: the values at [%llu, +%llu) and the sums at [%llu, +%llu) of one buffer overlap", (unsigned long long)in_at,
+                         (unsigned long long)(w * n), (unsigned long long)out_at, (unsigned long long)(8 * (n + 1)));
+    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    MDBG_TRY(bytes_ready_on(ctx, in));                        // uploads still in flight: the kernels run behind them
+    MDBG_TRY(bytes_ready_on(ctx, out));
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(out->d.p + out_at);
+    if (width == 4) return exclusive_scan_u32(ctx, reinterpret_cast<const uint32_t *>(in->d.p + in_at), d_out, n);
+    return exclusive_scan_u64(ctx, reinterpret_cast<const uint64_t *>(in->d.p + in_at), d_out, n);
+} MDBG_API_CATCH(ctx)
