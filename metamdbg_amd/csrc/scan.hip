@@ -825,13 +825,14 @@ constexpr int HIST_TILES = 8;
 // read can produce and which of them are selected is fixed by (l, threshold): the walks probe a bitmap of the selected keys in LDS
 // (prefilter.hpp) instead of hashing -- one multiply, one shift, one ds_read_u8 and two field extracts a position where the candidate
 // hash takes 28 instructions -- and the positions that pass (8.65 % false positives + the selected ones, about 190 of a block's
-// 2048) are listed, hashed in full 64 at a time and only the survivors go on (confirm): behind it emit sees exact verdicts.
+// 2048) are listed and hashed in full 64 at a time; the lane that confirms one holds its position, both orientations and the verdict,
+// and writes the finished row to the stage from there (confirm): the variant has no emit, no materialise and defers no block.
 // The bitmap exists once per CU: ONE workgroup of PFW = 16 (or 8) waves per CU copies its 64 KB at set-up.  What a wave owns shrinks
-// to make room beside it: a ring of 8192 bases (one block deferred instead of three), a stage of PF_STAGE_CAP rows, a list of
-// PF_LIST_CAP candidate positions and 64 words the confirmed verdicts come back through.  The waves of a workgroup take reads from a
+// to make room beside it: a ring of 8192 bases (released after every block), a stage of PF_STAGE_CAP rows and a list of
+// PF_LIST_CAP candidate positions.  The waves of a workgroup take reads from a
 // counter in LDS over the workgroup's chunk of reads, so that a CU is not left to the slowest of 16 fixed shares.
-constexpr unsigned PF_RING_BASES = 8192;              // per wave: 1 deferred block + 2 * 2048 + 16 + 1 live bases = 6161
-constexpr unsigned PF_DEFER_BLOCKS = 1;
+constexpr unsigned PF_RING_BASES = 8192;              // per wave: 2 * 2048 + 16 + 1 live bases = 4113 (a power of two)
+constexpr unsigned PF_DEFER_BLOCKS = 0;               // a block's rows are finished when its confirmation is: the ring keeps none
 constexpr int PF_STAGE_CAP = 176;
 constexpr unsigned PF_LIST_CAP = 224;                 // candidate positions confirmed per pass (a block has 187 +- 13; more take further passes)
 template <int PFW> struct FastGeometry {
@@ -839,9 +840,9 @@ template <int PFW> struct FastGeometry {
     static constexpr int WAVES = PF ? PFW : FAST_WAVES, BLOCK = 64 * WAVES, STAGE = PF ? PF_STAGE_CAP : STAGE_CAP;
     static constexpr unsigned RING = PF ? PF_RING_BASES : RING_BASES, DEFER = PF ? PF_DEFER_BLOCKS : DEFER_BLOCKS;
     static constexpr unsigned RING_WORDS = RING / 16, RING_WMASK = RING_WORDS - 1;      // u32 words of the ring
-    // LDS of a workgroup of the pre-filtered variant: bitmap, tables, per wave ring + stage + list + verdict words, the read counter
+    // LDS of a workgroup of the pre-filtered variant: bitmap, tables, per wave ring + stage + list, the read counter
     static constexpr size_t PF_LDS = PREFILTER_BYTES + 2 * HPC_LUT_SIZE + REP_FILTER_BITS / 8 + 16 +
-                                     (size_t)WAVES * (RING / 4 + STAGE * 8 + PF_LIST_CAP * 2 + 64 * 4);
+                                     (size_t)WAVES * (RING / 4 + STAGE * 8 + PF_LIST_CAP * 2);
 };
 static_assert(FastGeometry<16>::PF_LDS + 28672 <= 163840, "16 waves fit beside the 28 KB the benchmark's other batch asks for");
 
@@ -856,6 +857,10 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
     constexpr bool PF = Geo::PF;
     static_assert(!PF || (HPC && !QUAL && APPROX), "the bitmap holds the keys of compressed reads; its candidates are confirmed like APPROX ones");
     static_assert(Geo::DEFER * BLOCK_POS + 2 * BLOCK_POS + 17 <= Geo::RING, "deferred blocks + live bases fit the ring");
+    // PF: the variant needs 92 - 93 vector registers, one granule of eight less than the 104 it is allotted beside the first pass's
+    // kernels (tests/test_gpu_step_residency.py pins which of them fit beside it).  Which kernels share a CU with the scan
+    // is a decision of its own, with a measurement of its own: the allotment stays 104 -- v103 is named here, where nothing is live
+    if constexpr (PF) asm volatile("" ::: "v103");
     __shared__ uint8_t lds_stage_q[QUAL ? Geo::WAVES : 1][QUAL ? Geo::STAGE : 1];
     __shared__ uint16_t lds_hist_o[(QUAL && HPC) ? Geo::WAVES * HIST_TILES * 64 : 1];
     __shared__ uint32_t lds_hist_c[(QUAL && HPC) ? Geo::WAVES : 1][(QUAL && HPC) ? HIST_TILES : 1];
@@ -876,17 +881,16 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
     // PF: the bitmap from global memory (it stays in L2 between workgroups), the workgroup's read counter, the waves' lists
     const uint8_t *pf_map = nullptr;
     uint16_t *pf_list_all = nullptr;
-    uint32_t *pf_surv_all = nullptr, *pf_next = nullptr;
+    uint32_t *pf_next = nullptr;
     if constexpr (PF) {
         __shared__ alignas(16) uint32_t lds_pf_map[PREFILTER_BYTES / 4];
         __shared__ uint16_t lds_pf_list[Geo::WAVES][PF_LIST_CAP];
-        __shared__ uint32_t lds_pf_surv[Geo::WAVES][64];
         __shared__ uint32_t lds_pf_next;
         for (unsigned i = threadIdx.x; i < PREFILTER_BYTES / 16u; i += Geo::BLOCK)
             reinterpret_cast<uint4 *>(lds_pf_map)[i] = reinterpret_cast<const uint4 *>(a.pf_bits)[i];
         if (threadIdx.x == 0) lds_pf_next = 0u;
         pf_map = reinterpret_cast<const uint8_t *>(lds_pf_map);
-        pf_list_all = &lds_pf_list[0][0]; pf_surv_all = &lds_pf_surv[0][0]; pf_next = &lds_pf_next;
+        pf_list_all = &lds_pf_list[0][0]; pf_next = &lds_pf_next;
     }
     __syncthreads();
     for (unsigned i = threadIdx.x; i < a.n_rep; i += Geo::BLOCK) {
@@ -932,9 +936,8 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
 
     const uint32_t wave_global = blockIdx.x * Geo::WAVES + wv;
     const uint32_t n_waves = gridDim.x * Geo::WAVES;
-    // PF: this wave's list of candidate positions, the words their verdicts come back through, the bitmap's shift
+    // PF: this wave's list of candidate positions, the bitmap's shift
     uint16_t *pf_list = PF ? pf_list_all + wv * PF_LIST_CAP : nullptr;
-    uint32_t *pf_surv = PF ? pf_surv_all + wv * 64u : nullptr;
     const uint32_t pf_shift = a.pf_shift;
     const uint4 *const pf_table = PF ? a.pf_table : nullptr;      // wave-uniform; null: confirm hashes its candidates
     const uint32_t pf_table_shift = a.pf_table_shift;
@@ -990,7 +993,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         const uint32_t trim_first = seg_inner ? 0u : a.trim;
         const uint32_t nwords = (L + 31u) / 32u;
         const uint32_t ntiles = (nwords + TILE_WORDS - 1) / TILE_WORDS;
-        const bool bump = a.cursor != nullptr;
+        const bool bump = PF || a.cursor != nullptr;      // (every launch of the variant has a cursor: launch_scan, choose_prefilter)
         const uint64_t cap0 = bump ? 0ull : a.cap_off[r];
         const uint32_t cap = bump ? 0u : (uint32_t)(a.cap_off[r + 1] - cap0);
         uint32_t t_done = 0;       // raw tiles appended to the ring so far (HPC && QUAL: their offsets are in hist_*)
@@ -1110,10 +1113,10 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
         };
 
         // ---- emission: list the positions recorded in `bits` (span length P per lane, oldest position in bit P-1) ----
+        // (the four-wave kernels'; the variant's rows are staged by confirm, below)
         auto emit = [&](uint32_t bits, unsigned P, uint32_t npos_limit) {
             // positions at or beyond npos_limit (tail lanes past the end) and the trimmed first position of the read
-            // (PF: confirm has masked them already and hands back a subset of what it kept)
-            if constexpr (!PF) {
+            {
                 if (P < 32u) bits &= (1u << P) - 1u;
                 const uint32_t first_j = lane * P;                 // span-relative index of this lane's first position
                 if (first_j >= npos_limit) bits = 0;
@@ -1140,8 +1143,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             if (bump) {
                 if (outgrown || nout + total > (unsigned)Geo::STAGE) {
                     if (!outgrown) { materialise(); n_staged_at_outgrowth = nout; }
-                    if (APPROX && !PF) {   // the count the host places the read by must be exact: hash the candidates in full (PF: confirm's
-                                           // verdicts are exact already)
+                    if (APPROX) {          // the count the host places the read by must be exact: hash the candidates in full
                         uint32_t bad = 0;
                         while (bits) {
                             const unsigned bit = 31u - (unsigned)__clz((int)bits);
@@ -1206,26 +1208,51 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
             const uint32_t byte = pf_map[h >> (pf_shift + 3u)];
             b = (b << 1) | ((byte >> ((h >> pf_shift) & 7u)) & 1u);
         };
-        // ---- PF: confirmation, between a walk and emit.  `bits` (span length P per lane, oldest position in bit P - 1) holds the
-        // positions whose probe passed; what comes back holds those whose full hash is below the threshold.  The set positions are
-        // listed in LDS in lane order (6 bits of lane, 5 of bit), the lanes take listed positions 64 at a time, rebuild the key from
-        // the ring and hash it, and a survivor is ORed into its owner's word.  The list holds PF_LIST_CAP positions: what a pass
-        // cannot list stays in `bits` for the next pass, so a block with any number of candidates is confirmed exactly ----
-        auto confirm = [&](uint32_t bits, unsigned P, uint32_t npos_limit) -> uint32_t {
-            // positions at or beyond npos_limit and the trimmed first position of the read are nobody's (emit masks them again)
+        // ---- PF: confirmation, behind a walk: what the four-wave kernels' emit and materialise do, for the variant.  `bits` (span length
+        // P per lane, oldest position in bit P - 1) holds the positions whose probe passed.  The set positions are listed in LDS in lane
+        // order (6 bits of lane, 5 of bit), i.e. in position order; the lanes take listed positions 64 at a time (a ROUND), rebuild the
+        // window from the ring and take its exact verdict; the lane of a selected one holds position, both orientations and verdict, and
+        // writes the finished row to the stage at its rank in the round's ballot.  Rounds and passes go up through the positions, so the
+        // rows stay in position order.  The list holds PF_LIST_CAP positions: what a pass cannot list stays in `bits` for the next
+        // pass, so a block with any number of candidates is confirmed exactly.  A round that would pass the stage's end makes the
+        // read `outgrown`; from there on the rounds count only (the host places and re-runs the read by that count) ----
+        auto confirm = [&](uint32_t bits, unsigned P, uint32_t npos_limit) {
+            // positions at or beyond npos_limit (tail lanes past the end) and the trimmed first position of the read are nobody's
             if (P < 32u) bits &= (1u << P) - 1u;
             {
                 const uint32_t first_j = lane * P;
                 if (first_j >= npos_limit) bits = 0;
                 else if (first_j + P > npos_limit) bits &= ~((1u << (first_j + P - npos_limit)) - 1u);
-                if (done == 0u && lane == 0u && trim_first) bits &= ~(1u << (P - 1u));
+                if (done == 0u && lane == 0u && trim_first) bits &= ~(1u << (P - 1u));      // Kmer.hpp:1395
             }
-            uint32_t kept = 0u;
+            // the row of listed position q (6 bits of owner lane, 5 of bit): v the canonical form, y = (position << 1) | direction,
+            // direction 1 iff the reverse complement is the canonical form, ties included (Kmer.hpp:427)
+            auto listed_row = [&](uint32_t q, uint32_t &v, uint32_t &y) {
+                const uint32_t j = done + (q >> 5) * P + (P - 1u - (q & 31u));
+                const uint32_t e = ring_window(S, j, Geo::RING_WMASK) & kmask;
+                const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
+                const uint32_t d = fw < rev ? 0u : 1u;
+                v = d ? rev : fw; y = (j << 1) | d;
+            };
+            // Kmer.hpp:1437: a repetitive minimizer is not selected
+            auto repetitive = [&](uint32_t v) -> bool {
+                const uint32_t fb = rep_filter_bit(v);
+                return ((lds_rep_filter[fb >> 5] >> (fb & 31u)) & 1u) && rep_contains(a.rep, a.n_rep, v);
+            };
+            // one round's rows leave for the stage: rank = the selected lanes below this one
+            auto stage_round = [&](bool sel, uint32_t v, uint32_t y) {
+                if (a.n_rep) { if (sel && repetitive(v)) sel = false; }
+                const uint64_t m = __ballot(sel);
+                if (m == 0ull) return;
+                const unsigned c = (unsigned)__popcll(m);
+                if (outgrown || nout + c > (unsigned)Geo::STAGE) outgrown = true;       // counted only: the read is re-run by the general kernel
+                else if (sel) stage[nout - flushed + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = make_uint2(v, y);
+                nout += c;
+            };
             unsigned cnt = (unsigned)__popc(bits);
             unsigned incl = wave_inclusive_sum_dpp(cnt);
             unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
             while (total != 0u) {
-                pf_surv[lane] = 0u;
                 unsigned at = incl - cnt;
                 while (bits && at < PF_LIST_CAP) {
                     const unsigned bit = 31u - (unsigned)__clz((int)bits);
@@ -1234,63 +1261,53 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 }
                 const unsigned n = total < PF_LIST_CAP ? total : PF_LIST_CAP;
                 wave_lds_sync();
-                // the key of listed position q (6 bits of owner lane, 5 of bit)
-                auto listed_key = [&](uint32_t q) -> uint32_t {
-                    const uint32_t e = ring_window(S, done + (q >> 5) * P + (P - 1u - (q & 31u)), Geo::RING_WMASK) & kmask;
-                    const uint32_t rev = e ^ comp_mask, fw = digit_reverse(e, K);
-                    return fw < rev ? fw : rev;
-                };
                 if (pf_table != nullptr) {
                     // the verdicts from the selected-key table (prefilter.hpp): the loads of every round of the pass are issued before
                     // the first is waited for; a lane without a listed position keeps a bucket of zeros, which selects nothing
                     constexpr unsigned ROUNDS = (PF_LIST_CAP + 63u) / 64u;
-                    uint32_t lh[ROUNDS];
+                    uint32_t lv[ROUNDS], ly[ROUNDS];
                     uint4 lw[ROUNDS];
 #pragma unroll
                     for (unsigned k = 0; k < ROUNDS; k++) {
-                        lh[k] = 0u; lw[k] = make_uint4(0u, 0u, 0u, 0u);
+                        lv[k] = 0u; ly[k] = 0u; lw[k] = make_uint4(0u, 0u, 0u, 0u);
                         if (64u * k < n) {
                             const unsigned i = lane + 64u * k;
                             if (i < n) {
-                                lh[k] = confirm_hash(listed_key(pf_list[i]));
-                                lw[k] = pf_table[lh[k] >> pf_table_shift];
+                                listed_row(pf_list[i], lv[k], ly[k]);
+                                lw[k] = pf_table[confirm_hash(lv[k]) >> pf_table_shift];
                             }
                         }
                     }
-                    uint32_t ask = 0u;
 #pragma unroll
                     for (unsigned k = 0; k < ROUNDS; k++) {
                         if (64u * k < n) {
-                            const uint32_t verdict = confirm_verdict(lw[k].x, lw[k].y, lw[k].z, lw[k].w, lh[k]);
-                            if (verdict == CONFIRM_YES) { const uint32_t q = pf_list[lane + 64u * k]; atomicOr(&pf_surv[q >> 5], 1u << (q & 31u)); }
-                            if (verdict == CONFIRM_ASK) ask |= 1u << k;
-                        }
-                    }
-                    // keys of buckets the builder marked ask the hash (no bucket is marked at density 0.005f): one loop for all rounds
-                    if (__ballot(ask != 0u) != 0ull) {
-#pragma nounroll
-                        for (unsigned k = 0; k < ROUNDS; k++) {
-                            if ((ask >> k) & 1u) {
-                                const uint32_t q = pf_list[lane + 64u * k];
-                                if (kmer_hash32(listed_key(q)) < threshold) atomicOr(&pf_surv[q >> 5], 1u << (q & 31u));
+                            const uint32_t verdict = confirm_verdict(lw[k].x, lw[k].y, lw[k].z, lw[k].w, confirm_hash(lv[k]));
+                            bool sel = verdict == CONFIRM_YES;
+                            // keys of buckets the builder marked ask the hash (no bucket is marked at density 0.005f), within their round:
+                            // the rows stay in order
+                            if (__ballot(verdict == CONFIRM_ASK) != 0ull) {
+                                if (verdict == CONFIRM_ASK) sel = kmer_hash32(lv[k]) < threshold;
                             }
+                            stage_round(sel, lv[k], ly[k]);
                         }
                     }
                 } else {
-                    for (unsigned i = lane; i < n; i += 64u) {
-                        const uint32_t q = pf_list[i];
-                        if (kmer_hash32(listed_key(q)) < threshold) atomicOr(&pf_surv[q >> 5], 1u << (q & 31u));
+                    for (unsigned i0 = 0u; i0 < n; i0 += 64u) {
+                        uint32_t v = 0u, y = 0u;
+                        bool sel = false;
+                        if (i0 + lane < n) {
+                            listed_row(pf_list[i0 + lane], v, y);
+                            sel = kmer_hash32(v) < threshold;
+                        }
+                        stage_round(sel, v, y);
                     }
                 }
-                wave_lds_sync();
-                kept |= pf_surv[lane];
                 if (total <= PF_LIST_CAP) break;      // everything was listed: nothing is left in `bits`
-                wave_lds_sync();          // read before the next pass clears the words
+                wave_lds_sync();          // the list is read before the next pass rewrites it
                 cnt = (unsigned)__popc(bits);
                 incl = wave_inclusive_sum_dpp(cnt);
                 total -= PF_LIST_CAP;
             }
-            return kept;
         };
 
         // ---- the slow path of the shared hash (APPROX, guarded walks): this lane's span of P positions once more, position by
@@ -1359,22 +1376,28 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                     Tprev = T;
                 }
             };
-            if constexpr (PF) {          // l = 15, compressed, no slack (launch_scan): the one walk, then the exact verdicts
+            if constexpr (PF) {          // l = 15, compressed, no slack (launch_scan): the one walk, then the exact verdicts as staged rows
                 walk(std::true_type(), std::false_type());
-                st.bits = confirm(st.bits, (unsigned)SP, 64u * (unsigned)SP);
-            } else if (K == 15u) { if (APPROX && !unguarded) walk(std::true_type(), std::true_type()); else walk(std::true_type(), std::false_type()); }
-            else walk(std::false_type(), std::integral_constant<bool, APPROX>());
-            emit(st.bits, (unsigned)SP, 64u * (unsigned)SP);
-            wave_lds_sync();
-            done += 64u * (unsigned)SP;
-            // materialise when most of a wave's lanes have a position to take, or when the ring cannot keep the blocks any longer
-            // (with qualities under HPC the run starts of a listed position must still be in the tile history: one block less)
-            constexpr unsigned defer = (QUAL && HPC) ? Geo::DEFER - 1u : Geo::DEFER;
-            if (nout - n_mat >= 48u || nout == n_mat || done - zero_from > defer * BLOCK_POS) {
-                materialise();
-                release_ring(done);
+                confirm(st.bits, (unsigned)SP, 64u * (unsigned)SP);
+                wave_lds_sync();
+                done += 64u * (unsigned)SP;
+                release_ring(done);      // its rows are finished: nothing of the block is read again
+                wave_lds_sync();
+            } else {
+                if (K == 15u) { if (APPROX && !unguarded) walk(std::true_type(), std::true_type()); else walk(std::true_type(), std::false_type()); }
+                else walk(std::false_type(), std::integral_constant<bool, APPROX>());
+                emit(st.bits, (unsigned)SP, 64u * (unsigned)SP);
+                wave_lds_sync();
+                done += 64u * (unsigned)SP;
+                // materialise when most of a wave's lanes have a position to take, or when the ring cannot keep the blocks any longer
+                // (with qualities under HPC the run starts of a listed position must still be in the tile history: one block less)
+                constexpr unsigned defer = (QUAL && HPC) ? Geo::DEFER - 1u : Geo::DEFER;
+                if (nout - n_mat >= 48u || nout == n_mat || done - zero_from > defer * BLOCK_POS) {
+                    materialise();
+                    release_ring(done);
+                }
+                wave_lds_sync();
             }
-            wave_lds_sync();
         };
 
         uint64_t x_next = (lane < nwords) ? rw[lane] : 0;
@@ -1485,7 +1508,7 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 // A chain needs 32 + 2 (Ph - 1) <= 62 stream bits from its first position on: three ring words, read once and aligned
                 // to the position (a per-lane shift); the walk then takes its window with the uniform shift 2 u and reads no LDS.
                 // The words may lie up to 48 bases past a chain's first position, i.e. below done + 63 P + Ph + 48 <= done + 2080:
-                // with the Geo::DEFER blocks kept behind `done` that is 8224 of the four-wave ring's 16384 bases (4128 of the variant's 8192), so they never lap into kept
+                // with the Geo::DEFER blocks kept behind `done` that is 8224 of the four-wave ring's 16384 bases (the variant keeps none: 2080 of its 8192), so they never lap into kept
                 // bases; what they hold beyond `fill` is zero, and positions at or beyond npos are masked in emit whatever they hash to.
                 auto chain_words = [&](unsigned p, uint32_t &lo, uint32_t &hi) {
                     const unsigned b = 2u * p, w = (b >> 5) & Geo::RING_WMASK, sh = b & 31u;
@@ -1538,13 +1561,13 @@ __global__ __launch_bounds__(FastGeometry<PFW>::BLOCK, PFW ? PFW / 4 : 5) void s
                 };
                 if constexpr (PF) {
                     tail_walk(std::true_type(), std::false_type());
-                    bits = confirm(bits, P, npos);
+                    confirm(bits, P, npos);
                 } else if (K == 15u) { if (APPROX && !unguarded) tail_walk(std::true_type(), std::true_type()); else tail_walk(std::true_type(), std::false_type()); }
                 else tail_walk(std::false_type(), std::integral_constant<bool, APPROX>());
-                emit(bits, P, npos);
+                if constexpr (!PF) emit(bits, P, npos);
             }
             wave_lds_sync();
-            materialise();
+            if constexpr (!PF) materialise();
             // leave the ring zero for the next read: everything from `zero_from` to `fill`
             release_ring(((fill + 15u) & ~15u) + 16u);
         }
