@@ -632,6 +632,93 @@ int  mdbg_reads_stitch_ranges(mdbg_ctx *ctx, const mdbg_reads *reads, const mdbg
 int  mdbg_sequences_to_fasta_bytes(mdbg_ctx *ctx, const mdbg_sequences *seqs, const uint32_t *names /* optional */,
                                    const uint8_t *circular /* optional */, mdbg_bytes **out, uint64_t *n_bytes /* optional */);
 
+/* ---- reads mapped against reads in minimizer space: index, anchors, chains --------------------------------------------------------------
+ * Replaces the data-parallel part of ReadMapper (readSelection/ReadMapper.hpp), which ReadCorrection runs over read_data_init.txt
+ * (ReadCorrection.hpp:2159), at k = 2 as ReadMapper::execute sets it (:172).  It reads minimizers and their positions only -- what a scan
+ * output already keeps on the device -- and no base.
+ *
+ * Window i of a read of n minimizers (n - 1 windows), a = m[i], b = m[i + 1]: reversed = (a >= b) (KmerVec::normalize, Commons.hpp:886-916),
+ * pair = (min(a, b) << 32) | max(a, b) (packPair, :937), position = (pos[i] + pos[i + 1]) / 2, index = i.  A read's global number is the
+ * call's first_read + its number in the set.
+ *
+ * mdbg_minimizers_attach_positions  gives a set made by mdbg_minimizers_from_host the position array a scan output has (host, one per
+ *       minimizer).  MDBG_EINVAL with the first offending read: a position that is not strictly above the one before it inside its read,
+ *       or one >= 2^31 (the reference takes position differences in int32_t, ReadMapper.hpp:1159-1166).  Sets that carry positions: a scan
+ *       output, a concat or apply_density_threshold of scan outputs, a set with attached positions; every other set is MDBG_EINVAL below.
+ *
+ * mdbg_map_index_build  replaces ReadFunctor (:465-505), Commons::sortParallel and createLookupTable (:550-627): every window of every read
+ *       of the chunk, reads below 10 minimizers included, grouped by pair; a pair's entries are in (read, index) order.  info: entries,
+ *       distinct pairs, the longest run of one pair, reads.  _to_host gives the entries in index order (any array may be NULL).
+ *       MDBG_ERANGE: 2^32 entries or more.  Timer names: "map_index", "radix_sort".
+ *
+ * mdbg_map_anchors  replaces the join and the per-read std::sort of AlignReadsLowDensityFunctor::operator() (:668-756) for the reads
+ *       [query_begin, query_end) of `queries` (0, 0: all).  A query below 10 minimizers produces nothing (Utils::isReadTooShort,
+ *       Commons.hpp:2190); every other window produces one anchor per index entry of its pair whose global read number differs from the
+ *       query's own: (ref_read, ref_position, ref_index, query_position, query_index, reversed = ref.reversed != query.reversed).  The
+ *       anchors of a query are in (ref_read, ref_position, query_position) order, the queries in read order; the anchors of one (query,
+ *       ref_read) are a PAIR, and pairs of fewer than min_anchors anchors are dropped (processAnchors, :850: 3; 0 and 1 keep everything).
+ *       Result: pair_offsets[n_queries + 1]; per pair ref_read and anchor_offsets[n_pairs + 1]; the six arrays per anchor.
+ *       info: queries, pairs, anchors, the longest pair.  device_ptrs, in order: pair_offsets (u64), pair_ref_read (u32), anchor_offsets
+ *       (u64), ref_read, ref_position, ref_index, query_position, query_index (u32), reversed (u8).
+ *       MDBG_ERANGE: the call would produce 2^32 anchors or more -- known after the count pass, before anything is allocated for them; the
+ *       message says how many query reads from query_begin fit.  MDBG_EINVAL: a query range outside the set.
+ *       Timer names: "map_count", "map_fill", "map_group", "radix_sort".
+ *
+ * mdbg_map_chains  replaces chainAnchors + argmaxPosition (:887-1230): one row per pair, in the pairs' order.  Scores are integers: the
+ *       reference's floats are sums of 20 - gap with an integer gap <= 100, exact while a pair has fewer than 2^24 / 80 = 209 715
+ *       anchors; a longer pair gets flags = MDBG_CHAIN_TOO_LONG and zero fields, never an approximate chain.  For anchor i ascending,
+ *       score[i] = 20 without parent unless a predecessor j = i - 1 ... max(0, i - max_chaining_band) qualifies: skipped when the
+ *       reversed flags differ, ref_position or query_position are equal, d_q (q_i - q_j; q_j - q_i when reversed) > 5000, d_r > 5000,
+ *       d_r <= 0, |d_r - d_q| > 100, d_q < 0; new = score[j] + 20 - |d_r - d_q|, the best strictly positive new wins, on a tie the LARGEST
+ *       j.  The best anchor has the largest score, on a tie the SMALLEST i.  Its chain (the parents walked to the root) of fewer than 3
+ *       anchors is no chain (flags 0, zero fields).  Otherwise flags = MDBG_CHAIN_FOUND and the fields are Chain2's as :1017-1047 leaves
+ *       them, `first` the best anchor and `last` the root: score, n_matches, query_reversed = first.query_index > last.query_index (true for
+ *       a same-strand match), n_diff_query, n_diff_reference, query_start / query_end (indexes), reference_start = first.ref_position,
+ *       reference_end = last.ref_position, alignment_score = n_matches - n_diff_query (:1241), and the pair's match list
+ *       _queryAnchorPositions: the query indexes from the best anchor to the root, turned round when query_reversed.
+ *       Result: pair_offsets[n_queries + 1] (the anchors' own), chains[n_pairs], match_offsets[n_pairs + 1], matches.
+ *       info: queries, pairs, chains found, matches in all.  device_ptrs, in order: pair_offsets, chains, match_offsets, matches.
+ *       MDBG_EINVAL: max_chaining_band 0.  Timer names: "map_chains", "map_matches".
+ * What stays with the caller: the per-position top-20 selection (addAlignmentScore, :1233-1313), the compression of the match lists and the
+ * partition files. */
+typedef struct mdbg_map_index mdbg_map_index;
+typedef struct mdbg_anchors mdbg_anchors;
+typedef struct mdbg_chains mdbg_chains;
+typedef struct { uint32_t max_chaining_band;   /* ReadCorrection.hpp:1738: (u64)(2500 * density_correction), 62 at 0.025 */
+                 uint32_t min_anchors;         /* ReadMapper.hpp:850: 3 */
+                 uint32_t query_begin, query_end; /* reads [begin, end) of the query set; 0, 0 = all */
+                 uint32_t reserved[4]; } mdbg_map_params;
+#define MDBG_CHAIN_FOUND    1u
+#define MDBG_CHAIN_TOO_LONG 2u
+typedef struct { uint32_t ref_read, flags; int32_t score; uint32_t n_matches, query_reversed, reserved;
+                 int64_t n_diff_query, n_diff_reference, query_start, query_end, reference_start, reference_end, alignment_score; } mdbg_chain;
+int  mdbg_minimizers_attach_positions(mdbg_ctx *ctx, mdbg_minimizers *m, const uint32_t *positions);
+int  mdbg_map_index_build(mdbg_ctx *ctx, const mdbg_minimizers *chunk, uint32_t chunk_first_read, mdbg_map_index **out);
+int  mdbg_map_index_info(const mdbg_map_index *ix, uint64_t info[4]);
+int  mdbg_map_index_to_host(mdbg_ctx *ctx, const mdbg_map_index *ix, uint64_t *pairs, uint32_t *reads, uint32_t *positions, uint32_t *indexes,
+                            uint8_t *reversed);
+void mdbg_map_index_free(mdbg_map_index *ix);
+int  mdbg_map_anchors(mdbg_ctx *ctx, const mdbg_map_index *ix, const mdbg_minimizers *queries, uint32_t query_first_read,
+                      const mdbg_map_params *p, mdbg_anchors **out);
+int  mdbg_anchors_info(const mdbg_anchors *a, uint64_t info[4]);
+int  mdbg_anchors_to_host(mdbg_ctx *ctx, const mdbg_anchors *a, uint64_t *pair_offsets, uint32_t *pair_ref_read, uint64_t *anchor_offsets,
+                          uint32_t *ref_read, uint32_t *ref_position, uint32_t *ref_index, uint32_t *query_position, uint32_t *query_index,
+                          uint8_t *reversed);
+int  mdbg_anchors_device_ptrs(const mdbg_anchors *a, const void *d_ptrs[9]);
+void mdbg_anchors_free(mdbg_anchors *a);
+int  mdbg_map_chains(mdbg_ctx *ctx, const mdbg_anchors *a, const mdbg_map_params *p, mdbg_chains **out);
+int  mdbg_chains_info(const mdbg_chains *c, uint64_t info[4]);
+int  mdbg_chains_to_host(mdbg_ctx *ctx, const mdbg_chains *c, uint64_t *pair_offsets, mdbg_chain *chains, uint64_t *match_offsets, uint32_t *matches);
+int  mdbg_chains_device_ptrs(const mdbg_chains *c, const void *d_ptrs[4]);
+void mdbg_chains_free(mdbg_chains *c);
+/* The library's stable radix sort (8-bit digits, least significant first; a digit in which all keys agree is skipped) on caller-chosen
+   data: n uint64 keys from byte keys_at of `keys` and their n uint32 values from byte values_at of `values`, sorted by key in place, equal
+   keys keeping their order.  Returns when done.  info (optional): digit passes run, digit passes skipped.  MDBG_EINVAL: a null argument,
+   keys_at not a multiple of 8, values_at not a multiple of 4, a range that leaves its object, overlapping ranges of one object.
+   MDBG_ERANGE: 2^32 items or more.  Timer name: "radix_sort". */
+int  mdbg_bytes_sort_u64_pairs(mdbg_ctx *ctx, mdbg_bytes *keys, uint64_t keys_at, mdbg_bytes *values, uint64_t values_at, uint64_t n,
+                               uint64_t info[2]);
+
 /* ---- FASTA / FASTQ text taken apart on the device -----------------------------------------------------------------------------------
  * Replaces the host side of ReadParserParallel for a plain file: the kseq loop (KSEQ_INIT(gzFile, gzread), Commons.hpp:82) that
  * ReadParser::parse / ReadParserParallel::parse run over every character (Commons.hpp:5827-5922).  The file's bytes travel as they are

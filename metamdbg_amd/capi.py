@@ -22,6 +22,10 @@ SEQ_REQUEST = np.dtype([("window", "<u8"), ("part", "<u4"), ("reserved", "<u4")]
 SEQ_RANGE = np.dtype([("read", "<u4"), ("start", "<u4"), ("length", "<u4"), ("reversed", "<u4")])  # mdbg_seq_range
 STITCH_PIECE = np.dtype([("window", "<u8"), ("part", "<u4"), ("flip", "<u4")])                      # mdbg_stitch_piece
 STITCH_NONE = 0xFFFFFFFFFFFFFFFF            # MDBG_STITCH_NONE: no sequence for this k-min-mer
+CHAIN_FOUND, CHAIN_TOO_LONG = 1, 2          # MDBG_CHAIN_*: the flags of a row of mdbg_map_chains
+CHAIN = np.dtype([("ref_read", "<u4"), ("flags", "<u4"), ("score", "<i4"), ("n_matches", "<u4"), ("query_reversed", "<u4"), ("reserved", "<u4"),
+                  ("n_diff_query", "<i8"), ("n_diff_reference", "<i8"), ("query_start", "<i8"), ("query_end", "<i8"),
+                  ("reference_start", "<i8"), ("reference_end", "<i8"), ("alignment_score", "<i8")])        # mdbg_chain
 
 
 class MdbgError(RuntimeError):
@@ -35,6 +39,11 @@ class ScanParams(C.Structure):
                 ("min_read_quality", C.c_float), ("repetitive", C.POINTER(C.c_uint32)),
                 ("n_repetitive", C.c_uint32), ("apply_read_filters", C.c_int32), ("quality_window", C.c_int32), ("no_end_trim", C.c_int32),
                 ("ignore_qualities", C.c_int32)]
+
+
+class MapParams(C.Structure):
+    _fields_ = [("max_chaining_band", C.c_uint32), ("min_anchors", C.c_uint32), ("query_begin", C.c_uint32), ("query_end", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
 
 
 # name -> (restype, argtypes); every symbol include/mdbg_hip.h declares
@@ -160,6 +169,22 @@ SIGNATURES = {
     "mdbg_bytes_copy": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64]),
     "mdbg_fastx_whole_records": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, _u64p, C.POINTER(C.c_int)]),
     "mdbg_bytes_prefix_sum": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64]),
+    "mdbg_bytes_sort_u64_pairs": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64, _u64p]),
+    "mdbg_minimizers_attach_positions": (C.c_int, [_P, _P, _P]),
+    "mdbg_map_index_build": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    "mdbg_map_index_info": (C.c_int, [_P, _u64p]),
+    "mdbg_map_index_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "mdbg_map_index_free": (None, [_P]),
+    "mdbg_map_anchors": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(MapParams), C.POINTER(_P)]),
+    "mdbg_anchors_info": (C.c_int, [_P, _u64p]),
+    "mdbg_anchors_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mdbg_anchors_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_anchors_free": (None, [_P]),
+    "mdbg_map_chains": (C.c_int, [_P, _P, C.POINTER(MapParams), C.POINTER(_P)]),
+    "mdbg_chains_info": (C.c_int, [_P, _u64p]),
+    "mdbg_chains_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "mdbg_chains_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_chains_free": (None, [_P]),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
@@ -593,6 +618,47 @@ class Context:
         total; queued in stream order, not waited for (mdbg_bytes_prefix_sum)."""
         self.check(lib().mdbg_bytes_prefix_sum(self.h, src.h if src is not None else None, src_at, width, n, dst.h if dst is not None else None, dst_at))
 
+    def bytes_sort_u64_pairs(self, keys: "DeviceBytes", keys_at: int, values: "DeviceBytes", values_at: int, n: int) -> dict:
+        """The n uint64 keys at keys[keys_at ...) and their uint32 values at values[values_at ...) sorted by key in place, equal keys in
+        their order (mdbg_bytes_sort_u64_pairs); returns dict(passes_run, passes_skipped)."""
+        info = (C.c_uint64 * 2)()
+        self.check(lib().mdbg_bytes_sort_u64_pairs(self.h, keys.h if keys is not None else None, keys_at, values.h if values is not None else None, values_at, n, info))
+        return dict(passes_run=int(info[0]), passes_skipped=int(info[1]))
+
+    # -- reads mapped against reads in minimizer space ------------------------------------------------
+    def minimizers_with_positions(self, mins: np.ndarray, offsets: np.ndarray, positions: np.ndarray) -> "Minimizers":
+        """A set from the host with the position array a scan output has (mdbg_minimizers_from_host + mdbg_minimizers_attach_positions)."""
+        m = self.minimizers_from_host(mins, offsets)
+        m.attach_positions(positions)
+        return m
+
+    @staticmethod
+    def _map_params(band: int, min_anchors: int, query_begin: int, query_end: int) -> MapParams:
+        return MapParams(band, min_anchors, query_begin, query_end, (C.c_uint32 * 4)())
+
+    def map_index_build(self, chunk: "Minimizers", chunk_first_read: int = 0) -> "MapIndex":
+        """Every window of two minimizers of the chunk's reads, grouped by pair (mdbg_map_index_build)."""
+        h = C.c_void_p()
+        self.check(lib().mdbg_map_index_build(self.h, chunk.h if chunk is not None else None, chunk_first_read, C.byref(h)))
+        return MapIndex(self, h)
+
+    def map_anchors(self, index: "MapIndex", queries: "Minimizers", query_first_read: int = 0, min_anchors: int = 3, query_begin: int = 0,
+                    query_end: int = 0, band: int = 62) -> "Anchors":
+        """The anchors of the query reads [query_begin, query_end) (0, 0: all) against the index, grouped per (query, reference read)
+        (mdbg_map_anchors)."""
+        h = C.c_void_p()
+        p = self._map_params(band, min_anchors, query_begin, query_end)
+        self.check(lib().mdbg_map_anchors(self.h, index.h if index is not None else None, queries.h if queries is not None else None, query_first_read, C.byref(p),
+                                          C.byref(h)))
+        return Anchors(self, h)
+
+    def map_chains(self, anchors: "Anchors", band: int = 62) -> "Chains":
+        """One chain row per pair of the anchors (mdbg_map_chains); band is max_chaining_band."""
+        h = C.c_void_p()
+        p = self._map_params(band, 0, 0, 0)
+        self.check(lib().mdbg_map_chains(self.h, anchors.h if anchors is not None else None, C.byref(p), C.byref(h)))
+        return Chains(self, h)
+
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
         cut, fmt = C.c_uint64(0), C.c_int(0)
@@ -908,6 +974,11 @@ class Minimizers:
         lib().mdbg_minimizers_device_ptrs(self.h, C.byref(a), C.byref(b))
         return a.value or 0, b.value or 0
 
+    def attach_positions(self, positions: np.ndarray) -> None:
+        """One position per minimizer, strictly rising inside a read and below 2^31 (mdbg_minimizers_attach_positions)."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32)
+        self.ctx.check(lib().mdbg_minimizers_attach_positions(self.ctx.h, self.h, _ptr(pos) if len(pos) else None))
+
     def free(self) -> None:
         if self.h:
             lib().mdbg_minimizers_free(self.h)
@@ -918,6 +989,90 @@ class Minimizers:
             self.free()
         except Exception:
             pass
+
+
+class _MapHandle:
+    _free = None
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h = ctx, h
+
+    def free(self) -> None:
+        if self.h:
+            getattr(lib(), self._free)(self.h)
+            self.h = None
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MapIndex(_MapHandle):
+    """The windows of a chunk's reads grouped by minimizer pair (mdbg_map_index_build)."""
+    _free = "mdbg_map_index_free"
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_map_index_info(self.h, a)
+        return dict(zip(("n_entries", "n_pairs", "longest_run", "n_reads"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        n = self.info()["n_entries"]
+        out = dict(pair=np.zeros(n, np.uint64), read=np.zeros(n, np.uint32), position=np.zeros(n, np.uint32), index=np.zeros(n, np.uint32),
+                   reversed=np.zeros(n, np.uint8))
+        self.ctx.check(lib().mdbg_map_index_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+
+class Anchors(_MapHandle):
+    """The anchors of a batch of query reads, grouped per (query, reference read) (mdbg_map_anchors)."""
+    _free = "mdbg_anchors_free"
+    _NAMES = ("pair_offsets", "pair_ref_read", "anchor_offsets", "ref_read", "ref_position", "ref_index", "query_position", "query_index", "reversed")
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_anchors_info(self.h, a)
+        return dict(zip(("n_queries", "n_pairs", "n_anchors", "longest_pair"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        i = self.info()
+        q, p, n = i["n_queries"], i["n_pairs"], i["n_anchors"]
+        out = dict(pair_offsets=np.zeros(q + 1, np.uint64), pair_ref_read=np.zeros(p, np.uint32), anchor_offsets=np.zeros(p + 1, np.uint64),
+                   ref_read=np.zeros(n, np.uint32), ref_position=np.zeros(n, np.uint32), ref_index=np.zeros(n, np.uint32),
+                   query_position=np.zeros(n, np.uint32), query_index=np.zeros(n, np.uint32), reversed=np.zeros(n, np.uint8))
+        self.ctx.check(lib().mdbg_anchors_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = (C.c_void_p * 9)()
+        lib().mdbg_anchors_device_ptrs(self.h, p)
+        return dict(zip(self._NAMES, [x or 0 for x in p]))
+
+
+class Chains(_MapHandle):
+    """One chain row per pair of an Anchors, and the match lists (mdbg_map_chains)."""
+    _free = "mdbg_chains_free"
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_chains_info(self.h, a)
+        return dict(zip(("n_queries", "n_pairs", "n_chains", "n_matches"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        i = self.info()
+        out = dict(pair_offsets=np.zeros(i["n_queries"] + 1, np.uint64), chains=np.zeros(i["n_pairs"], CHAIN),
+                   match_offsets=np.zeros(i["n_pairs"] + 1, np.uint64), matches=np.zeros(i["n_matches"], np.uint32))
+        self.ctx.check(lib().mdbg_chains_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = (C.c_void_p * 4)()
+        lib().mdbg_chains_device_ptrs(self.h, p)
+        return dict(zip(("pair_offsets", "chains", "match_offsets", "matches"), [x or 0 for x in p]))
 
 
 class Spans:

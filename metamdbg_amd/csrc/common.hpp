@@ -232,6 +232,7 @@ const StepKernel *prims_step_kernels(uint32_t *n);
 const StepKernel *scan_step_kernels(uint32_t *n);
 const StepKernel *extract_step_kernels(uint32_t *n);
 const StepKernel *stitch_step_kernels(uint32_t *n);
+const StepKernel *mapper_step_kernels(uint32_t *n);
 
 int set_error(mdbg_ctx *ctx, int code, const char *fmt, ...);
 extern thread_local std::string g_last_error;  // for failures before a context exists (per calling thread)
@@ -439,6 +440,10 @@ __device__ __forceinline__ WaveSpan wave_span(uint64_t n_items, uint32_t unit) {
 // device-wide exclusive scan (prims.hip): out[i] = sum(in[0..i)), out[n] = total; out has n+1 entries.
 int exclusive_scan_u32(mdbg_ctx *ctx, const uint32_t *d_in, uint64_t *d_out, uint64_t n);
 int exclusive_scan_u64(mdbg_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint64_t n);     // ... of 64-bit values (d_in != d_out)
+
+// device-wide stable sort of (64-bit key, 32-bit value) pairs by key, in place (prims.hip); n < 2^32.  passes (optional): [0] digit passes
+// run, [1] skipped because every key agreed in the digit.  Waits for the stream once (the digits that differ travel to the host).
+int sort_u64_pairs(mdbg_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t passes[2]);
 
 // density (f32) -> integer threshold: hash < T  <=>  (double)hash < (double)density * 2^64, the compare of
 // MinimizerParser (utils/kmer/Kmer.hpp:1421-1430) and Utils::applyDensityThreshold (Commons.hpp:2524-2533; its

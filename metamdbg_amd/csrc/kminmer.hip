@@ -1584,7 +1584,7 @@ extern "C" int mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]) {
 
 // ---- what the runtime knows of a kernel of the step (the residency rule is checked against the loaded code object) -------------------
 static const StepKernel *step_kernel_at(uint32_t i) {
-    const StepKernel *(*const tables[])(uint32_t *) = {scan_step_kernels, minimizers_step_kernels, prims_step_kernels, partition_step_kernels, extract_step_kernels, stitch_step_kernels};
+    const StepKernel *(*const tables[])(uint32_t *) = {scan_step_kernels, minimizers_step_kernels, prims_step_kernels, partition_step_kernels, extract_step_kernels, stitch_step_kernels, mapper_step_kernels};
     for (auto table : tables) {
         uint32_t n = 0;
         const StepKernel *k = table(&n);
