@@ -294,3 +294,22 @@ extern "C" void mdbg_host_free(mdbg_ctx *ctx, void *p) {
     (void)ctx;
     if (p) (void)hipHostFree(p);
 }
+
+// ---- how the context's last first pass ran (written by kminmer.hip and partition.hip) ----
+extern "C" int mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]) {
+    if (!ctx || !info) return MDBG_EINVAL;
+    for (int i = 0; i < 8; i++) info[i] = ctx->part_info[i];
+    return MDBG_OK;
+}
+
+extern "C" int mdbg_first_pass_form(const mdbg_ctx *ctx, uint64_t form[4]) {
+    if (!ctx || !form) return MDBG_EINVAL;
+    for (int i = 0; i < 4; i++) form[i] = ctx->part_form[i];
+    return MDBG_OK;
+}
+
+extern "C" int mdbg_first_pass_slot_fall_backs(const mdbg_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return MDBG_EINVAL;
+    *n = ctx->part_fell_back;
+    return MDBG_OK;
+}

@@ -12,13 +12,13 @@
 //                              previous table, missing/0 => 1; keep > 1 (graph/CreateMdbg.hpp:3933-4005)
 //   k >= firstK+2            : abundance = min(prev[i], prev[i+1]) along the sequence; insert-if-absent
 //                              when > 1 (graph/CreateMdbg.hpp:1240-1265, :1450-1459)
+// The table handle's own entry points are tables.hip, the sharded passes shard.hip; kminmer_host.hpp declares what they call here.
 #include "common.hpp"
 #include "murmur.hpp"
 #include "objects.hpp"
 #include "table.hpp"
 #include "kminmer_dev.hpp"
-
-#include <vector>
+#include "kminmer_host.hpp"
 
 namespace mdbg {
 
@@ -29,58 +29,6 @@ __global__ void inst_count_kernel(const uint64_t *off, uint32_t n_reads, uint32_
         uint64_t n = off[r + 1] - off[r];
         cnt[r] = n >= k ? (uint32_t)(n - k + 1) : 0u;
     }
-}
-
-// read owning global instance g: largest r with inst_off[r] <= g
-__device__ __forceinline__ uint32_t find_read(const uint64_t *inst_off, uint32_t n_reads, uint64_t g) {
-    uint32_t lo = 0, hi = n_reads;  // invariant: inst_off[lo] <= g < inst_off[hi]
-    while (hi - lo > 1) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (inst_off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t table_upsert_count(const TableView &t, uint64_t lo, uint64_t hi, uint32_t add, uint32_t rep) {
-    if (lo == 0ull || hi == 0ull) return table_exc_upsert(t, lo, hi, add, 0, false, rep, true);
-    bool created = false;
-    uint32_t s = table_find_or_insert(t, lo, hi, true, &created);
-    if (s != SLOT_NONE) {
-        if (add) atomicAdd(&t.slots[s].val, add);
-        if (created) t.slots[s].rep = rep;   // the instance that published the key represents it: one store per key, not per instance
-    }
-    return s;
-}
-
-__device__ __forceinline__ uint32_t table_upsert_set(const TableView &t, uint64_t lo, uint64_t hi, uint32_t v, uint32_t rep) {
-    if (lo == 0ull || hi == 0ull) return table_exc_upsert(t, lo, hi, 0, v, true, rep, true);
-    bool created = false;
-    uint32_t s = table_find_or_insert(t, lo, hi, true, &created);
-    if (s != SLOT_NONE) {
-        __hip_atomic_store(&t.slots[s].val, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (created) t.slots[s].rep = rep;
-    }
-    return s;
-}
-
-// insert-if-absent with a value that is a function of the key (the index passes: min of the previous abundances of the window's two
-// sub-windows, the same for every instance of the key and in either orientation): only the instance that publishes the key stores it.
-// The other instances -- nineteen in twenty at 50x -- stop at the probe instead of each sending its own copy of the value to memory.
-__device__ __forceinline__ uint32_t table_insert_once(const TableView &t, uint64_t lo, uint64_t hi, uint32_t v) {
-    if (lo == 0ull || hi == 0ull) return table_exc_upsert(t, lo, hi, 0, v, true, 0u, true);
-    bool created = false;
-    uint32_t s = table_find_or_insert(t, lo, hi, true, &created);
-    if (s != SLOT_NONE && created) __hip_atomic_store(&t.slots[s].val, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return s;
-}
-
-// the same when the rows of the table carry their vectors (k = firstK + 1): the publishing instance also names itself
-__device__ __forceinline__ uint32_t table_insert_once_rep(const TableView &t, uint64_t lo, uint64_t hi, uint32_t v, uint32_t rep) {
-    if (lo == 0ull || hi == 0ull) return table_exc_upsert(t, lo, hi, 0, v, true, rep, true);
-    bool created = false;
-    uint32_t s = table_find_or_insert(t, lo, hi, true, &created);
-    if (s != SLOT_NONE && created) { __hip_atomic_store(&t.slots[s].val, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); t.slots[s].rep = rep; }
-    return s;
 }
 
 // Visit every instance with 16 lanes per sequence (4 sequences per wave): sequences hold a few dozen
@@ -287,14 +235,6 @@ __global__ __launch_bounds__(256) void emit_rescued_kernel(SeqView s, uint32_t k
         }
     }
 }
-
-// The rescue pass over one read set against the counts in `t`: per-read decision, row positions, total.
-struct RescuePlan {
-    DevBuf<uint8_t> cls;      // 2-bit count class per table slot
-    DevBuf<uint32_t> cnt;
-    DevBuf<uint64_t> pos;
-    uint64_t cap = 0, total = 0;
-};
 
 // ---- k > firstK --------------------------------------------------------------------------------------
 // distinct keys of all k-windows (k = firstK+1)
@@ -808,152 +748,6 @@ __global__ __launch_bounds__(256) void table_occupied_kernel(TableView t, uint64
     if (threadIdx.x == 0 && n) atomicAdd(&occ_count[blockIdx.x % TABLE_OCC_WAYS], (uint32_t)n);
 }
 
-// ---- prev tables ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rows_insert_kernel(const uint64_t *lo, const uint64_t *hi, const uint32_t *ab, uint64_t n,
-                                                          int skip_one, TableView t) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (skip_one && ab[i] == 1u) return;   // graph/CreateMdbg.cpp:3445
-    table_upsert_set(t, lo[i], hi[i], ab[i], 0u);
-}
-
-// (graph/CreateMdbg.cpp:3466-3507)
-__global__ __launch_bounds__(256) void overlay_kernel(SeqView s, uint32_t kprev, const uint32_t *unitig_ab, TableView t) {
-    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= s.n_inst) return;
-    uint32_t r = find_read(s.inst_off, s.n_reads, g);
-    uint32_t a = unitig_ab[r];
-    if (a == 0xFFFFFFFFu) return;   // unitig without refined abundance
-    const uint32_t *m = s.mins + s.off[r] + (g - s.inst_off[r]);
-    uint64_t hi, lo;
-    window_hash(m, kprev, hi, lo);
-    if (a == 1u) {
-        // modify_if: set to 0 only when present
-        if (lo == 0ull || hi == 0ull) { table_exc_upsert(t, lo, hi, 0, 0, true, 0, false); return; }
-        uint32_t slot = table_find_or_insert(t, lo, hi, false);
-        if (slot != SLOT_NONE) __hip_atomic_store(&t.slots[slot].val, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        table_upsert_set(t, lo, hi, a, 0u);
-    }
-}
-
-__global__ __launch_bounds__(256) void lookup_kernel(TableView t, const uint64_t *lo, const uint64_t *hi, uint64_t n, uint32_t *out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t v;
-    out[i] = table_lookup(t, lo[i], hi[i], v) ? v : 0u;
-}
-
-// small-contig test of IndexKminmerFunctor (graph/CreateMdbg.hpp:1330; getAbundance(0, .) :988-1010): one thread per unitig
-__global__ __launch_bounds__(256) void small_contig_kernel(const uint64_t *off, uint32_t n_unitigs, const uint32_t *mins, uint32_t k,
-                                                           uint32_t k_prev, TableView prev, uint8_t *flags) {
-    uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_unitigs) return;
-    const uint64_t b = off[u], n = off[u + 1] - b;
-    uint8_t f = 0;
-    if (n < k && n >= k_prev) {
-        const uint32_t windows = (n - k_prev + 1) < 2 ? 1u : 2u;     // prev[0], or min(prev[0], prev[1])
-        uint32_t a = 0xFFFFFFFFu;
-        for (uint32_t i = 0; i < windows; i++) {
-            uint64_t hi, lo;
-            window_hash(mins + b + i, k_prev, hi, lo);
-            uint32_t v;
-            if (!table_lookup(prev, lo, hi, v)) v = 1u;               // getPrevAbundances: missing => 1 (:1240-1265)
-            a = v < a ? v : a;
-        }
-        f = a > 1u;
-    }
-    flags[u] = f;
-}
-
-// EdgeIndexer::partitionNode (graph/CreateMdbg.hpp:4083-4100): prefix and suffix identities of one node
-__global__ __launch_bounds__(256) void edge_insert_kernel(const uint32_t *vecs, uint64_t n, uint32_t k, TableView t) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t *v = vecs + i * k;
-    uint64_t hi, lo;
-    window_hash(v, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-    window_hash(v + 1, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-}
-
-// UnitigEdgeIndexer::partitionUnitig (graph/CreateMdbg.hpp:4352-4389): the same two identities for the first and
-// the last k-min-mer of every unitig (the last one skipped when it is the first).  The reference normalises the node
-// before taking prefix and suffix; the pair {prefix, suffix} of a vector and of its reverse are each other's reverses,
-// and every identity is taken on the normalised (k-1)-vector, so the orientation of the node does not matter.
-__global__ __launch_bounds__(256) void unitig_edge_insert_kernel(const uint64_t *off, uint32_t n_unitigs, const uint32_t *mins, uint32_t k, TableView t) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_unitigs) return;
-    const uint64_t f = off[i], n = off[i + 1] - f;
-    if (n < k) return;
-    uint64_t hi, lo;
-    const uint32_t *v = mins + f;
-    window_hash(v, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-    window_hash(v + 1, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-    if (n == k) return;
-    v = mins + f + (n - k);
-    window_hash(v, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-    window_hash(v + 1, k - 1, hi, lo);
-    table_upsert_count(t, lo, hi, 0u, 0u);
-}
-
-__global__ __launch_bounds__(256) void sum_u64_kernel(const uint64_t *v, uint64_t n, unsigned long long *out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t x = i < n ? v[i] : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    if ((threadIdx.x & 63u) == 0 && x) atomicAdd(out, (unsigned long long)x);
-}
-
-// out[0] += sum abundance * lo (the reference's "Checksum kminmer abundance"), out[1] += sum abundance, out[2] += sum hi,
-// out[3] += sum over rows with a vector of (v[0] + 3 v[1] + 5 v[2] ...) * (lo | 1): ties the vectors to their keys
-__global__ __launch_bounds__(256) void table_checksum_kernel(const uint64_t *lo, const uint64_t *hi, const uint32_t *ab, const uint32_t *vec,
-                                                             uint32_t k, uint64_t n, unsigned long long *out) {
-    uint64_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t l = lo[i], a = ab[i];
-        s0 += a * l; s1 += a; s2 += hi[i];
-        if (vec) {
-            uint64_t w = 0;
-            for (uint32_t j = 0; j < k; j++) w += (uint64_t)vec[i * k + j] * (2u * j + 1u);
-            s3 += w * (l | 1ull);
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        s0 += __shfl_xor(s0, d, 64); s1 += __shfl_xor(s1, d, 64); s2 += __shfl_xor(s2, d, 64); s3 += __shfl_xor(s3, d, 64);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        atomicAdd(out + 0, (unsigned long long)s0); atomicAdd(out + 1, (unsigned long long)s1);
-        atomicAdd(out + 2, (unsigned long long)s2); atomicAdd(out + 3, (unsigned long long)s3);
-    }
-}
-
-__global__ void interleave_keys_kernel(const uint64_t *lo, const uint64_t *hi, uint64_t n, uint64_t *out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { out[2 * i] = lo[i]; out[2 * i + 1] = hi[i]; }
-}
-
-__global__ void unpack_records_kernel(const uint8_t *rec, uint64_t n, uint64_t *lo, uint64_t *hi, uint32_t *ab) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t *p = reinterpret_cast<const uint32_t *>(rec) + 5 * i;      // (records are 20 bytes from a 256-byte aligned start)
-    lo[i] = (uint64_t)p[0] | ((uint64_t)p[1] << 32); hi[i] = (uint64_t)p[2] | ((uint64_t)p[3] << 32); ab[i] = p[4];
-}
-
-__global__ void pack_records_kernel(const uint64_t *lo, const uint64_t *hi, const uint32_t *ab, uint64_t n, uint8_t *rec) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint8_t *p = rec + 20 * i;
-    uint64_t l = lo[i], h = hi[i]; uint32_t a = ab[i];
-    for (int b = 0; b < 8; b++) { p[b] = (uint8_t)(l >> (8 * b)); p[8 + b] = (uint8_t)(h >> (8 * b)); }
-    for (int b = 0; b < 4; b++) p[16 + b] = (uint8_t)(a >> (8 * b));
-}
-
 // ---- host helpers ------------------------------------------------------------------------------------------
 // Size the next table of this kind for the distinct keys just seen (+12.5 %): build_table_adaptive doubles that and
 // rounds up to a power of two, i.e. 25-45 % load.
@@ -961,12 +755,7 @@ void update_key_hint(mdbg_ctx *ctx, int kind, uint64_t distinct, uint64_t instan
     if (instances) { ctx->key_ratio_hint[kind] = 1.125 * (double)distinct / (double)instances; ctx->key_ratio_known[kind] = true; }
 }
 
-struct InstIndex {
-    DevBuf<uint64_t> off;   // n_reads + 1
-    uint64_t total = 0;
-};
-
-static int build_inst_index(mdbg_ctx *ctx, const mdbg_minimizers *m, uint32_t k, InstIndex &ix) {
+int build_inst_index(mdbg_ctx *ctx, const mdbg_minimizers *m, uint32_t k, InstIndex &ix) {
     DevBuf<uint32_t> cnt;
     MDBG_TRY(cnt.alloc(ctx, m->n_reads));
     MDBG_TRY(ix.off.alloc(ctx, (size_t)m->n_reads + 1));
@@ -978,8 +767,7 @@ static int build_inst_index(mdbg_ctx *ctx, const mdbg_minimizers *m, uint32_t k,
 }
 
 // dense counts + per-read rescue decision + row positions (only meaningful when min_abundance <= 1)
-static int plan_rescue(mdbg_ctx *ctx, const DeviceTable &tab, const InstIndex &ix, uint32_t n_reads, const uint32_t *inst_slot,
-                       RescuePlan &p) {
+int plan_rescue(mdbg_ctx *ctx, const DeviceTable &tab, const InstIndex &ix, uint32_t n_reads, const uint32_t *inst_slot, RescuePlan &p) {
     TableView tv = tab.view();
     const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
     const uint32_t m_star = rescue_m_star();
@@ -1002,13 +790,12 @@ static int plan_rescue(mdbg_ctx *ctx, const DeviceTable &tab, const InstIndex &i
     return MDBG_OK;
 }
 
-static void launch_emit_rescued(mdbg_ctx *ctx, const SeqView &sv, uint32_t k, const uint32_t *inst_slot, const RescuePlan &p, const RowOut &ro,
-                                uint64_t row_base) {
+void launch_emit_rescued(mdbg_ctx *ctx, const SeqView &sv, uint32_t k, const uint32_t *inst_slot, const RescuePlan &p, const RowOut &ro, uint64_t row_base) {
     unsigned blocks = grid_for((uint64_t)sv.n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
     hipLaunchKernelGGL(emit_rescued_kernel, dim3(blocks), dim3(256), 0, ctx->stream, sv, k, inst_slot, p.cls.p, p.cap, p.cnt.p, p.pos.p, ro, row_base);
 }
 
-static SeqView make_view(const mdbg_minimizers *m, const InstIndex &ix) {
+SeqView make_view(const mdbg_minimizers *m, const InstIndex &ix) {
     SeqView v;
     v.mins = m ? m->d_min.p : nullptr;
     v.off = m ? m->d_off.p : nullptr;
@@ -1029,15 +816,59 @@ int alloc_rows(mdbg_ctx *ctx, mdbg_table *t, uint64_t n, bool vec) {
     return MDBG_OK;
 }
 
-}  // namespace mdbg
-
-using namespace mdbg;
-
-static int check_seq(mdbg_ctx *ctx, const mdbg_minimizers *m, const char *who) {
+int check_seq(mdbg_ctx *ctx, const mdbg_minimizers *m, const char *who) {
     if (!m) return set_error(ctx, MDBG_EINVAL, "%s: null sequence set", who);
     if (m->n_min >= (1ull << 32)) return set_error(ctx, MDBG_ERANGE, "%s: more than 2^32 minimizers in one batch", who);
     return ensure_canonical(ctx, m);      // a scan output handed over without the purge in between
 }
+
+// distinct keys are usually a small fraction of the instances (coverage): start small so the table
+// stays cache-resident, grow and rebuild when a probe sequence gets long
+int count_instances(mdbg_ctx *ctx, const SeqView &sv, uint32_t k, int hint_kind, DeviceTable &tab, DevBuf<uint32_t> &inst_slot) {
+    const uint64_t I = sv.n_inst;
+    MDBG_TRY(inst_slot.alloc(ctx, I));
+    return build_table_adaptive(ctx, tab, (uint64_t)((double)I * ctx->key_ratio_hint[hint_kind]), I, [&](TableView v) {
+        if (I) {
+            LaunchTimer timer(ctx, "kminmer_insert");
+            hipLaunchKernelGGL(count_insert_kernel, dim3(instance_grid(ctx, sv.n_reads)), dim3(256), 0, ctx->stream, sv, k, v, inst_slot.p, (uint64_t)0);
+        }
+        return MDBG_OK;
+    }, ctx->key_ratio_known[hint_kind]);
+}
+
+int flag_occupied_slots(mdbg_ctx *ctx, const DeviceTable &tab, DevBuf<uint32_t> &flag) {
+    const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
+    MDBG_TRY(flag.alloc(ctx, nslots));
+    hipLaunchKernelGGL(slot_flag_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tab.view(), tab.cap, 0u, 2, flag.p);
+    return MDBG_OK;
+}
+
+int rows_from_flags(mdbg_ctx *ctx, const DeviceTable &tab, const DevBuf<uint32_t> &flag, uint32_t k, const SeqView &a, const SeqView &b, bool vectors,
+                    FlaggedRows &how, std::unique_ptr<mdbg_table> &out) {
+    const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
+    DevBuf<uint64_t> &pos = how.pos;
+    MDBG_TRY(pos.alloc(ctx, nslots + 1));
+    MDBG_TRY(exclusive_scan_u32(ctx, flag.p, pos.p, nslots));
+    uint64_t n_rows = 0, extra = 0;
+    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_rows, pos.p + nslots, 8, hipMemcpyDeviceToHost));
+    if (how.extra_rows) MDBG_TRY(how.extra_rows(n_rows, extra));
+    std::unique_ptr<mdbg_table> t(new mdbg_table());
+    t->k = k;
+    t->n_solid = n_rows;
+    MDBG_TRY(alloc_rows(ctx, t.get(), n_rows + extra, vectors));
+    const RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, vectors ? t->d_vec.p : nullptr, k};
+    auto emit = [&] {
+        hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tab.view(), tab.cap, flag.p, pos.p, a, b, ro, (uint64_t)0);
+        if (how.emit_extra) how.emit_extra(ro, n_rows);
+    };
+    if (how.timer) { LaunchTimer timer(ctx, how.timer); emit(); } else emit();
+    out = std::move(t);
+    return MDBG_OK;
+}
+
+}  // namespace mdbg
+
+using namespace mdbg;
 
 extern "C" int mdbg_kminmer_count_first(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, uint32_t min_abundance,
                                         mdbg_table **out) try {
@@ -1046,7 +877,7 @@ extern "C" int mdbg_kminmer_count_first(mdbg_ctx *ctx, const mdbg_minimizers *re
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     // instances partitioned by key and counted in LDS (partition.hip) -- by default from a few million minimizers up, where the one
     // table below no longer sits in a cache; it hands the input back when it is not for it (k > 32, more keys than its buckets hold)
-    if (ctx->first_pass_mode == 2 || (ctx->first_pass_mode == 0 && reads->n_min >= ctx->part_auto_min)) {
+    if (first_pass_partitioned(ctx, reads->n_min)) {
         bool done = false;
         MDBG_TRY(count_first_partitioned(ctx, reads, k, min_abundance, out, &done));
         if (done) return MDBG_OK;
@@ -1057,25 +888,14 @@ extern "C" int mdbg_kminmer_count_first(mdbg_ctx *ctx, const mdbg_minimizers *re
     SeqView sv = make_view(reads, ix), none{};
     DeviceTable tab;
     DevBuf<uint32_t> inst_slot, sflag;
-    MDBG_TRY(inst_slot.alloc(ctx, I));
     for (uint64_t &v : ctx->part_info) v = 0;
     ctx->part_info[0] = 1; ctx->part_info[7] = I;
-    // distinct keys are usually a small fraction of the instances (coverage): start small so the table
-    // stays cache-resident, grow and rebuild when a probe sequence gets long
-    MDBG_TRY(build_table_adaptive(ctx, tab, (uint64_t)((double)I * ctx->key_ratio_hint[0]), I, [&](TableView v) {
-        if (I) {
-            LaunchTimer timer(ctx, "kminmer_insert");
-            hipLaunchKernelGGL(count_insert_kernel, dim3(instance_grid(ctx, sv.n_reads)), dim3(256), 0, ctx->stream, sv, k, v, inst_slot.p, (uint64_t)0);
-        }
-        return MDBG_OK;
-    }, ctx->key_ratio_known[0]));
+    MDBG_TRY(count_instances(ctx, sv, k, 0, tab, inst_slot));
     TableView tv = tab.view();
 
     // solid rows
     const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
-    DevBuf<uint64_t> spos;
     MDBG_TRY(sflag.alloc(ctx, nslots));
-    MDBG_TRY(spos.alloc(ctx, nslots + 1));
     // rescue (graph/CreateMdbg.cpp:317-319: only when min_abundance <= 1) wants the count class of every slot:
     // produced by the same pass over the table that flags the solid slots
     RescuePlan plan;
@@ -1086,123 +906,26 @@ extern "C" int mdbg_kminmer_count_first(mdbg_ctx *ctx, const mdbg_minimizers *re
         hipLaunchKernelGGL(slot_flag_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, min_abundance, 0, sflag.p,
                            plan.cls.p, rescue_m_star(), tv.occ);
     }
-    MDBG_TRY(exclusive_scan_u32(ctx, sflag.p, spos.p, nslots));
-    uint64_t n_solid = 0, n_resc = 0, n_keys = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_solid, spos.p + nslots, 8, hipMemcpyDeviceToHost));
-    MDBG_TRY(tab.occupied(ctx, &n_keys));
-    update_key_hint(ctx, 0, n_keys, I);
-
-    if (do_rescue) {
-        MDBG_TRY(plan_rescue(ctx, tab, ix, reads->n_reads, inst_slot.p, plan));
+    uint64_t n_keys = 0;
+    FlaggedRows how;
+    how.timer = "kminmer_emit";
+    how.extra_rows = [&](uint64_t, uint64_t &n_resc) {
+        MDBG_TRY(tab.occupied(ctx, &n_keys));
+        update_key_hint(ctx, 0, n_keys, I);
+        if (do_rescue) MDBG_TRY(plan_rescue(ctx, tab, ix, reads->n_reads, inst_slot.p, plan));
         n_resc = plan.total;
-    }
-
-    mdbg_table *t = new mdbg_table();
-    t->k = k;
-    t->n_solid = n_solid;
+        return MDBG_OK;
+    };
+    how.emit_extra = [&](const RowOut &ro, uint64_t n_solid) { if (plan.total) launch_emit_rescued(ctx, sv, k, inst_slot.p, plan, ro, n_solid); };
+    std::unique_ptr<mdbg_table> t;
+    MDBG_TRY(rows_from_flags(ctx, tab, sflag, k, sv, none, true, how, t));
     t->st_minimizers = reads->n_min; t->st_instances = I; t->st_keys = n_keys; t->st_slots = nslots;
-    int rc = alloc_rows(ctx, t, n_solid + n_resc, true);
-    if (rc) { delete t; return rc; }
-    RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, t->d_vec.p, k};
-    {
-        LaunchTimer timer(ctx, "kminmer_emit");
-        hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, sflag.p, spos.p, sv, none, ro, (uint64_t)0);
-        if (n_resc) launch_emit_rescued(ctx, sv, k, inst_slot.p, plan, ro, n_solid);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "kminmer_count_first failed: %s", hipGetErrorString(e)); }
-    *out = t;
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-// build a lookup DeviceTable from the rows of `t` (abundance == 1 skipped as loadRefinedAbundances does)
-static int ensure_lookup(mdbg_ctx *ctx, mdbg_table *t, bool skip_one) {
-    if (t->lookup) return MDBG_OK;
-    std::unique_ptr<DeviceTable> tab(new DeviceTable());
-    MDBG_TRY(tab->init(ctx, table_slots_for(t->n_records)));
-    if (t->n_records)
-        hipLaunchKernelGGL(rows_insert_kernel, dim3(grid_for(t->n_records, 256)), dim3(256), 0, ctx->stream,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p, t->n_records, skip_one ? 1 : 0, tab->view());
-    MDBG_HIP_CHECK(ctx, hipGetLastError());
-    MDBG_TRY(tab->check_overflow(ctx));
-    t->lookup = std::move(tab);
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_prev_from_records(mdbg_ctx *ctx, const uint8_t *records20, uint64_t n_records, mdbg_table **out) try {
-    if (!ctx || !out || (n_records && !records20)) return set_error(ctx, MDBG_EINVAL, "mdbg_prev_from_records: bad argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    mdbg_table *t = new mdbg_table();
-    auto fail = [&](int rc) { delete t; return rc; };
-    int rc;
-    DevBuf<uint8_t> d_rec;
-    if ((rc = d_rec.alloc(ctx, n_records * 20)) || (rc = alloc_rows(ctx, t, n_records, false))) return fail(rc);
-    if (n_records) {
-        hipError_t e = hipMemcpyAsync(d_rec.p, records20, n_records * 20, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "record upload failed: %s", hipGetErrorString(e)));
-        hipLaunchKernelGGL(unpack_records_kernel, dim3(grid_for(n_records, 256)), dim3(256), 0, ctx->stream, d_rec.p, n_records,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p);
-    }
-    // headroom: the unitig overlay may add keys that are not in the record file
-    std::unique_ptr<DeviceTable> tab(new DeviceTable());
-    if ((rc = tab->init(ctx, table_slots_for(n_records + n_records / 4) + 4096))) return fail(rc);
-    if (n_records)
-        hipLaunchKernelGGL(rows_insert_kernel, dim3(grid_for(n_records, 256)), dim3(256), 0, ctx->stream,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p, n_records, 1, tab->view());
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(set_error(ctx, MDBG_EHIP, "prev table build failed: %s", hipGetErrorString(e)));
-    if ((rc = tab->check_overflow(ctx))) return fail(rc);
-    t->lookup = std::move(tab);
-    *out = t;
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-namespace mdbg { int bytes_ready_on(mdbg_ctx *ctx, const mdbg_bytes *b); }
-
-extern "C" int mdbg_prev_from_record_bytes(mdbg_ctx *ctx, const mdbg_bytes *records, uint64_t n_records, mdbg_table **out) try {
-    if (!ctx || !out || !records) return set_error(ctx, MDBG_EINVAL, "mdbg_prev_from_record_bytes: bad argument");
-    if (n_records * 20 != records->n) return set_error(ctx, MDBG_EINVAL, "mdbg_prev_from_record_bytes: %llu records are not the buffer's %llu bytes",
-                                                       (unsigned long long)n_records, (unsigned long long)records->n);
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<mdbg_table> t(new mdbg_table());
-    MDBG_TRY(alloc_rows(ctx, t.get(), n_records, false));
-    MDBG_TRY(bytes_ready_on(ctx, records));
-    if (n_records)
-        hipLaunchKernelGGL(unpack_records_kernel, dim3(grid_for(n_records, 256)), dim3(256), 0, ctx->stream, records->d.p, n_records,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p);
-    std::unique_ptr<DeviceTable> tab(new DeviceTable());
-    MDBG_TRY(tab->init(ctx, table_slots_for(n_records + n_records / 4) + 4096));      // headroom: the unitig overlay may add keys
-    if (n_records)
-        hipLaunchKernelGGL(rows_insert_kernel, dim3(grid_for(n_records, 256)), dim3(256), 0, ctx->stream,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p, n_records, 1, tab->view());
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    MDBG_TRY(tab->check_overflow(ctx));
-    t->lookup = std::move(tab);
     *out = t.release();
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
 
-extern "C" int mdbg_prev_overlay_unitigs(mdbg_ctx *ctx, mdbg_table *prev, const mdbg_minimizers *unitigs,
-                                         const uint32_t *abundance, uint32_t k_prev) try {
-    if (!ctx || !prev || !prev->lookup || !abundance || k_prev < 2) return set_error(ctx, MDBG_EINVAL, "mdbg_prev_overlay_unitigs: bad argument");
-    MDBG_TRY(check_seq(ctx, unitigs, "mdbg_prev_overlay_unitigs"));
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    InstIndex ix;
-    MDBG_TRY(build_inst_index(ctx, unitigs, k_prev, ix));
-    if (prev->lookup->cap < (prev->n_records + ix.total) * 3 / 2)
-        return set_error(ctx, MDBG_ERANGE, "prev table too small for the unitig overlay (%llu windows)", (unsigned long long)ix.total);
-    DevBuf<uint32_t> d_ab;
-    MDBG_TRY(d_ab.alloc(ctx, unitigs->n_reads));
-    if (unitigs->n_reads) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(d_ab.p, abundance, (size_t)unitigs->n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
-    SeqView sv = make_view(unitigs, ix);
-    if (ix.total)
-        hipLaunchKernelGGL(overlay_kernel, dim3(grid_for(ix.total, 256)), dim3(256), 0, ctx->stream, sv, k_prev, d_ab.p, prev->lookup->view());
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    prev->image.reset();                 // (made again, from the overlaid table, by the pass that reads it)
-    return prev->lookup->check_overflow(ctx);
-} MDBG_API_CATCH(ctx)
-
-static int prev_view(mdbg_ctx *ctx, const mdbg_table *prev, TableView &pv) {
+int mdbg::prev_view(mdbg_ctx *ctx, const mdbg_table *prev, TableView &pv) {
     if (!prev) return set_error(ctx, MDBG_EINVAL, "previous table is null");
     MDBG_TRY(ensure_lookup(ctx, const_cast<mdbg_table *>(prev), true));
     pv = prev->lookup->view();
@@ -1216,6 +939,17 @@ static int prev_image(mdbg_ctx *ctx, const mdbg_table *prev_c, BucketView &pv) {
     mdbg_table *prev = const_cast<mdbg_table *>(prev_c);
     if (!prev->image) {
         std::unique_ptr<BucketTable> img(new BucketTable());
+        // filled at load 0.75; a table in which a probe sequence got too long is made again at half the load, down to below 0.05
+        auto build = [&](uint64_t n_keys, auto fill) {
+            for (double load = 0.75;; load *= 0.5) {
+                MDBG_TRY(img->init(ctx, BucketTable::buckets_for(n_keys + 64, load), false));
+                fill(img->view());
+                const int o = img->overflowed(ctx);
+                if (o < 0) return o;
+                if (!o) return (int)MDBG_OK;
+                if (load < 0.05) return set_error(ctx, MDBG_ERANGE, "previous table: bucket table overflow");
+            }
+        };
         if (prev->lookup) {
             DeviceTable &src = *prev->lookup;
             const uint64_t nslots = src.cap + TABLE_EXC_CAP;
@@ -1223,28 +957,17 @@ static int prev_image(mdbg_ctx *ctx, const mdbg_table *prev_c, BucketView &pv) {
             hipLaunchKernelGGL(table_occupied_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, src.view(), src.cap, src.view().occ);
             uint64_t n_keys = 0;
             MDBG_TRY(src.occupied(ctx, &n_keys));
-            for (double load = 0.75;; load *= 0.5) {
-                MDBG_TRY(img->init(ctx, BucketTable::buckets_for(n_keys + 64, load), false));
+            MDBG_TRY(build(n_keys, [&](BucketView v) {
                 LaunchTimer timer(ctx, "kminmer_prev_image");
-                hipLaunchKernelGGL(bucket_from_table_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, src.view(), src.cap, img->view());
-                const int o = img->overflowed(ctx);
-                if (o < 0) return o;
-                if (!o) break;
-                if (load < 0.05) return set_error(ctx, MDBG_ERANGE, "previous table: bucket table overflow");
-            }
+                hipLaunchKernelGGL(bucket_from_table_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, src.view(), src.cap, v);
+            }));
         } else {
-            for (double load = 0.75;; load *= 0.5) {
-                MDBG_TRY(img->init(ctx, BucketTable::buckets_for(prev->n_records + 64, load), false));
-                if (prev->n_records) {
-                    LaunchTimer timer(ctx, "kminmer_prev_image");
-                    hipLaunchKernelGGL(bucket_rows_insert_kernel, dim3(grid_for(prev->n_records, 256)), dim3(256), 0, ctx->stream,
-                                       prev->d_lo.p, prev->d_hi.p, prev->d_ab.p, prev->n_records, 1, img->view());
-                }
-                const int o = img->overflowed(ctx);
-                if (o < 0) return o;
-                if (!o) break;
-                if (load < 0.05) return set_error(ctx, MDBG_ERANGE, "previous table: bucket table overflow");
-            }
+            MDBG_TRY(build(prev->n_records, [&](BucketView v) {
+                if (!prev->n_records) return;
+                LaunchTimer timer(ctx, "kminmer_prev_image");
+                hipLaunchKernelGGL(bucket_rows_insert_kernel, dim3(grid_for(prev->n_records, 256)), dim3(256), 0, ctx->stream,
+                                   prev->d_lo.p, prev->d_hi.p, prev->d_ab.p, prev->n_records, 1, v);
+            }));
         }
         prev->image = std::move(img);
     }
@@ -1351,35 +1074,23 @@ extern "C" int mdbg_kminmer_count_refined(mdbg_ctx *ctx, const mdbg_minimizers *
     TableView tv = tab.view();
     const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
     DevBuf<uint32_t> sflag;
-    DevBuf<uint64_t> spos;
     MDBG_TRY(sflag.alloc(ctx, nslots));
-    MDBG_TRY(spos.alloc(ctx, nslots + 1));
     {
         LaunchTimer timer(ctx, "kminmer_emit");
         if (!lazy) hipLaunchKernelGGL(refine_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, a, b, k, pv);
         hipLaunchKernelGGL(slot_flag_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, 0u, 1, sflag.p,
                            (uint8_t *)nullptr, 0u, tv.occ);
     }
-    MDBG_TRY(exclusive_scan_u32(ctx, sflag.p, spos.p, nslots));
     uint64_t n_keys = 0;
     MDBG_TRY(tab.occupied(ctx, &n_keys));
     update_key_hint(ctx, 1, n_keys, I);
-    uint64_t n_rows = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_rows, spos.p + nslots, 8, hipMemcpyDeviceToHost));
-    mdbg_table *t = new mdbg_table();
-    t->k = k;
-    t->n_solid = n_rows;
+    FlaggedRows how;
+    how.timer = "kminmer_emit";
+    std::unique_ptr<mdbg_table> t;
+    MDBG_TRY(rows_from_flags(ctx, tab, sflag, k, a, b, true, how, t));
     t->st_minimizers = a.n_min + b.n_min; t->st_instances = I; t->st_keys = n_keys; t->st_slots = nslots;
-    int rc = alloc_rows(ctx, t, n_rows, true);
-    if (rc) { delete t; return rc; }
-    RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, t->d_vec.p, k};
-    {
-        LaunchTimer timer(ctx, "kminmer_emit");
-        hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, sflag.p, spos.p, a, b, ro, (uint64_t)0);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "kminmer_count_refined failed: %s", hipGetErrorString(e)); }
-    *out = t;
+    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = t.release();
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
 
@@ -1529,756 +1240,19 @@ extern "C" int mdbg_kminmer_index(mdbg_ctx *ctx, const mdbg_minimizers *reads, c
         if (unitigs) MDBG_TRY(index_one_set(ctx, unitigs, k, pv, v, n_inst));
         return MDBG_OK;
     }));
-    TableView tv = tab.view();
-    const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
     DevBuf<uint32_t> sflag;
-    DevBuf<uint64_t> spos;
-    MDBG_TRY(sflag.alloc(ctx, nslots));
-    MDBG_TRY(spos.alloc(ctx, nslots + 1));
-    hipLaunchKernelGGL(slot_flag_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, 0u, 2, sflag.p);
-    MDBG_TRY(exclusive_scan_u32(ctx, sflag.p, spos.p, nslots));
-    uint64_t n_rows = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_rows, spos.p + nslots, 8, hipMemcpyDeviceToHost));
-    update_key_hint(ctx, 2, n_rows, bound);   // every occupied slot is a row
-    mdbg_table *t = new mdbg_table();
-    t->k = k;
-    t->n_solid = n_rows;
-    t->st_minimizers = bound; t->st_instances = n_inst; t->st_keys = n_rows; t->st_slots = nslots;
-    int rc = alloc_rows(ctx, t, n_rows, false);
-    if (rc) { delete t; return rc; }
-    RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, nullptr, k};
-    {
-        LaunchTimer timer(ctx, "kminmer_emit");
-        hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, sflag.p, spos.p, SeqView{}, SeqView{}, ro, (uint64_t)0);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "kminmer_index failed: %s", hipGetErrorString(e)); }
+    MDBG_TRY(flag_occupied_slots(ctx, tab, sflag));
+    FlaggedRows how;
+    how.timer = "kminmer_emit";
+    how.extra_rows = [&](uint64_t n_rows, uint64_t &) { update_key_hint(ctx, 2, n_rows, bound); return MDBG_OK; };   // every occupied slot is a row
+    std::unique_ptr<mdbg_table> t;
+    MDBG_TRY(rows_from_flags(ctx, tab, sflag, k, SeqView{}, SeqView{}, false, how, t));
+    t->st_minimizers = bound; t->st_instances = n_inst; t->st_keys = t->n_solid; t->st_slots = tab.cap + TABLE_EXC_CAP;
+    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     // The table the pass filled IS the key -> abundance map of its rows (every slot published, every value above 1): it stays with the
     // result as its look-up structure, so the next pass of the loop -- or mdbg_table_lookup -- does not build one from the rows again
     // (a clear of the slots and an insert per row: 1 ms of every pass at 10 M reads).  "keep_index_table" = 0: drop it (rounds 1 - 5).
     if (ctx->keep_index_table) t->lookup = std::move(tabp);
-    *out = t;
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_table_info(const mdbg_table *t, uint32_t *k, uint64_t *n_records, uint64_t *n_solid, int *has_vectors) {
-    if (!t) return MDBG_EINVAL;
-    if (k) *k = t->k;
-    if (n_records) *n_records = t->n_records;
-    if (n_solid) *n_solid = t->n_solid;
-    if (has_vectors) *has_vectors = t->has_vectors ? 1 : 0;
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_table_stats(const mdbg_table *t, uint64_t stats[4]) {
-    if (!t || !stats) return MDBG_EINVAL;
-    stats[0] = t->st_minimizers; stats[1] = t->st_instances; stats[2] = t->st_keys; stats[3] = t->st_slots;
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_first_pass_info(const mdbg_ctx *ctx, uint64_t info[8]) {
-    if (!ctx || !info) return MDBG_EINVAL;
-    for (int i = 0; i < 8; i++) info[i] = ctx->part_info[i];
-    return MDBG_OK;
-}
-
-// ---- what the runtime knows of a kernel of the step (the residency rule is checked against the loaded code object) -------------------
-static const StepKernel *step_kernel_at(uint32_t i) {
-    const StepKernel *(*const tables[])(uint32_t *) = {scan_step_kernels, minimizers_step_kernels, prims_step_kernels, partition_step_kernels, extract_step_kernels, stitch_step_kernels, mapper_step_kernels};
-    for (auto table : tables) {
-        uint32_t n = 0;
-        const StepKernel *k = table(&n);
-        if (i < n) return k + i;
-        i -= n;
-    }
-    return nullptr;
-}
-
-extern "C" const char *mdbg_step_kernel_name(uint32_t index) {
-    const StepKernel *k = step_kernel_at(index);
-    return k ? k->name : nullptr;
-}
-
-extern "C" int mdbg_kernel_attributes(mdbg_ctx *ctx, const char *kernel, uint64_t attr[8]) try {
-    if (!ctx || !kernel || !attr) return set_error(ctx, MDBG_EINVAL, "mdbg_kernel_attributes: null argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    for (uint32_t i = 0;; i++) {
-        const StepKernel *k = step_kernel_at(i);
-        if (!k) return set_error(ctx, MDBG_EINVAL, "mdbg_kernel_attributes: no kernel '%s'", kernel);
-        if (strcmp(k->name, kernel) != 0) continue;
-        hipFuncAttributes at;
-        MDBG_HIP_CHECK(ctx, hipFuncGetAttributes(&at, k->fn));
-        attr[0] = (uint64_t)at.numRegs; attr[1] = at.sharedSizeBytes; attr[2] = (uint64_t)at.maxThreadsPerBlock; attr[3] = k->threads;
-        attr[4] = k->role; attr[5] = at.localSizeBytes; attr[6] = 0; attr[7] = 0;
-        return MDBG_OK;
-    }
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_first_pass_form(const mdbg_ctx *ctx, uint64_t form[4]) {
-    if (!ctx || !form) return MDBG_EINVAL;
-    for (int i = 0; i < 4; i++) form[i] = ctx->part_form[i];
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_first_pass_slot_fall_backs(const mdbg_ctx *ctx, uint64_t *n) {
-    if (!ctx || !n) return MDBG_EINVAL;
-    *n = ctx->part_fell_back;
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_table_checksum(mdbg_ctx *ctx, const mdbg_table *t, uint64_t sums[4]) try {
-    if (!ctx || !t || !sums) return set_error(ctx, MDBG_EINVAL, "mdbg_table_checksum: null argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    DevBuf<unsigned long long> acc;
-    MDBG_TRY(acc.alloc(ctx, 4));
-    MDBG_HIP_CHECK(ctx, hipMemsetAsync(acc.p, 0, 32, ctx->stream));
-    if (t->n_records)
-        hipLaunchKernelGGL(table_checksum_kernel, dim3(grid_for(t->n_records, 256 * 8, 4096)), dim3(256), 0, ctx->stream, t->d_lo.p, t->d_hi.p,
-                           t->d_ab.p, t->has_vectors ? t->d_vec.p : nullptr, t->k, t->n_records, acc.p);
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, sums, acc.p, 32, hipMemcpyDeviceToHost));
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_table_to_host(mdbg_ctx *ctx, const mdbg_table *t, uint8_t *records20, uint32_t *vectors) try {
-    if (!ctx || !t) return set_error(ctx, MDBG_EINVAL, "mdbg_table_to_host: null argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (records20 && t->n_records) {
-        DevBuf<uint8_t> d_rec;
-        MDBG_TRY(d_rec.alloc(ctx, t->n_records * 20));
-        hipLaunchKernelGGL(pack_records_kernel, dim3(grid_for(t->n_records, 256)), dim3(256), 0, ctx->stream,
-                           t->d_lo.p, t->d_hi.p, t->d_ab.p, t->n_records, d_rec.p);
-        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(records20, d_rec.p, t->n_records * 20, hipMemcpyDeviceToHost, ctx->stream));
-        MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (vectors) {
-        if (!t->has_vectors) return set_error(ctx, MDBG_EINVAL, "mdbg_table_to_host: table has no vectors (k >= firstK+2)");
-        if (t->n_records) MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, vectors, t->d_vec.p, t->n_records * t->k * 4, hipMemcpyDeviceToHost));
-    }
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_table_to_host_range(mdbg_ctx *ctx, const mdbg_table *t, uint64_t first, uint64_t count, uint8_t *records20, uint32_t *vectors) try {
-    if (!ctx || !t) return set_error(ctx, MDBG_EINVAL, "mdbg_table_to_host_range: null argument");
-    if (first > t->n_records || count > t->n_records - first) return set_error(ctx, MDBG_EINVAL, "mdbg_table_to_host_range: rows [%llu, +%llu) of %llu",
-                                                                               (unsigned long long)first, (unsigned long long)count, (unsigned long long)t->n_records);
-    if (vectors && !t->has_vectors) return set_error(ctx, MDBG_EINVAL, "mdbg_table_to_host_range: table has no vectors (k >= firstK+2)");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (!count) return MDBG_OK;
-    DevBuf<uint8_t> d_rec;
-    if (records20) {
-        MDBG_TRY(d_rec.alloc(ctx, count * 20));
-        hipLaunchKernelGGL(pack_records_kernel, dim3(grid_for(count, 256)), dim3(256), 0, ctx->stream, t->d_lo.p + first, t->d_hi.p + first, t->d_ab.p + first,
-                           count, d_rec.p);
-        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(records20, d_rec.p, count * 20, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (vectors) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(vectors, t->d_vec.p + first * t->k, count * t->k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));      // one wait for both
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_table_lookup(mdbg_ctx *ctx, const mdbg_table *t, const uint64_t *hash_lo, const uint64_t *hash_hi,
-                                 uint64_t n, uint32_t *abundance) try {
-    if (!ctx || !t || (n && (!hash_lo || !hash_hi || !abundance))) return set_error(ctx, MDBG_EINVAL, "mdbg_table_lookup: null argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    MDBG_TRY(ensure_lookup(ctx, const_cast<mdbg_table *>(t), false));
-    if (!n) return MDBG_OK;
-    DevBuf<uint64_t> dl, dh;
-    DevBuf<uint32_t> dv;
-    MDBG_TRY(dl.alloc(ctx, n));
-    MDBG_TRY(dh.alloc(ctx, n));
-    MDBG_TRY(dv.alloc(ctx, n));
-    MDBG_HIP_CHECK(ctx, hipMemcpyAsync(dl.p, hash_lo, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    MDBG_HIP_CHECK(ctx, hipMemcpyAsync(dh.p, hash_hi, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(lookup_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, t->lookup->view(), dl.p, dh.p, n, dv.p);
-    MDBG_HIP_CHECK(ctx, hipMemcpyAsync(abundance, dv.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_small_contigs(mdbg_ctx *ctx, const mdbg_minimizers *unitigs, uint32_t k, uint32_t k_prev, const mdbg_table *prev,
-                                  uint8_t *flags) try {
-    if (!ctx || !unitigs || k_prev < 1 || k <= k_prev) return set_error(ctx, MDBG_EINVAL, "mdbg_small_contigs: bad argument");
-    MDBG_TRY(check_seq(ctx, unitigs, "mdbg_small_contigs"));
-    if (unitigs->n_reads && !flags) return set_error(ctx, MDBG_EINVAL, "mdbg_small_contigs: flags is null");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    TableView pv;
-    MDBG_TRY(prev_view(ctx, prev, pv));
-    if (!unitigs->n_reads) return MDBG_OK;
-    DevBuf<uint8_t> d_flags;
-    MDBG_TRY(d_flags.alloc(ctx, unitigs->n_reads));
-    hipLaunchKernelGGL(small_contig_kernel, dim3(grid_for(unitigs->n_reads, 256)), dim3(256), 0, ctx->stream, unitigs->d_off.p,
-                       unitigs->n_reads, unitigs->d_min.p, k, k_prev, pv, d_flags.p);
-    MDBG_HIP_CHECK(ctx, hipMemcpyAsync(flags, d_flags.p, unitigs->n_reads, hipMemcpyDeviceToHost, ctx->stream));
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-// every occupied slot of `tab` becomes a key-only row of a new table of (k-1)-identities
-static int edges_from_table(mdbg_ctx *ctx, DeviceTable &tab, uint32_t k_edge, mdbg_table **edges, uint64_t *checksum, const char *who) {
-    TableView tv = tab.view();
-    const uint64_t nslots = tab.cap + TABLE_EXC_CAP;
-    DevBuf<uint32_t> sflag;
-    DevBuf<uint64_t> spos;
-    MDBG_TRY(sflag.alloc(ctx, nslots));
-    MDBG_TRY(spos.alloc(ctx, nslots + 1));
-    hipLaunchKernelGGL(slot_flag_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, 0u, 2, sflag.p);
-    MDBG_TRY(exclusive_scan_u32(ctx, sflag.p, spos.p, nslots));
-    uint64_t n_rows = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_rows, spos.p + nslots, 8, hipMemcpyDeviceToHost));
-    mdbg_table *t = new mdbg_table();
-    t->k = k_edge;
-    t->n_solid = n_rows;
-    int rc = alloc_rows(ctx, t, n_rows, false);
-    if (rc) { delete t; return rc; }
-    RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, nullptr, t->k};
-    hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, tv, tab.cap, sflag.p, spos.p, SeqView{}, SeqView{}, ro, (uint64_t)0);
-    if (checksum) {
-        DevBuf<unsigned long long> acc;
-        rc = acc.alloc(ctx, 1);
-        if (rc) { delete t; return rc; }
-        (void)hipMemsetAsync(acc.p, 0, 8, ctx->stream);
-        if (n_rows) hipLaunchKernelGGL(sum_u64_kernel, dim3(grid_for(n_rows, 256)), dim3(256), 0, ctx->stream, t->d_lo.p, n_rows, acc.p);
-        hipError_t e = memcpy_sync(ctx, checksum, acc.p, 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "edge checksum copy failed: %s", hipGetErrorString(e)); }
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "%s failed: %s", who, hipGetErrorString(e)); }
-    *edges = t;
-    return MDBG_OK;
-}
-
-extern "C" int mdbg_edge_index(mdbg_ctx *ctx, const mdbg_table *nodes, mdbg_table **edges, uint64_t *checksum) try {
-    if (!ctx || !nodes || !edges) return set_error(ctx, MDBG_EINVAL, "mdbg_edge_index: null argument");
-    if (!nodes->has_vectors || nodes->k < 3) return set_error(ctx, MDBG_EINVAL, "mdbg_edge_index: needs a table with vectors (k <= firstK+1)");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint64_t n = nodes->n_records;
-    DeviceTable tab;
-    MDBG_TRY(build_table_adaptive(ctx, tab, n, 2 * n, [&](TableView v) {
-        if (n) {
-            LaunchTimer timer(ctx, "edge_index");
-            hipLaunchKernelGGL(edge_insert_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, nodes->d_vec.p, n, nodes->k, v);
-        }
-        return MDBG_OK;
-    }));
-    return edges_from_table(ctx, tab, nodes->k - 1, edges, checksum, "mdbg_edge_index");
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_unitig_edge_index(mdbg_ctx *ctx, const mdbg_minimizers *unitigs, uint32_t k, mdbg_table **edges, uint64_t *checksum) try {
-    if (!ctx || !edges || k < 3) return set_error(ctx, MDBG_EINVAL, "mdbg_unitig_edge_index: bad argument");
-    MDBG_TRY(check_seq(ctx, unitigs, "mdbg_unitig_edge_index"));
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint64_t n = unitigs->n_reads;
-    DeviceTable tab;
-    MDBG_TRY(build_table_adaptive(ctx, tab, 2 * n, 4 * n, [&](TableView v) {
-        if (n) {
-            LaunchTimer timer(ctx, "edge_index");
-            hipLaunchKernelGGL(unitig_edge_insert_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, unitigs->d_off.p, (uint32_t)n,
-                               unitigs->d_min.p, k, v);
-        }
-        return MDBG_OK;
-    }));
-    return edges_from_table(ctx, tab, k - 1, edges, checksum, "mdbg_unitig_edge_index");
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_table_keys_to_host(mdbg_ctx *ctx, const mdbg_table *t, uint64_t *keys_lo_hi) try {
-    if (!ctx || !t || (t->n_records && !keys_lo_hi)) return set_error(ctx, MDBG_EINVAL, "mdbg_table_keys_to_host: null argument");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (!t->n_records) return MDBG_OK;
-    DevBuf<uint64_t> tmp;
-    MDBG_TRY(tmp.alloc(ctx, t->n_records * 2));
-    hipLaunchKernelGGL(interleave_keys_kernel, dim3(grid_for(t->n_records, 256)), dim3(256), 0, ctx->stream, t->d_lo.p, t->d_hi.p, t->n_records, tmp.p);
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, keys_lo_hi, tmp.p, t->n_records * 16, hipMemcpyDeviceToHost));
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" void mdbg_table_free(mdbg_table *t) { delete t; }
-
-
-// =====================================================================================================
-// Sharded first pass (reads split over several GPUs, one process each).  See include/mdbg_hip.h.
-// =====================================================================================================
-namespace mdbg {
-
-constexpr uint32_t SHARD_ROW_WORDS = 3;                 // [hash_lo, hash_hi, count]
-constexpr uint64_t SHARD_EMIT_BIT = 1ull << 63;         // in a reply: "you list this key in your table"
-
-__device__ __forceinline__ uint32_t owner_of(uint64_t hi, uint32_t n_ranks) {
-    return (uint32_t)(((hi >> 32) * (uint64_t)n_ranks) >> 32);
-}
-
-__device__ __forceinline__ bool slot_read(const TableView &t, uint64_t cap, uint64_t s, uint64_t &lo, uint64_t &hi, uint32_t &v) {
-    if (s < cap) {
-        const uint4 *q = reinterpret_cast<const uint4 *>(t.slots + s);
-        const uint4 key = q[0];
-        lo = (uint64_t)key.x | ((uint64_t)key.y << 32);
-        if (lo == 0ull) return false;
-        hi = (uint64_t)key.z | ((uint64_t)key.w << 32);
-        v = q[1].x;
-        return true;
-    }
-    uint32_t i = (uint32_t)(s - cap);
-    if (i >= *t.exc_n) return false;
-    lo = t.exc_lo[i]; hi = t.exc_hi[i]; v = t.exc_val[i];
-    return true;
-}
-
-// Rows are grouped by owner without a single global atomic (same-address device-scope atomics cost
-// ~0.2 us each on this part, serialised): pass 1 writes one LDS histogram per block of SHARD_SPB slots
-// to block_hist[owner][block]; an exclusive scan over that owner-major array gives every (owner, block)
-// its first row; pass 2 hands out the places inside the block's range through LDS.
-constexpr uint32_t SHARD_SPB = 2048;   // slots per block
-
-__global__ __launch_bounds__(256) void owner_hist_kernel(TableView t, uint64_t cap, uint32_t n_ranks, uint32_t *block_hist) {
-    __shared__ uint32_t h[64];
-    if (threadIdx.x < 64) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t s0 = (uint64_t)blockIdx.x * SHARD_SPB;
-    for (uint32_t j = threadIdx.x; j < SHARD_SPB; j += 256) {
-        uint64_t lo, hi; uint32_t v;
-        if (s0 + j < cap + TABLE_EXC_CAP && slot_read(t, cap, s0 + j, lo, hi, v)) atomicAdd(&h[owner_of(hi, n_ranks)], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < n_ranks) block_hist[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-// write every occupied slot as a row [lo, hi, count] into its owner's range and remember its slot
-__global__ __launch_bounds__(256) void owner_scatter_kernel(TableView t, uint64_t cap, uint32_t n_ranks, const uint64_t *block_base,
-                                                            uint64_t *rows, uint32_t *row_slot) {
-    __shared__ uint32_t h[64];
-    if (threadIdx.x < 64) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t s0 = (uint64_t)blockIdx.x * SHARD_SPB;
-    for (uint32_t j = threadIdx.x; j < SHARD_SPB; j += 256) {
-        const uint64_t s = s0 + j;
-        uint64_t lo, hi; uint32_t v;
-        if (!(s < cap + TABLE_EXC_CAP && slot_read(t, cap, s, lo, hi, v))) continue;
-        const uint32_t own = owner_of(hi, n_ranks);
-        const uint64_t row = block_base[(uint64_t)own * gridDim.x + blockIdx.x] + atomicAdd(&h[own], 1u);
-        uint64_t *o = rows + row * SHARD_ROW_WORDS;
-        o[0] = lo; o[1] = hi; o[2] = v;
-        row_slot[row] = s < cap ? (uint32_t)s : (0x80000000u | (uint32_t)(s - cap));
-    }
-}
-
-// The owner's table keys a row by (fmix64(hash_lo), hash_hi), not by the identity itself.  A slot's home is the TOP bits of
-// lo ^ (hi >> 17) (table_home), of which the first 17 are hash_lo's alone; and this table is what takes the rows over when a bucket
-// of part_owner_reduce outgrew its LDS table -- which is when more keys share the top bits of hash_lo than a table has slots.  With
-// the identity as the key those very keys shared a handful of home slots here as well, and the hand-over ended in "hash table
-// overflow" at any capacity.  fmix64 is a bijection that keeps 0 at 0: distinct keys stay distinct, a zero word stays a zero word
-// (the side list), and the table belongs to this call alone (mdbg_shard_reduce drops it once the replies are written).
-__device__ __forceinline__ uint64_t owner_key_lo(uint64_t lo) { return fmix64(lo); }
-
-// owner: sum the received rows by key; rep = index of the received row that created the key -- its sender is the
-// one rank that will list the key
-__global__ __launch_bounds__(256) void rows_add_kernel(const uint64_t *rows, uint64_t n, TableView t) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t *r = rows + i * SHARD_ROW_WORDS;
-    table_upsert_count(t, owner_key_lo(r[0]), r[1], (uint32_t)r[2], (uint32_t)i);
-}
-
-__global__ __launch_bounds__(256) void rows_reply_kernel(const uint64_t *rows, uint64_t n, TableView t, uint64_t *reply) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t *r = rows + i * SHARD_ROW_WORDS;
-    const uint32_t slot = table_lookup_slot(t, owner_key_lo(r[0]), r[1]);
-    uint64_t out = 0;
-    if (slot != SLOT_NONE) out = (uint64_t)table_slot_val(t, slot) | (table_slot_rep(t, slot) == (uint32_t)i ? SHARD_EMIT_BIT : 0ull);
-    reply[i] = out;
-}
-
-// global counts back into the local table (the slot of every sent row was remembered); the rows this rank
-// was told to list and that are solid get their flag
-__global__ __launch_bounds__(256) void apply_global_counts_kernel(const uint64_t *reply, const uint32_t *row_slot, uint64_t n, TableView t,
-                                                                  uint64_t cap, uint32_t min_abundance, uint32_t *flag) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = row_slot[i], v = (uint32_t)reply[i];
-    const bool emit = (reply[i] & SHARD_EMIT_BIT) != 0ull && v > 1u && !(v < min_abundance);
-    if (s & 0x80000000u) { t.exc_val[s & 0x7FFFFFFFu] = v; flag[cap + (s & 0x7FFFFFFFu)] = emit ? 1u : 0u; }
-    else { t.slots[s].val = v; flag[s] = emit ? 1u : 0u; }
-}
-
-// ---- the same grouping by owner for the rows of a finished local table (sharded k > firstK) ----
-constexpr uint32_t SHARD_RPB = 2048;   // rows per block
-
-__global__ __launch_bounds__(256) void table_owner_hist_kernel(const uint64_t *hi, uint64_t n, uint32_t n_ranks, uint32_t *block_hist) {
-    __shared__ uint32_t h[64];
-    if (threadIdx.x < 64) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t r0 = (uint64_t)blockIdx.x * SHARD_RPB;
-    for (uint32_t j = threadIdx.x; j < SHARD_RPB; j += 256)
-        if (r0 + j < n) atomicAdd(&h[owner_of(hi[r0 + j], n_ranks)], 1u);
-    __syncthreads();
-    if (threadIdx.x < n_ranks) block_hist[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void table_owner_scatter_kernel(const uint64_t *lo, const uint64_t *hi, const uint32_t *ab, uint64_t n,
-                                                                  uint32_t n_ranks, const uint64_t *block_base, uint64_t *rows, uint32_t *row_index) {
-    __shared__ uint32_t h[64];
-    if (threadIdx.x < 64) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t r0 = (uint64_t)blockIdx.x * SHARD_RPB;
-    for (uint32_t j = threadIdx.x; j < SHARD_RPB; j += 256) {
-        const uint64_t i = r0 + j;
-        if (i >= n) continue;
-        const uint32_t own = owner_of(hi[i], n_ranks);
-        const uint64_t row = block_base[(uint64_t)own * gridDim.x + blockIdx.x] + atomicAdd(&h[own], 1u);
-        uint64_t *o = rows + row * SHARD_ROW_WORDS;
-        o[0] = lo[i]; o[1] = hi[i]; o[2] = ab[i];
-        row_index[row] = (uint32_t)i;
-    }
-}
-
-// the sharded first pass on the partitioned machinery: reply i belongs to local key row_index[i]
-__global__ void replies_to_keys_kernel(const uint64_t *reply, const uint32_t *row_index, uint64_t n, uint32_t min_abundance, uint32_t *gcount, uint32_t *listed) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t v = (uint32_t)reply[i], key = row_index[i];
-    gcount[key] = v;
-    listed[key] = ((reply[i] & SHARD_EMIT_BIT) != 0ull && v > 1u && !(v < min_abundance)) ? 1u : 0u;
-}
-
-__global__ void keep_flag_kernel(const uint64_t *reply, const uint32_t *row_index, uint64_t n, uint32_t *flag) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flag[row_index[i]] = (reply[i] & SHARD_EMIT_BIT) ? 1u : 0u;
-}
-
-__global__ void keep_rows_kernel(const uint32_t *flag, const uint64_t *pos, uint64_t n, uint32_t k, const uint64_t *lo, const uint64_t *hi,
-                                 const uint32_t *ab, const uint32_t *vec, uint64_t *olo, uint64_t *ohi, uint32_t *oab, uint32_t *ovec) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const uint64_t d = pos[i];
-    olo[d] = lo[i]; ohi[d] = hi[i]; oab[d] = ab[i];
-    if (vec) for (uint32_t j = 0; j < k; j++) ovec[d * k + j] = vec[i * k + j];
-}
-
-}  // namespace mdbg
-
-struct mdbg_shard {
-    uint32_t k = 0, n_ranks = 1;
-    const mdbg_minimizers *reads = nullptr;
-    const mdbg_table *table = nullptr;       // mdbg_shard_from_table: the local table whose rows are being deduplicated
-    mdbg::DevBuf<uint32_t> row_index;        // ... and the table row every sent row came from
-    mdbg::InstIndex ix;
-    mdbg::DeviceTable local, owner;
-    mdbg::DevBuf<uint32_t> inst_slot, row_slot;
-    mdbg::DevBuf<uint64_t> rows, reply;
-    mdbg::DevBuf<uint64_t> local_replies;    // mdbg_shard_exchange_local: the replies to this shard's rows
-    uint64_t n_rows = 0;
-    bool reduced = false;
-    // the rank's share counted by the partitioned pass (csrc/partition.hip) instead of a local table: its distinct keys are the rows
-    mdbg::PartLocal *part = nullptr;
-    ~mdbg_shard() { if (part) mdbg::part_local_free(part); }
-};
-
-extern "C" uint32_t mdbg_row_words(uint32_t) { return mdbg::SHARD_ROW_WORDS; }
-
-extern "C" int mdbg_shard_begin(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, uint32_t n_ranks,
-                                mdbg_shard **out, const uint64_t **d_rows, uint64_t *counts) try {
-    if (!ctx || !reads || !out || !d_rows || !counts || k < 2 || n_ranks < 1 || n_ranks > 64)
-        return set_error(ctx, MDBG_EINVAL, "mdbg_shard_begin: bad argument");
-    MDBG_TRY(check_seq(ctx, reads, "mdbg_shard_begin"));
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<mdbg_shard> sh(new mdbg_shard());
-    sh->k = k; sh->n_ranks = n_ranks; sh->reads = reads;
-    // the rank's share through the partitioned pass (as mdbg_kminmer_count_first chooses): its distinct keys with their local counts come out
-    // bucket after bucket and are grouped by owner like the rows of a finished table (mdbg_shard_from_table)
-    if (ctx->first_pass_mode == 2 || (ctx->first_pass_mode == 0 && reads->n_min >= ctx->part_auto_min)) {
-        bool done = false;
-        MDBG_TRY(part_local_keys(ctx, reads, k, &sh->part, &done));
-        if (done) {
-            const uint64_t *klo, *khi; const uint32_t *kcnt; uint64_t n = 0, n_inst = 0;
-            part_local_arrays(sh->part, &klo, &khi, &kcnt, &n, &n_inst);
-            if (n >= (1ull << 32)) return set_error(ctx, MDBG_ERANGE, "more than 2^32 distinct local keys");
-            const unsigned nb = grid_for(n, SHARD_RPB);
-            const uint64_t nh = (uint64_t)nb * n_ranks;
-            DevBuf<uint32_t> block_hist;
-            DevBuf<uint64_t> block_base;
-            MDBG_TRY(block_hist.alloc(ctx, nh));
-            MDBG_TRY(block_base.alloc(ctx, nh + 1));
-            {
-                LaunchTimer timer(ctx, "shard_rows");
-                hipLaunchKernelGGL(table_owner_hist_kernel, dim3(nb), dim3(256), 0, ctx->stream, khi, n, n_ranks, block_hist.p);
-            }
-            MDBG_TRY(exclusive_scan_u32(ctx, block_hist.p, block_base.p, nh));
-            std::vector<uint64_t> base(nh + 1);
-            MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, base.data(), block_base.p, (nh + 1) * 8, hipMemcpyDeviceToHost));
-            for (uint32_t r = 0; r < n_ranks; r++) counts[r] = base[(uint64_t)(r + 1) * nb] - base[(uint64_t)r * nb];
-            update_key_hint(ctx, 3, n, n_inst);
-            MDBG_TRY(sh->rows.alloc(ctx, n * SHARD_ROW_WORDS));
-            MDBG_TRY(sh->row_index.alloc(ctx, n));
-            sh->n_rows = n;
-            {
-                LaunchTimer timer(ctx, "shard_rows");
-                hipLaunchKernelGGL(table_owner_scatter_kernel, dim3(nb), dim3(256), 0, ctx->stream, klo, khi, kcnt, n, n_ranks, block_base.p, sh->rows.p, sh->row_index.p);
-            }
-            MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            MDBG_DBG(ctx, "shard_begin (partitioned): %llu rows", (unsigned long long)n);
-            *d_rows = sh->rows.p;
-            *out = sh.release();
-            return MDBG_OK;
-        }
-    }
-    MDBG_TRY(build_inst_index(ctx, reads, k, sh->ix));
-    const uint64_t I = sh->ix.total;
-    MDBG_DBG(ctx, "shard_begin: %llu instances", (unsigned long long)I);
-    SeqView sv = make_view(reads, sh->ix);
-    MDBG_TRY(sh->inst_slot.alloc(ctx, I));
-    MDBG_TRY(build_table_adaptive(ctx, sh->local, (uint64_t)((double)I * ctx->key_ratio_hint[3]), I, [&](TableView v) {
-        if (I) {
-            LaunchTimer timer(ctx, "kminmer_insert");
-            hipLaunchKernelGGL(count_insert_kernel, dim3(instance_grid(ctx, sv.n_reads)), dim3(256), 0, ctx->stream, sv, k, v, sh->inst_slot.p, (uint64_t)0);
-        }
-        return MDBG_OK;
-    }, ctx->key_ratio_known[3]));
-    TableView tv = sh->local.view();
-    const uint64_t nslots = sh->local.cap + TABLE_EXC_CAP;
-    const unsigned nb = grid_for(nslots, SHARD_SPB);
-    const uint64_t nh = (uint64_t)nb * n_ranks;
-    DevBuf<uint32_t> block_hist;
-    DevBuf<uint64_t> block_base;
-    MDBG_TRY(block_hist.alloc(ctx, nh));
-    MDBG_TRY(block_base.alloc(ctx, nh + 1));
-    {
-        LaunchTimer timer(ctx, "shard_rows");
-        hipLaunchKernelGGL(owner_hist_kernel, dim3(nb), dim3(256), 0, ctx->stream, tv, sh->local.cap, n_ranks, block_hist.p);
-    }
-    MDBG_TRY(exclusive_scan_u32(ctx, block_hist.p, block_base.p, nh));
-    std::vector<uint64_t> base(nh + 1);
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, base.data(), block_base.p, (nh + 1) * 8, hipMemcpyDeviceToHost));
-    for (uint32_t r = 0; r < n_ranks; r++) counts[r] = base[(uint64_t)(r + 1) * nb] - base[(uint64_t)r * nb];
-    const uint64_t total = base[nh];
-    if (total >= (1ull << 32)) return set_error(ctx, MDBG_ERANGE, "more than 2^32 distinct local keys");
-    update_key_hint(ctx, 3, total, I);        // one row per distinct local key
-    MDBG_TRY(sh->rows.alloc(ctx, total * SHARD_ROW_WORDS));
-    MDBG_TRY(sh->row_slot.alloc(ctx, total));
-    sh->n_rows = total;
-    {
-        LaunchTimer timer(ctx, "shard_rows");
-        hipLaunchKernelGGL(owner_scatter_kernel, dim3(nb), dim3(256), 0, ctx->stream, tv, sh->local.cap, n_ranks, block_base.p,
-                           sh->rows.p, sh->row_slot.p);
-    }
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    MDBG_DBG(ctx, "shard_begin: %llu rows", (unsigned long long)total);
-    *d_rows = sh->rows.p;
-    *out = sh.release();
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-__global__ void rows_zero_word_kernel(const uint64_t *rows, uint64_t n, unsigned long long *out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (rows[i * SHARD_ROW_WORDS] == 0ull || rows[i * SHARD_ROW_WORDS + 1] == 0ull)) atomicAdd(out, 1ull);
-}
-
-extern "C" int mdbg_shard_reduce(mdbg_ctx *ctx, mdbg_shard *sh, const uint64_t *d_recv, uint64_t n_recv, const uint64_t **d_reply) try {
-    if (!ctx || !sh || !d_reply || (n_recv && !d_recv)) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_reduce: bad argument");
-    if (n_recv >= (1ull << 32)) return set_error(ctx, MDBG_ERANGE, "more than 2^32 received rows");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    // every key this rank owns arrives once from each rank that saw it: about n_recv / n_ranks distinct keys.  Sized for
-    // that (+50 %), the table is n_ranks times smaller than one sized for the rows; it grows and refills if that was short.
-    const uint64_t expected = n_recv / sh->n_ranks + n_recv / (2 * sh->n_ranks) + 1024;
-    MDBG_DBG(ctx, "shard_reduce: %llu rows", (unsigned long long)n_recv);
-    if (debug_on() && n_recv) {
-        DevBuf<unsigned long long> z;
-        MDBG_TRY(z.alloc(ctx, 1));
-        (void)hipMemsetAsync(z.p, 0, 8, ctx->stream);
-        hipLaunchKernelGGL(rows_zero_word_kernel, dim3(grid_for(n_recv, 256)), dim3(256), 0, ctx->stream, d_recv, n_recv, z.p);
-        unsigned long long hz = 0;
-        MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &hz, z.p, 8, hipMemcpyDeviceToHost));
-        MDBG_DBG(ctx, "shard_reduce: %llu rows with a zero key word", hz);
-    }
-    if (ctx->first_pass_mode != 1) {          // the rows bucketed by key, every bucket summed in LDS (csrc/partition.hip)
-        bool done = false;
-        MDBG_TRY(sh->reply.alloc(ctx, n_recv));
-        MDBG_TRY(part_owner_reduce(ctx, d_recv, n_recv, sh->reply.p, &done));
-        if (done) {
-            sh->reduced = true;
-            *d_reply = sh->reply.p;
-            return MDBG_OK;
-        }
-    }
-    MDBG_TRY(build_table_adaptive(ctx, sh->owner, expected < n_recv ? expected : n_recv, n_recv, [&](TableView v) {
-        if (n_recv) {
-            LaunchTimer timer(ctx, "shard_reduce");
-            hipLaunchKernelGGL(rows_add_kernel, dim3(grid_for(n_recv, 256)), dim3(256), 0, ctx->stream, d_recv, n_recv, v);
-        }
-        return MDBG_OK;
-    }));
-    TableView tv = sh->owner.view();
-    MDBG_TRY(sh->reply.alloc(ctx, n_recv));
-    if (n_recv) {
-        LaunchTimer timer(ctx, "shard_reduce");
-        hipLaunchKernelGGL(rows_reply_kernel, dim3(grid_for(n_recv, 256)), dim3(256), 0, ctx->stream, d_recv, n_recv, tv, sh->reply.p);
-    }
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    MDBG_TRY(sh->owner.check_overflow(ctx));
-    sh->owner = DeviceTable();      // only the replies are needed from here on
-    sh->reduced = true;
-    *d_reply = sh->reply.p;
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_shard_finish(mdbg_ctx *ctx, mdbg_shard *sh, const uint64_t *d_replies, uint32_t min_abundance, mdbg_table **out) try {
-    if (!ctx || !sh || !out || (sh->n_rows && !d_replies)) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_finish: bad argument");
-    if (!sh->reduced) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_finish: mdbg_shard_reduce has not run");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (sh->part) {
-        // the replies, row by row, back to the order of the local keys: global count, and whether this rank lists the key
-        DevBuf<uint32_t> gcount, listed;
-        MDBG_TRY(gcount.alloc(ctx, sh->n_rows));
-        MDBG_TRY(listed.alloc(ctx, sh->n_rows));
-        if (sh->n_rows)
-            hipLaunchKernelGGL(replies_to_keys_kernel, dim3(grid_for(sh->n_rows, 256)), dim3(256), 0, ctx->stream, d_replies, sh->row_index.p, sh->n_rows, min_abundance,
-                               gcount.p, listed.p);
-        return part_local_finish(ctx, sh->part, gcount.p, listed.p, min_abundance, out);
-    }
-    const uint32_t k = sh->k;
-    const uint64_t I = sh->ix.total;
-    TableView lv = sh->local.view();
-    const uint64_t nslots = sh->local.cap + TABLE_EXC_CAP;
-    DevBuf<uint32_t> sflag;
-    DevBuf<uint64_t> spos;
-    MDBG_TRY(sflag.alloc(ctx, nslots));
-    MDBG_TRY(spos.alloc(ctx, nslots + 1));
-    MDBG_HIP_CHECK(ctx, hipMemsetAsync(sflag.p, 0, nslots * 4, ctx->stream));
-    if (sh->n_rows)
-        hipLaunchKernelGGL(apply_global_counts_kernel, dim3(grid_for(sh->n_rows, 256)), dim3(256), 0, ctx->stream, d_replies, sh->row_slot.p,
-                           sh->n_rows, lv, sh->local.cap, min_abundance, sflag.p);
-    MDBG_TRY(exclusive_scan_u32(ctx, sflag.p, spos.p, nslots));
-    uint64_t n_solid = 0, n_resc = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &n_solid, spos.p + nslots, 8, hipMemcpyDeviceToHost));
-    // rescue over the local reads against the global counts now sitting in the local table
-    SeqView sv = make_view(sh->reads, sh->ix), none{};
-    RescuePlan plan;
-    if (min_abundance <= 1 && I) {
-        MDBG_TRY(plan_rescue(ctx, sh->local, sh->ix, sv.n_reads, sh->inst_slot.p, plan));
-        n_resc = plan.total;
-    }
-    mdbg_table *t = new mdbg_table();
-    t->k = k;
-    t->n_solid = n_solid;
-    t->st_minimizers = sv.n_min; t->st_instances = I; t->st_keys = sh->n_rows; t->st_slots = nslots;
-    int rc = alloc_rows(ctx, t, n_solid + n_resc, true);
-    if (rc) { delete t; return rc; }
-    RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, t->d_vec.p, k};
-    {
-        LaunchTimer timer(ctx, "kminmer_emit");
-        hipLaunchKernelGGL(emit_slots_kernel, dim3(grid_for(nslots, 256)), dim3(256), 0, ctx->stream, lv, sh->local.cap, sflag.p, spos.p, sv, none, ro, (uint64_t)0);
-        if (n_resc) launch_emit_rescued(ctx, sv, k, sh->inst_slot.p, plan, ro, n_solid);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { delete t; return set_error(ctx, MDBG_EHIP, "mdbg_shard_finish failed: %s", hipGetErrorString(e)); }
-    *out = t;
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-// ---- sharded k > firstK -------------------------------------------------------------------------------------------
-extern "C" int mdbg_shard_from_table(mdbg_ctx *ctx, const mdbg_table *local, uint32_t n_ranks, mdbg_shard **out, const uint64_t **d_rows,
-                                     uint64_t *counts) try {
-    if (!ctx || !local || !out || !d_rows || !counts || n_ranks < 1 || n_ranks > 64)
-        return set_error(ctx, MDBG_EINVAL, "mdbg_shard_from_table: bad argument");
-    if (local->n_records >= (1ull << 32)) return set_error(ctx, MDBG_ERANGE, "mdbg_shard_from_table: more than 2^32 rows");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<mdbg_shard> sh(new mdbg_shard());
-    sh->k = local->k; sh->n_ranks = n_ranks; sh->table = local;
-    const uint64_t n = local->n_records;
-    const unsigned nb = grid_for(n, SHARD_RPB);
-    const uint64_t nh = (uint64_t)nb * n_ranks;
-    DevBuf<uint32_t> block_hist;
-    DevBuf<uint64_t> block_base;
-    MDBG_TRY(block_hist.alloc(ctx, nh));
-    MDBG_TRY(block_base.alloc(ctx, nh + 1));
-    {
-        LaunchTimer timer(ctx, "shard_rows");
-        hipLaunchKernelGGL(table_owner_hist_kernel, dim3(nb), dim3(256), 0, ctx->stream, local->d_hi.p, n, n_ranks, block_hist.p);
-    }
-    MDBG_TRY(exclusive_scan_u32(ctx, block_hist.p, block_base.p, nh));
-    std::vector<uint64_t> base(nh + 1);
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, base.data(), block_base.p, (nh + 1) * 8, hipMemcpyDeviceToHost));
-    for (uint32_t r = 0; r < n_ranks; r++) counts[r] = base[(uint64_t)(r + 1) * nb] - base[(uint64_t)r * nb];
-    MDBG_TRY(sh->rows.alloc(ctx, n * SHARD_ROW_WORDS));
-    MDBG_TRY(sh->row_index.alloc(ctx, n));
-    sh->n_rows = n;
-    {
-        LaunchTimer timer(ctx, "shard_rows");
-        hipLaunchKernelGGL(table_owner_scatter_kernel, dim3(nb), dim3(256), 0, ctx->stream, local->d_lo.p, local->d_hi.p, local->d_ab.p, n, n_ranks,
-                           block_base.p, sh->rows.p, sh->row_index.p);
-    }
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *d_rows = sh->rows.p;
-    *out = sh.release();
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" int mdbg_shard_keep(mdbg_ctx *ctx, mdbg_shard *sh, const uint64_t *d_replies, mdbg_table **out) try {
-    if (!ctx || !sh || !out || !sh->table || (sh->n_rows && !d_replies)) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_keep: bad argument");
-    if (!sh->reduced) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_keep: mdbg_shard_reduce has not run");
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const mdbg_table *src = sh->table;
-    const uint64_t n = sh->n_rows;
-    DevBuf<uint32_t> flag;
-    DevBuf<uint64_t> pos;
-    MDBG_TRY(flag.alloc(ctx, n));
-    MDBG_TRY(pos.alloc(ctx, n + 1));
-    if (n) hipLaunchKernelGGL(keep_flag_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, d_replies, sh->row_index.p, n, flag.p);
-    MDBG_TRY(exclusive_scan_u32(ctx, flag.p, pos.p, n));
-    uint64_t kept = 0;
-    MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &kept, pos.p + n, 8, hipMemcpyDeviceToHost));
-    std::unique_ptr<mdbg_table> t(new mdbg_table());
-    t->k = src->k;
-    MDBG_TRY(alloc_rows(ctx, t.get(), kept, src->has_vectors));
-    t->n_solid = kept;
-    if (n) hipLaunchKernelGGL(keep_rows_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, flag.p, pos.p, n, src->k, src->d_lo.p, src->d_hi.p,
-                              src->d_ab.p, src->has_vectors ? src->d_vec.p : nullptr, t->d_lo.p, t->d_hi.p, t->d_ab.p,
-                              src->has_vectors ? t->d_vec.p : nullptr);
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     *out = t.release();
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
-
-// Both all-to-alls of a sharded pass among shards that live on ONE device (a job checking itself, tests): device-to-device copies
-// stand in for the wire, everything else -- mdbg_shard_reduce on every owner, the replies back in the order the rows were sent --
-// is what mdbg_shard_exchange does between GPUs.
-extern "C" int mdbg_shard_exchange_local(mdbg_ctx *ctx, mdbg_shard *const *shards, uint32_t n, const uint64_t *const *d_rows, const uint64_t *counts,
-                                         const uint64_t **d_replies) try {
-    if (!ctx || !shards || !d_rows || !counts || !d_replies || n < 1 || n > 64) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_exchange_local: bad argument");
-    for (uint32_t r = 0; r < n; r++)
-        if (!shards[r] || shards[r]->n_ranks != n) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_exchange_local: shard %u was not begun for %u ranks", r, n);
-    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint32_t rw = SHARD_ROW_WORDS;
-    // soff[src][dst]: first row of src's rows for dst; roff[dst][src]: first received row on dst that came from src
-    std::vector<uint64_t> soff((size_t)n * (n + 1), 0), roff((size_t)n * (n + 1), 0);
-    for (uint32_t a = 0; a < n; a++)
-        for (uint32_t b = 0; b < n; b++) {
-            soff[(size_t)a * (n + 1) + b + 1] = soff[(size_t)a * (n + 1) + b] + counts[(size_t)a * n + b];
-            roff[(size_t)a * (n + 1) + b + 1] = roff[(size_t)a * (n + 1) + b] + counts[(size_t)b * n + a];
-        }
-    std::vector<const uint64_t *> reply(n, nullptr);
-    for (uint32_t dst = 0; dst < n; dst++) {
-        const uint64_t n_recv = roff[(size_t)dst * (n + 1) + n];
-        DevBuf<uint64_t> recv;
-        MDBG_TRY(recv.alloc(ctx, n_recv * rw));
-        for (uint32_t src = 0; src < n; src++) {
-            const uint64_t c = counts[(size_t)src * n + dst];
-            if (!c) continue;
-            if (!d_rows[src]) return set_error(ctx, MDBG_EINVAL, "mdbg_shard_exchange_local: shard %u has rows but no row pointer", src);
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(recv.p + roff[(size_t)dst * (n + 1) + src] * rw, d_rows[src] + soff[(size_t)src * (n + 1) + dst] * rw, c * rw * 8,
-                                               hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        MDBG_TRY(mdbg_shard_reduce(ctx, shards[dst], recv.p, n_recv, &reply[dst]));   // (synchronises: recv may go)
-    }
-    for (uint32_t src = 0; src < n; src++) {
-        MDBG_TRY(shards[src]->local_replies.alloc(ctx, soff[(size_t)src * (n + 1) + n]));
-        for (uint32_t dst = 0; dst < n; dst++) {
-            const uint64_t c = counts[(size_t)src * n + dst];
-            if (c) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(shards[src]->local_replies.p + soff[(size_t)src * (n + 1) + dst], reply[dst] + roff[(size_t)dst * (n + 1) + src],
-                                                      c * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        d_replies[src] = shards[src]->local_replies.p;
-    }
-    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return MDBG_OK;
-} MDBG_API_CATCH(ctx)
-
-extern "C" void mdbg_shard_free(mdbg_shard *shard) { delete shard; }

@@ -132,10 +132,6 @@ inline uint32_t rescue_m_star() {
     return m;
 }
 
-// host helpers of kminmer.hip used by partition.hip
-int alloc_rows(mdbg_ctx *ctx, mdbg_table *t, uint64_t n, bool vec);
-void update_key_hint(mdbg_ctx *ctx, int kind, uint64_t distinct, uint64_t instances);
-
 // partition.hip: the first pass with the instances partitioned by key and counted in LDS.  *done = false: this
 // input is not for it (the caller takes the one-table path); otherwise *out holds the table.
 int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, uint32_t min_abundance, mdbg_table **out, bool *done);

@@ -28,6 +28,7 @@
 // times the buckets; if that is not enough the caller's one-table path takes over.
 #include "common.hpp"
 #include "kminmer_dev.hpp"
+#include "kminmer_host.hpp"
 #include "partition_plan.hpp"
 
 #include <algorithm>

@@ -1,7 +1,7 @@
 // exchange_double.cpp -- TEST INFRASTRUCTURE: what csrc/multigpu.hip needs from the other translation units of the library, on a CPU.
 // tests/test_exchange_on_cpu.py builds libmdbg_exchange_cpu.so from the SHIPPED context.hip + multigpu.hip (+ peerlink.hpp, common.hpp,
 // objects.hpp) compiled by g++ against tests/host/hip_on_host (a stand-in for the HIP runtime over host memory), plus this file: the
-// owner-side reduction of a sharded pass (mdbg_shard_reduce, csrc/kminmer.hip on the device) restated over host memory -- for every received
+// owner-side reduction of a sharded pass (mdbg_shard_reduce, csrc/shard.hip on the device) restated over host memory -- for every received
 // row [lo, hi, count] the sum of the counts of its key, bit 63 on exactly one row per key -- and a way to make the shard handle it hangs on.
 // Nothing of the product links this.
 #include <map>

@@ -11,7 +11,7 @@ COUNT_MASK = np.uint64(0xFFFFFFFF)
 
 
 def owner_of(hi, n_ranks: int) -> np.ndarray:
-    """csrc/kminmer.hip owner_of: ((hi >> 32) * n_ranks) >> 32, the top half of hash_hi scaled to [0, n_ranks)."""
+    """csrc/shard.hip owner_of: ((hi >> 32) * n_ranks) >> 32, the top half of hash_hi scaled to [0, n_ranks)."""
     hi = np.asarray(hi).astype(np.uint64, copy=False)
     return (((hi >> np.uint64(32)) * np.uint64(n_ranks)) >> np.uint64(32)).astype(np.int64)
 

@@ -17,7 +17,7 @@ import torch.multiprocessing as mp  # noqa: E402
 
 
 def owner_of(hi: np.ndarray, n_ranks: int) -> np.ndarray:
-    """Same owner function as csrc/kminmer.hip (owner_of): top 32 bits of hash_hi scaled to [0, n_ranks)."""
+    """Same owner function as csrc/shard.hip (owner_of): top 32 bits of hash_hi scaled to [0, n_ranks)."""
     return (((hi >> np.uint64(32)) * np.uint64(n_ranks)) >> np.uint64(32)).astype(np.int64)
 
 

@@ -1,6 +1,6 @@
 """The owner's side of the sharded passes on rows and keys that are CHOSEN, against tests/shard_model.py.
 
-mdbg_shard_reduce has two forms.  The one-table form (rows_add_kernel / rows_reply_kernel, csrc/kminmer.hip) is what every small sharded
+mdbg_shard_reduce has two forms.  The one-table form (rows_add_kernel / rows_reply_kernel, csrc/shard.hip) is what every small sharded
 test runs.  The bucket form (part_owner_reduce, csrc/partition.hip: a radix split of the rows by the top bits of hash_lo, then
 owner_bucket_kernel, one workgroup per bucket summing in an LDS table) is taken from 2^17 received rows up, whatever the options say, so
 everything here that is to reach it has 2^17 rows or more -- 3 MB.  The rows are uploaded as they stand: any 128-bit key can be fed.
