@@ -679,8 +679,41 @@ int  mdbg_sequences_to_fasta_bytes(mdbg_ctx *ctx, const mdbg_sequences *seqs, co
  *       Result: pair_offsets[n_queries + 1] (the anchors' own), chains[n_pairs], match_offsets[n_pairs + 1], matches.
  *       info: queries, pairs, chains found, matches in all.  device_ptrs, in order: pair_offsets, chains, match_offsets, matches.
  *       MDBG_EINVAL: max_chaining_band 0.  Timer names: "map_chains", "map_matches".
- * What stays with the caller: the per-position top-20 selection (addAlignmentScore, :1233-1313), the compression of the match lists and the
- * partition files. */
+ *
+ * ---- the per-position selection, its merge across chunks, the alignment file --------------------------------------------------------------
+ * The rule (addAlignmentScore, :1233-1313, with AlignmentScoreComparator, :90-97): every query index of a pair's match list owns a heap of
+ * `coverage` entries (_usedCoverageForCorrection, ReadCorrection.hpp:1728: 20) whose top is the lowest score and, among equal scores, the
+ * largest read; a pair replaces the top unless its score is lower, or equal with a larger read.  Pairs arrive in ascending ref_read, so the
+ * heap a position ends with is the first `coverage` of the pairs covering it under (score descending, ref_read ascending), and a pair is
+ * SELECTED iff it is among them at one position of its list at least (:809-820).  The score is n_matches - n_diff_query (:1241) =
+ * 2 n - (last - first + 1) of the match list (mergeAlignmentScore, :376-382); it may be zero or negative, nothing filters it (:1243).
+ *
+ * mdbg_map_select  replaces the heaps of AlignReadsLowDensityFunctor::operator() (:772-841), processAnchors (:848-884) and
+ *       addAlignmentScore (:1233-1313) for one chunk: the pairs of `chains` with flags == MDBG_CHAIN_FOUND take part.  coverage: 1 ... 255,
+ *       anything else is MDBG_EINVAL.  Result per query: sel_offsets[n_queries + 1] and the selected rows in ascending ref_read (:836) --
+ *       ref_read, score, n_matches, part = 0, pair = the pair's index in `chains` -- and, gathered behind the rows, their match lists
+ *       (match_offsets[n_selected + 1], matches): the object needs no other.  n_matches is the list's full length: the reference's
+ *       partition record cuts it to 16 bits (:1279), which is a limit of that record, the caller's, not of the selection.
+ *       Timer names: "map_select", "radix_sort".
+ * mdbg_selection_from_host  a selection made of stored parts: per query the reads (strictly ascending) and per read its match list (not
+ *       empty, strictly ascending).  No score is passed: the library computes 2 n - (last - first + 1), as mergeAlignmentScore (:365-443)
+ *       does.  part = 0, pair = the row's own number.  MDBG_EINVAL with the first offending query: reads or a list that do not ascend
+ *       strictly, an empty list, offsets that do not ascend.
+ * mdbg_map_select_merge  replaces mergeAlignmentPartition (:228-363) + mergeAlignmentScore (:365-443): per query the rows of the parts
+ *       -- in chunk order, all of one n_queries -- one behind the other, selected again by the same rule.  The rows' reads must ascend
+ *       strictly across the parts (checked on the device; MDBG_EINVAL names the first offending query).  part = the part's number in this
+ *       call, pair is carried through.  n_parts == 1 re-selects one part at another coverage.  Selecting per chunk and merging gives what
+ *       one selection over all chunks' chains gives.  Timer names: "map_select", "radix_sort".
+ * mdbg_selection_to_alignment_bytes  the bytes writeAlignments (:1391-1410) writes for the selection, on the device: for every query with at
+ *       least one selected row u32 read = query_first_read + its number, u32 n, u32 ref_read[n], in read order; *n_bytes (optional) is
+ *       their size.  Fetch with mdbg_bytes_download, release with mdbg_bytes_free.  Timer name: "select_alignment_write".
+ * mdbg_selection_info  queries, selected rows, matches, candidates that took part.  _to_host: any array may be NULL.  device_ptrs, in order:
+ *       sel_offsets (u64), rows (mdbg_selected), match_offsets (u64), matches (u32).  Empty inputs give empty results.
+ * mdbg_select_lds_positions  positions of a query up to which the selection's counters live in LDS; a longer query counts in global memory.
+ *
+ * What stays with the caller: the compression of the match lists (TurboPFor, compressMatches :1315-1320) and the BGZF partition files --
+ * the reference's way of carrying a chunk's result to its merge, which an mdbg_selection (or its arrays, stored and given back through
+ * mdbg_selection_from_host) replaces -- and the base-level alignRead of ReadCorrection. */
 typedef struct mdbg_map_index mdbg_map_index;
 typedef struct mdbg_anchors mdbg_anchors;
 typedef struct mdbg_chains mdbg_chains;
@@ -711,6 +744,18 @@ int  mdbg_chains_info(const mdbg_chains *c, uint64_t info[4]);
 int  mdbg_chains_to_host(mdbg_ctx *ctx, const mdbg_chains *c, uint64_t *pair_offsets, mdbg_chain *chains, uint64_t *match_offsets, uint32_t *matches);
 int  mdbg_chains_device_ptrs(const mdbg_chains *c, const void *d_ptrs[4]);
 void mdbg_chains_free(mdbg_chains *c);
+typedef struct mdbg_selection mdbg_selection;
+typedef struct { uint32_t ref_read; int32_t score; uint32_t n_matches; uint32_t part; uint64_t pair; } mdbg_selected;   /* 24 bytes */
+int  mdbg_map_select(mdbg_ctx *ctx, const mdbg_chains *chains, uint32_t coverage, mdbg_selection **out);
+int  mdbg_selection_from_host(mdbg_ctx *ctx, uint64_t n_queries, const uint64_t *sel_offsets, const uint32_t *ref_read, const uint64_t *match_offsets,
+                              const uint32_t *matches, mdbg_selection **out);
+int  mdbg_map_select_merge(mdbg_ctx *ctx, const mdbg_selection *const *parts, uint32_t n_parts, uint32_t coverage, mdbg_selection **out);
+int  mdbg_selection_to_alignment_bytes(mdbg_ctx *ctx, const mdbg_selection *sel, uint32_t query_first_read, mdbg_bytes **out, uint64_t *n_bytes /* optional */);
+int  mdbg_selection_info(const mdbg_selection *s, uint64_t info[4]);
+int  mdbg_selection_to_host(mdbg_ctx *ctx, const mdbg_selection *s, uint64_t *sel_offsets, mdbg_selected *rows, uint64_t *match_offsets, uint32_t *matches);
+int  mdbg_selection_device_ptrs(const mdbg_selection *s, const void *d_ptrs[4]);
+void mdbg_selection_free(mdbg_selection *s);
+uint32_t mdbg_select_lds_positions(void);
 /* The library's stable radix sort (8-bit digits, least significant first; a digit in which all keys agree is skipped) on caller-chosen
    data: n uint64 keys from byte keys_at of `keys` and their n uint32 values from byte values_at of `values`, sorted by key in place, equal
    keys keeping their order.  Returns when done.  info (optional): digit passes run, digit passes skipped.  MDBG_EINVAL: a null argument,

@@ -26,6 +26,7 @@ CHAIN_FOUND, CHAIN_TOO_LONG = 1, 2          # MDBG_CHAIN_*: the flags of a row o
 CHAIN = np.dtype([("ref_read", "<u4"), ("flags", "<u4"), ("score", "<i4"), ("n_matches", "<u4"), ("query_reversed", "<u4"), ("reserved", "<u4"),
                   ("n_diff_query", "<i8"), ("n_diff_reference", "<i8"), ("query_start", "<i8"), ("query_end", "<i8"),
                   ("reference_start", "<i8"), ("reference_end", "<i8"), ("alignment_score", "<i8")])        # mdbg_chain
+SELECTED = np.dtype([("ref_read", "<u4"), ("score", "<i4"), ("n_matches", "<u4"), ("part", "<u4"), ("pair", "<u8")])   # mdbg_selected
 
 
 class MdbgError(RuntimeError):
@@ -185,6 +186,15 @@ SIGNATURES = {
     "mdbg_chains_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "mdbg_chains_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
     "mdbg_chains_free": (None, [_P]),
+    "mdbg_map_select": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P)]),
+    "mdbg_selection_from_host": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.POINTER(_P)]),
+    "mdbg_map_select_merge": (C.c_int, [_P, C.POINTER(_P), C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "mdbg_selection_to_alignment_bytes": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(_P), _u64p]),
+    "mdbg_selection_info": (C.c_int, [_P, _u64p]),
+    "mdbg_selection_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "mdbg_selection_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_selection_free": (None, [_P]),
+    "mdbg_select_lds_positions": (C.c_uint32, []),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
@@ -659,6 +669,42 @@ class Context:
         self.check(lib().mdbg_map_chains(self.h, anchors.h if anchors is not None else None, C.byref(p), C.byref(h)))
         return Chains(self, h)
 
+    def map_select(self, chains: "Chains", coverage: int = 20) -> "Selection":
+        """The per-position selection of one chunk's chains (mdbg_map_select); coverage is _usedCoverageForCorrection."""
+        h = C.c_void_p()
+        self.check(lib().mdbg_map_select(self.h, chains.h if chains is not None else None, coverage, C.byref(h)))
+        return Selection(self, h)
+
+    def selection_from_host(self, sel_offsets, ref_read, match_offsets, matches) -> "Selection":
+        """A selection made of stored parts; the library computes the scores from the lists (mdbg_selection_from_host)."""
+        so = np.ascontiguousarray(sel_offsets, dtype=np.uint64)
+        rr = np.ascontiguousarray(ref_read, dtype=np.uint32)
+        mo = np.ascontiguousarray(match_offsets, dtype=np.uint64)
+        mt = np.ascontiguousarray(matches, dtype=np.uint32)
+        h = C.c_void_p()
+        self.check(lib().mdbg_selection_from_host(self.h, len(so) - 1, _ptr(so), _ptr(rr) if len(rr) else None, _ptr(mo) if len(mo) else None,
+                                                  _ptr(mt) if len(mt) else None, C.byref(h)))
+        return Selection(self, h)
+
+    def map_select_merge(self, parts, coverage: int = 20) -> "Selection":
+        """The parts' rows of every query, in chunk order, selected again (mdbg_map_select_merge)."""
+        arr = (C.c_void_p * max(len(parts), 1))(*[p.h if p is not None else None for p in parts])
+        h = C.c_void_p()
+        self.check(lib().mdbg_map_select_merge(self.h, arr, len(parts), coverage, C.byref(h)))
+        return Selection(self, h)
+
+    def selection_to_alignment_bytes(self, sel: "Selection", query_first_read: int = 0) -> "DeviceBytes":
+        """The alignment file's bytes for the selection, composed on the device (mdbg_selection_to_alignment_bytes)."""
+        h = C.c_void_p()
+        n = C.c_uint64(0)
+        self.check(lib().mdbg_selection_to_alignment_bytes(self.h, sel.h if sel is not None else None, query_first_read, C.byref(h), C.byref(n)))
+        return DeviceBytes(self, h, int(n.value))
+
+    @staticmethod
+    def select_lds_positions() -> int:
+        """Positions of a query up to which the selection counts in LDS (mdbg_select_lds_positions)."""
+        return int(lib().mdbg_select_lds_positions())
+
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
         cut, fmt = C.c_uint64(0), C.c_int(0)
@@ -1073,6 +1119,28 @@ class Chains(_MapHandle):
         p = (C.c_void_p * 4)()
         lib().mdbg_chains_device_ptrs(self.h, p)
         return dict(zip(("pair_offsets", "chains", "match_offsets", "matches"), [x or 0 for x in p]))
+
+
+class Selection(_MapHandle):
+    """The selected rows of every query and their match lists (mdbg_map_select, mdbg_selection_from_host, mdbg_map_select_merge)."""
+    _free = "mdbg_selection_free"
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_selection_info(self.h, a)
+        return dict(zip(("n_queries", "n_selected", "n_matches", "n_candidates"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        i = self.info()
+        out = dict(sel_offsets=np.zeros(i["n_queries"] + 1, np.uint64), rows=np.zeros(i["n_selected"], SELECTED),
+                   match_offsets=np.zeros(i["n_selected"] + 1, np.uint64), matches=np.zeros(i["n_matches"], np.uint32))
+        self.ctx.check(lib().mdbg_selection_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = (C.c_void_p * 4)()
+        lib().mdbg_selection_device_ptrs(self.h, p)
+        return dict(zip(("sel_offsets", "rows", "match_offsets", "matches"), [x or 0 for x in p]))
 
 
 class Spans:

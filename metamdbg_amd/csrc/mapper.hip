@@ -47,14 +47,6 @@ struct mdbg_anchors {
     mdbg::DevBuf<uint8_t> d_rev;              // n_anchors
 };
 
-struct mdbg_chains {
-    uint64_t n_queries = 0, n_pairs = 0, n_found = 0, n_matches = 0;
-    mdbg::DevBuf<uint64_t> d_pair_off;        // n_queries + 1
-    mdbg::DevBuf<mdbg_chain> d_chain;         // n_pairs
-    mdbg::DevBuf<uint64_t> d_match_off;       // n_pairs + 1
-    mdbg::DevBuf<uint32_t> d_matches;         // n_matches
-};
-
 namespace mdbg {
 
 static_assert(sizeof(mdbg_chain) == 80, "a chain row is 80 bytes");

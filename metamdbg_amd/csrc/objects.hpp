@@ -126,6 +126,15 @@ struct mdbg_table {
     std::unique_ptr<mdbg::BucketTable> image;
 };
 
+// One chain row per (query, reference read) pair and the match lists (mapper.hip); mdbg_map_select (select.hip) reads them.
+struct mdbg_chains {
+    uint64_t n_queries = 0, n_pairs = 0, n_found = 0, n_matches = 0;
+    mdbg::DevBuf<uint64_t> d_pair_off;        // n_queries + 1
+    mdbg::DevBuf<mdbg_chain> d_chain;         // n_pairs
+    mdbg::DevBuf<uint64_t> d_match_off;       // n_pairs + 1
+    mdbg::DevBuf<uint32_t> d_matches;         // n_matches
+};
+
 // The k-min-mer spans of a batch (spans.hip); mdbg_spans_extract (extract.hip) reads the windows' fields.
 struct mdbg_spans {
     uint32_t n_reads = 0, k = 0;

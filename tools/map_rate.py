@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The rates of mdbg_map_index_build / mdbg_map_anchors / mdbg_map_chains on one resident batch, from the library's own timers (device
+"""The rates of mdbg_map_index_build / mdbg_map_anchors / mdbg_map_chains / mdbg_map_select on one resident batch, from the library's own timers (device
 events around the launches): "map_index" (windows, sort, entries, runs), "map_count" + "map_fill" (the join), "radix_sort" (the regrouping
-of the anchors), "map_group" (heads, sizes, the final rows), "map_chains" + "map_matches" -- beside a device-to-device copy of as many
+of the anchors), "map_group" (heads, sizes, the final rows), "map_chains" + "map_matches", "map_select" + its "radix_sort" -- beside a device-to-device copy of as many
 bytes as each step's algorithmic bytes, timed in the same process: the yardstick, which reads and writes that many bytes and does nothing
 else.
 
@@ -13,7 +13,10 @@ positions (mdbg_minimizers_from_host + mdbg_minimizers_attach_positions).  The r
 chunk; band 62, min_anchors 3.
 ALGORITHMIC bytes.  index: 8 B a minimizer read + 25 B an entry written + the sort's passes.  A sort pass: 12 B an item read twice (count,
 scatter) + 12 B written.  count + fill: 8 B a query minimizer + 20 B an anchor written.  group: 20 B an anchor read + 21 B written.
-chains: 13 B an anchor read + 80 B a pair written + 4 B a match.  The first call of every step is a warm-up and is not timed."""
+chains: 13 B an anchor read + 80 B a pair written + 4 B a match.  select (--coverage, 20): 80 B a pair read + 12 B a candidate's key and
+number written + the sort's passes (the query's bytes and one of the score) + 4 B a match read once + 24 B a selected row and 4 B a match of
+its list written.  Behind the table: the selected rows against the pairs, and the bytes that cross to the host with the selection (or with
+the alignment file alone) against those of the chain rows and their lists.  The first call of every step is a warm-up and is not timed."""
 from __future__ import annotations
 
 import argparse
@@ -50,13 +53,14 @@ def main():
     ap.add_argument("--coverage", type=float, default=20.0)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--band", type=int, default=62)
+    ap.add_argument("--select-coverage", type=int, default=20, help="coverage of the per-position selection (_usedCoverageForCorrection)")
     a = ap.parse_args()
     from metamdbg_amd import capi
     ctx = capi.Context(0)
     mins, off, pos = synthetic_reads(a.genome, a.read_len, a.coverage, 42)
     m = ctx.minimizers_with_positions(mins, off, pos)
     print(f"genome {a.genome} minimizers, {len(off) - 1} reads x {a.read_len} minimizers ({a.coverage:.0f}-fold), band {a.band}; {a.runs} timed runs a step")
-    for name in [n for n in ctx.step_kernel_names() if n.startswith(("map_", "sort_"))]:
+    for name in [n for n in ctx.step_kernel_names() if n.startswith(("map_", "sort_", "select"))]:
         at = ctx.kernel_attributes(name)
         print(f"kernel {name:18s} registers {at['registers']:3d}  scratch {at['scratch']}  static LDS {at['static_lds']:6d}  threads {at['threads']}")
 
@@ -126,6 +130,25 @@ def main():
     total += report("chains + match lists", chain_ms, 13 * n_a + 80 * ci["n_pairs"] + 4 * ci["n_matches"], ci["n_pairs"], "pairs")
     print(f"chains: {ci['n_chains']} of {ci['n_pairs']} pairs, {ci['n_matches']} matches")
     print(f"all steps {total:.3f} ms: {n_a / total / 1e3:.1f} M anchors/s, {ci['n_pairs'] / total / 1e3:.2f} M pairs/s; the anchors' sort is {100 * sort_ms / total:.0f} % of it")
+
+    sel, t = timed(lambda: ctx.map_select(ch, a.select_coverage), ("map_select", "radix_sort"))
+    si = sel.info()
+    n_q, n_c, n_s = si["n_queries"], si["n_candidates"], si["n_selected"]
+    rank_passes = digits(n_q - 1) + 1
+    select_ms = [x + y for x, y in zip(t["map_select"], t["radix_sort"])]
+    best = report(f"select ({rank_passes} passes of its sort)", select_ms, 80 * ci["n_pairs"] + 12 * n_c + rank_passes * 36 * n_c + 4 * ci["n_matches"] + 24 * n_s + 4 * si["n_matches"],
+                  n_c, "candidates")
+    mean_list = ci["n_matches"] / max(n_c, 1)
+    trips = max(1, -(-int(round(mean_list)) // 64))
+    print(f"select: its sort " + " ".join(f"{x:.3f}" for x in t["radix_sort"]) + f" ms; against the chains step of this run: {best / min(chain_ms):.2f}; "
+          f"mean list {mean_list:.1f} matches = {100 * mean_list / (64 * trips):.0f} % of the lanes of its {trips} trip(s)")
+    by = ctx.selection_to_alignment_bytes(sel)
+    chain_bytes = 8 * (n_q + 1) + 80 * ci["n_pairs"] + 8 * (ci["n_pairs"] + 1) + 4 * ci["n_matches"]
+    sel_bytes = 8 * (n_q + 1) + 24 * n_s + 8 * (n_s + 1) + 4 * si["n_matches"]
+    print(f"selected: {n_s} rows of {n_c} candidates of {ci['n_pairs']} pairs ({100 * n_s / max(ci['n_pairs'], 1):.1f} %) at coverage {a.select_coverage}")
+    print(f"to the host: chain rows + lists {chain_bytes / 1e6:.2f} MB; the selection with its lists {sel_bytes / 1e6:.2f} MB ({100 * sel_bytes / chain_bytes:.1f} %); "
+          f"the alignment file alone {by.n / 1e6:.2f} MB ({100 * by.n / chain_bytes:.1f} %)")
+    by.free(); sel.free()
     for o in (ch, an, ix, m):
         o.free()
     ctx.close()
