@@ -735,39 +735,78 @@ static SplitForm split_form(const mdbg_ctx *ctx) {
     return SplitForm{PART_NT, ctx->part_tile == 2048 ? PART_TILE / 2 : PART_TILE};
 }
 
-static void launch_split_hist(mdbg_ctx *ctx, bool from_mins, SplitForm f, unsigned grid, const SplitArgs &a, uint32_t *hist) {
-    if (f.threads == PART_NT_SMALL && PART_NT_SMALL != PART_NT) {
-        if (from_mins) hipLaunchKernelGGL((split_hist_kernel<true, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, hist);
-        else hipLaunchKernelGGL((split_hist_kernel<false, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, hist);
-    } else {
-        if (from_mins) hipLaunchKernelGGL((split_hist_kernel<true, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, hist);
-        else hipLaunchKernelGGL((split_hist_kernel<false, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, hist);
-    }
+// (FROM_MINS: level 1, which computes its records from the flat minimizer array; the record levels read them back)
+template <bool FROM_MINS>
+static void launch_split_hist(mdbg_ctx *ctx, SplitForm f, unsigned grid, const SplitArgs &a, uint32_t *hist) {
+    if (f.threads == PART_NT_SMALL && PART_NT_SMALL != PART_NT)
+        hipLaunchKernelGGL((split_hist_kernel<FROM_MINS, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, hist);
+    else
+        hipLaunchKernelGGL((split_hist_kernel<FROM_MINS, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, hist);
     ctx->part_form[0] = f.threads; ctx->part_form[1] = f.tile;
 }
 
-static void launch_split_scatter(mdbg_ctx *ctx, bool from_mins, SplitForm f, unsigned grid, const SplitArgs &a, const uint64_t *place, RecView out) {
-    if (f.tile == PART_TILE_SMALL && f.threads == PART_NT_SMALL) {
-        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E_SMALL, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, place, out);
-        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E_SMALL, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, place, out);
-    } else if (f.tile != PART_TILE) {
-        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E / 2, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
-        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E / 2, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
-    } else {
-        if (from_mins) hipLaunchKernelGGL((split_scatter_kernel<true, PART_E, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
-        else hipLaunchKernelGGL((split_scatter_kernel<false, PART_E, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
-    }
+template <bool FROM_MINS>
+static void launch_split_scatter(mdbg_ctx *ctx, SplitForm f, unsigned grid, const SplitArgs &a, const uint64_t *place, RecView out) {
+    if (f.tile == PART_TILE_SMALL && f.threads == PART_NT_SMALL)
+        hipLaunchKernelGGL((split_scatter_kernel<FROM_MINS, PART_E_SMALL, PART_NT_SMALL>), dim3(grid), dim3(PART_NT_SMALL), 0, ctx->stream, a, place, out);
+    else if (f.tile != PART_TILE)
+        hipLaunchKernelGGL((split_scatter_kernel<FROM_MINS, PART_E / 2, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
+    else
+        hipLaunchKernelGGL((split_scatter_kernel<FROM_MINS, PART_E, PART_NT>), dim3(grid), dim3(PART_NT), 0, ctx->stream, a, place, out);
     ctx->part_form[0] = f.threads; ctx->part_form[1] = f.tile;
 }
 
-struct LevelPlan { uint32_t bits, shift, ways, blocks_per_seg; uint64_t n_seg; };
+// What a radix split works in, and where it left the records: buf[cur] holds them, bucket b of the last level run is
+// [pos[b * stride], pos[(b + 1) * stride]) -- `pos` that level's `place` (the scanned histogram), `stride` its blocks per segment.
+// The buffers are their user's own, so that they go back to the pool when, and in the order, they always have.
+struct LevelBufs {
+    RecBufs *buf;                                      // [2]
+    DevBuf<uint32_t> &hist;
+    DevBuf<uint64_t> *place;                           // [3]
+    uint32_t cur = 0, stride = 1;
+    const uint64_t *pos = nullptr;
+};
 
-template <uint32_t C, uint32_t LIST>
-static void launch_bucket_count(mdbg_ctx *ctx, uint64_t n_buckets, RecView in, const uint64_t *pos, uint32_t stride, uint32_t min_abundance, uint32_t clip, int keep_all,
-                                RecView keys, uint32_t *kcnt, uint32_t *n_keys, uint32_t *n_kept, uint8_t *cnt8, uint32_t cnt8_default, uint32_t *overflow,
-                                uint32_t *fell_back) {
-    hipLaunchKernelGGL((bucket_count_kernel<C, LIST>), dim3((unsigned)n_buckets), dim3(BC_NT), 0, ctx->stream, in, pos, stride, min_abundance, clip, keep_all, keys, kcnt,
-                       n_keys, n_kept, cnt8, cnt8_default, overflow, fell_back, table_priority(ctx));
+// The n records of s.buf[s.cur] through levels [first, p.n_levels) of the plan: per level the histogram, its scan into place[l], the
+// scatter into the other buffer.  s.pos / s.stride come in as the level above's (null / 1: none, the records are one segment) and go out as
+// the last level's.  Interval: what wraps every split launch, the scans staying outside -- LaunchTimer: an interval of its own, named
+// `timer` (the first pass); NoInterval: nothing (the owner, which holds one object around everything).
+struct NoInterval { NoInterval(mdbg_ctx *, const char *) {} };
+
+template <typename Interval>
+static int run_record_levels(mdbg_ctx *ctx, SplitForm form, LevelBufs &s, uint64_t n, const BucketPlan &p, uint32_t first, uint32_t prio, const char *timer) {
+    for (uint32_t l = first; l < p.n_levels; l++) {
+        const LevelPlan &lv = p.lv[l];
+        SplitArgs d{};
+        d.in = s.buf[s.cur].view();
+        d.n_min = n;                                               // no level above: one segment, the records as they arrived (not read below one)
+        d.seg_pos = s.pos; d.seg_stride = s.stride; d.blocks_per_seg = deeper_blocks_per_seg(n, lv.n_seg, form.tile);
+        d.shift = lv.shift; d.ways = lv.ways; d.tile = form.tile; d.prio = prio;
+        const uint64_t entries = lv.n_seg * lv.ways * d.blocks_per_seg;
+        MDBG_TRY(s.hist.alloc(ctx, entries));
+        MDBG_TRY(s.place[l].alloc(ctx, entries + 1));
+        const unsigned grid = level_grid(lv.n_seg, d.blocks_per_seg);
+        {
+            Interval t(ctx, timer);
+            launch_split_hist<false>(ctx, form, grid, d, s.hist.p);
+        }
+        MDBG_TRY(exclusive_scan_u32(ctx, s.hist.p, s.place[l].p, entries));
+        {
+            Interval t(ctx, timer);
+            launch_split_scatter<false>(ctx, form, grid, d, s.place[l].p, s.buf[s.cur ^ 1].view());
+        }
+        s.cur ^= 1; s.pos = s.place[l].p; s.stride = d.blocks_per_seg;
+    }
+    return MDBG_OK;
+}
+
+// The kernels that keep a bucket's table in LDS are instantiated for 256, 1024 and 2048 slots: f(std::integral_constant<uint32_t, C>)
+// for the plan's ("partition_lds_slots" takes other values as 2048, as it always has).
+template <typename F>
+static void with_lds_slots(uint32_t lds_slots, F &&f) {
+    if (lds_slots == 256) f(std::integral_constant<uint32_t, 256>());
+    else if (lds_slots == 1024) f(std::integral_constant<uint32_t, 1024>());
+    else f(std::integral_constant<uint32_t, 2048>());
 }
 
 // the rows of one group of keys, kept aside while the next group reuses the record buffers (several groups only)
@@ -791,8 +830,6 @@ static double hll_estimate(const uint32_t *regs) {
 // One partitioned pass over a read set: the plan, the buffers, and the two halves every user runs per group of keys -- split_group (the
 // radix levels) and count_group (one workgroup per bucket) -- which mdbg_kminmer_count_first and the sharded first pass put together
 // differently (the latter keeps every distinct key and walks the records a second time once the global counts are back).
-constexpr uint32_t PART_MAX_BITS = 22;
-
 struct PartRun {
     mdbg_ctx *ctx = nullptr;
     const mdbg_minimizers *reads = nullptr;
@@ -803,11 +840,11 @@ struct PartRun {
     // before that the guess is the last first pass's keys per instance (key_ratio_hint), which only decides the ways of level 1
     // for small inputs: from 2^8 buckets up level 1 always takes 8 bits, so the histogram is not run twice.
     uint64_t I_est = 0, n_groups = 1;
-    uint32_t group_bits = 0, lds_slots = 0, bucket_bits = 0, n_levels = 1, extra_bits = 0, tile = PART_TILE;
+    uint32_t group_bits = 0, extra_bits = 0;
     SplitForm form{PART_NT, PART_TILE};
     double keys_est = 1.0;
     bool sketched = false;
-    LevelPlan lv[3];
+    BucketPlan bp;                                     // LDS slots, bucket bits, levels (partition_plan.hpp)
     // buffers
     DevBuf<uint32_t> start_bits, kcnt, hist, n_keys, n_kept, overflow, hll_merged;
     DevBuf<uint32_t> fell_back;                        // instances whose slot bucket_count looked up a second time (lds_find)
@@ -815,41 +852,11 @@ struct PartRun {
     DevBuf<uint64_t> place[3], key_pos, row_of;
     DevBuf<uint8_t> hll_blocks;
     RecBufs buf[2];
+    LevelBufs rec{buf, hist, place};
     // the group last split / counted
     uint64_t I = 0, n_buckets = 0;
-    uint32_t cur = 0, stride = 1;
-    const uint64_t *pos = nullptr;
 
-    uint32_t bits_for(uint32_t c) const {
-        // (a mean load of up to 0.78: the fullest of 65 536 buckets is then near 0.9, where an LDS probe sequence is still a dozen slots -- and
-        // one radix level less is worth more than short probes: at 6 x coverage, 46 M keys in 172 M instances, 0.70 asked for a third level)
-        const double b = keys_est / (double)n_groups / (0.78 * c);
-        uint32_t n = 0;
-        while ((double)(1ull << n) < b && n < 40) n++;
-        return n;
-    }
-    static uint32_t levels_for(uint32_t bits) { return bits <= 8 ? 1u : (bits + 7u) / 8u; }
-    void plan() {
-        lds_slots = ctx->part_lds_slots;
-        // (1024 slots where they need no level more than 2048 would: four buckets instead of two per CU count a fifth faster)
-        if (!lds_slots) lds_slots = levels_for(bits_for(1024) + extra_bits) <= levels_for(bits_for(2048) + extra_bits) && bits_for(1024) + extra_bits <= PART_MAX_BITS ? 1024u : 2048u;
-        bucket_bits = (ctx->part_bits ? ctx->part_bits : bits_for(lds_slots)) + extra_bits;
-        n_levels = levels_for(bucket_bits);
-        // level 1 takes 8 bits whenever there are that many, the deeper levels share the rest
-        uint32_t left = bucket_bits, used = group_bits;
-        uint64_t segs = 1;
-        for (uint32_t l = 0; l < n_levels && l < 3; l++) {
-            const uint32_t b = l == 0 ? std::min(left, 8u) : (left + (n_levels - l) - 1) / (n_levels - l);
-            lv[l].bits = b; lv[l].ways = 1u << b; lv[l].n_seg = segs;
-            // level 1 splits by window_mix, the deeper levels by the bits of hash_lo below the key group's
-            lv[l].shift = (l == 0 || used + b == 0) ? 0u : 64u - used - b;      // (one way: the digit is masked to 0 whatever the shift)
-            if (l > 0) used += b;
-            left -= b; segs <<= b;
-        }
-    }
-    // more distinct keys than the buckets of one launch hold (one 512-thread workgroup per bucket, and a launch of 2^32 threads wraps): not
-    // for this path -- 2^22 buckets of 2048 slots are 6.7 G keys per key group, more than the 2^32 minimizers a call takes
-    bool too_many_buckets() const { return bucket_bits > PART_MAX_BITS; }
+    void plan() { bp = first_pass_plan(keys_est, n_groups, group_bits, extra_bits, ctx->part_lds_slots, ctx->part_bits); }
 
     // sequence starts (one bit per minimizer), the key groups, the first plan
     int init(mdbg_ctx *c, const mdbg_minimizers *r, uint32_t k_) {
@@ -863,13 +870,11 @@ struct PartRun {
         }
         I_est = std::max<uint64_t>(M / 8 + 1, M > (uint64_t)(k - 1) * n_reads ? M - (uint64_t)(k - 1) * n_reads : 0);
         const uint64_t max_records = ctx->part_max_records ? ctx->part_max_records : std::max<uint64_t>(1ull << 24, (uint64_t)((double)ctx->hbm_bytes * 0.25 / 44.0));
-        group_bits = 0;
-        while (((I_est + ((1ull << group_bits) - 1)) >> group_bits) > max_records && group_bits < 16) group_bits++;
+        group_bits = group_bits_for(I_est, max_records);
         n_groups = 1ull << group_bits;
         keys_est = std::max(1.0, (double)I_est * ctx->key_ratio_hint[0]);
         sketched = ctx->part_bits != 0;                 // a forced plan needs no estimate
         form = split_form(ctx);
-        tile = form.tile;
         MDBG_TRY(overflow.alloc(ctx, 1));
         MDBG_TRY(fell_back.alloc(ctx, 1));
         plan();
@@ -882,39 +887,39 @@ struct PartRun {
         return MDBG_OK;
     }
 
-    // the records of key group g through every radix level; leaves I, cur, pos, stride, n_buckets.  *give_up: the sketch asks for more
-    // buckets than this path has (the caller hands the input back)
+    // the records of key group g through every radix level; leaves I, n_buckets and the records in `rec`.  *give_up: the sketch asks for
+    // more buckets than this path has (the caller hands the input back)
     int split_group(uint64_t g, bool *give_up) {
         *give_up = false;
+        const LevelPlan *lv = bp.lv;
         SplitArgs a{};
         a.mins = reads->d_min.p; a.start_bits = start_bits.p; a.n_min = M; a.k = k;
         a.group_bits = group_bits; a.group = g;
-        a.tile = tile;
+        a.tile = form.tile;
         a.prio = table_priority(ctx);
         // level 1: histogram, scan, the group's instance count, scatter
-        uint64_t entries = 0;
+        const uint32_t blocks = level1_blocks_per_seg(M, form.tile);
         for (;;) {
-            lv[0].blocks_per_seg = level1_blocks_per_seg(M, tile);
-            a.seg_pos = nullptr; a.seg_stride = 1; a.blocks_per_seg = lv[0].blocks_per_seg; a.shift = lv[0].shift; a.ways = lv[0].ways; a.mix_bits = lv[0].bits;
-            entries = (uint64_t)lv[0].ways * lv[0].blocks_per_seg;
-            MDBG_TRY(hist.alloc(ctx, entries));
-            MDBG_TRY(place[0].alloc(ctx, entries + 1));
+            a.seg_pos = nullptr; a.seg_stride = 1; a.blocks_per_seg = blocks; a.shift = lv[0].shift; a.ways = lv[0].ways; a.mix_bits = lv[0].bits;
+            const uint64_t entries = (uint64_t)lv[0].ways * blocks;
+            MDBG_TRY(rec.hist.alloc(ctx, entries));
+            MDBG_TRY(rec.place[0].alloc(ctx, entries + 1));
             a.hll = nullptr;
             if (!sketched) {
-                MDBG_TRY(hll_blocks.alloc(ctx, (uint64_t)lv[0].blocks_per_seg * HLL_M));
+                MDBG_TRY(hll_blocks.alloc(ctx, (uint64_t)blocks * HLL_M));
                 MDBG_TRY(hll_merged.alloc(ctx, HLL_M));
                 MDBG_HIP_CHECK(ctx, hipMemsetAsync(hll_merged.p, 0, HLL_M * 4, ctx->stream));
                 a.hll = hll_blocks.p;
             }
             {
                 LaunchTimer timer(ctx, "kminmer_split");
-                launch_split_hist(ctx, true, form, lv[0].blocks_per_seg, a, hist.p);
-                if (a.hll) hipLaunchKernelGGL(hll_merge_kernel, dim3(HLL_M / 256, 64), dim3(256), 0, ctx->stream, hll_blocks.p, lv[0].blocks_per_seg, hll_merged.p, a.prio);
+                launch_split_hist<true>(ctx, form, blocks, a, rec.hist.p);
+                if (a.hll) hipLaunchKernelGGL(hll_merge_kernel, dim3(HLL_M / 256, 64), dim3(256), 0, ctx->stream, hll_blocks.p, blocks, hll_merged.p, a.prio);
             }
-            MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[0].p, entries));
+            MDBG_TRY(exclusive_scan_u32(ctx, rec.hist.p, rec.place[0].p, entries));
             uint32_t regs[HLL_M];
             if (a.hll) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(regs, hll_merged.p, HLL_M * 4, hipMemcpyDeviceToHost, ctx->stream));
-            MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &I, place[0].p + entries, 8, hipMemcpyDeviceToHost));
+            MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &I, rec.place[0].p + entries, 8, hipMemcpyDeviceToHost));
             if (!a.hll) break;
             // the sketch saw every key of every group: plan on it (+8 %: three and a half standard errors); the histogram is
             // only repeated when that changes level 1, i.e. for inputs of fewer keys than 2^8 buckets hold
@@ -923,49 +928,25 @@ struct PartRun {
             keys_est = std::max(1.0, 1.08 * hll_estimate(regs));
             plan();
             MDBG_DBG(ctx, "partitioned first pass: about %.0f distinct keys", keys_est / 1.08);
-            if (too_many_buckets()) { *give_up = true; return MDBG_OK; }
+            if (bp.too_many_buckets()) { *give_up = true; return MDBG_OK; }
             if (lv[0].bits == old_bits) break;
         }
-        n_buckets = 1ull << bucket_bits;
+        n_buckets = 1ull << bp.bucket_bits;
         MDBG_DBG(ctx, "partitioned first pass: group %llu of %llu, %llu instances, %u + %u + %u bits, %u LDS slots", (unsigned long long)g,
-                 (unsigned long long)n_groups, (unsigned long long)I, lv[0].bits, n_levels > 1 ? lv[1].bits : 0, n_levels > 2 ? lv[2].bits : 0, lds_slots);
-        MDBG_TRY(buf[0].ensure(ctx, I));
-        MDBG_TRY(buf[1].ensure(ctx, I));
+                 (unsigned long long)n_groups, (unsigned long long)I, lv[0].bits, bp.n_levels > 1 ? lv[1].bits : 0, bp.n_levels > 2 ? lv[2].bits : 0, bp.lds_slots);
+        MDBG_TRY(rec.buf[0].ensure(ctx, I));
+        MDBG_TRY(rec.buf[1].ensure(ctx, I));
         if (kcnt.n < I || !kcnt.p) MDBG_TRY(kcnt.alloc(ctx, I));
         {
             LaunchTimer timer(ctx, "kminmer_split");
-            launch_split_scatter(ctx, true, form, lv[0].blocks_per_seg, a, place[0].p, buf[0].view());
+            launch_split_scatter<true>(ctx, form, blocks, a, rec.place[0].p, rec.buf[0].view());
         }
-        // deeper levels
-        cur = 0;
-        for (uint32_t l = 1; l < n_levels; l++) {
-            const uint64_t n_seg = lv[l].n_seg;
-            lv[l].blocks_per_seg = deeper_blocks_per_seg(I, n_seg, tile);
-            SplitArgs d{};
-            d.in = buf[cur].view();
-            d.seg_pos = place[l - 1].p; d.seg_stride = lv[l - 1].blocks_per_seg; d.blocks_per_seg = lv[l].blocks_per_seg;
-            d.shift = lv[l].shift; d.ways = lv[l].ways; d.n_min = 0; d.tile = tile; d.prio = a.prio;
-            entries = n_seg * lv[l].ways * lv[l].blocks_per_seg;
-            MDBG_TRY(hist.alloc(ctx, entries));
-            MDBG_TRY(place[l].alloc(ctx, entries + 1));
-            const unsigned grid = level_grid(n_seg, lv[l].blocks_per_seg);
-            {
-                LaunchTimer timer(ctx, "kminmer_split");
-                launch_split_hist(ctx, false, form, grid, d, hist.p);
-            }
-            MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[l].p, entries));
-            {
-                LaunchTimer timer(ctx, "kminmer_split");
-                launch_split_scatter(ctx, false, form, grid, d, place[l].p, buf[cur ^ 1].view());
-            }
-            cur ^= 1;
-        }
-        pos = place[n_levels - 1].p;
-        stride = lv[n_levels - 1].blocks_per_seg;
-        return MDBG_OK;
+        // deeper levels, each launch in an interval of its own
+        rec.cur = 0; rec.pos = rec.place[0].p; rec.stride = blocks;
+        return run_record_levels<LaunchTimer>(ctx, form, rec, I, bp, 1, a.prio, "kminmer_split");
     }
-    RecView records() { return buf[cur].view(); }
-    RecView keys() { return buf[cur ^ 1].view(); }      // the free record buffer: every bucket's kept keys, compacted, at its start
+    RecView records() { return rec.buf[rec.cur].view(); }
+    RecView keys() { return rec.buf[rec.cur ^ 1].view(); }      // the free record buffer: every bucket's kept keys, compacted, at its start
 
     // one workgroup per bucket: counts, the kept keys, (cnt8) the rare instances' counts; then the buckets' key / kept-key offsets
     int count_group(uint32_t min_abundance, uint32_t clip, int keep_all, uint8_t *cnt8, uint32_t cnt8_default) {
@@ -977,27 +958,39 @@ struct PartRun {
         }
         {
             LaunchTimer timer(ctx, "kminmer_insert");
-#define MDBG_BC(C, L) launch_bucket_count<C, L>(ctx, n_buckets, records(), pos, stride, min_abundance, clip, keep_all, keys(), kcnt.p, n_keys.p, n_kept.p, cnt8, cnt8_default, overflow.p, fell_back.p)
-            const bool list = ctx->part_slot_list != 0;
-            if (lds_slots == 256) { if (list) MDBG_BC(256, 8000); else MDBG_BC(256, 0); }
-            else if (lds_slots == 1024) { if (list) MDBG_BC(1024, 8000); else MDBG_BC(1024, 0); }
-            else { if (list) MDBG_BC(2048, 4096); else MDBG_BC(2048, 0); }
-#undef MDBG_BC
+            with_lds_slots(bp.lds_slots, [&](auto slots) {
+                constexpr uint32_t C = decltype(slots)::value, LIST = C == 2048 ? 4096 : 8000;
+                const auto kernel = ctx->part_slot_list ? bucket_count_kernel<C, LIST> : bucket_count_kernel<C, 0>;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)n_buckets), dim3(BC_NT), 0, ctx->stream, records(), rec.pos, rec.stride, min_abundance, clip, keep_all, keys(), kcnt.p,
+                                   n_keys.p, n_kept.p, cnt8, cnt8_default, overflow.p, fell_back.p, table_priority(ctx));
+            });
         }
         MDBG_HIP_CHECK(ctx, hipGetLastError());
         MDBG_TRY(exclusive_scan_u32(ctx, n_keys.p, key_pos.p, n_buckets));
         MDBG_TRY(exclusive_scan_u32(ctx, n_kept.p, row_of.p, n_buckets));
         return MDBG_OK;
     }
-    void record_info(uint32_t attempt, uint64_t total_inst) const {
-        ctx->part_info[0] = 2; ctx->part_info[1] = n_groups; ctx->part_info[2] = bucket_bits; ctx->part_info[3] = n_levels;
-        ctx->part_info[4] = attempt; ctx->part_info[5] = lds_slots; ctx->part_info[6] = n_buckets; ctx->part_info[7] = total_inst;
-        ctx->part_fell_back = fell_back_host;
-    }
-    // (with the pass's other totals: the caller synchronises before it reads fell_back_host)
-    int read_fell_back() {
-        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&fell_back_host, fell_back.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    // The totals of the group just counted: its distinct keys, its kept keys (null: not asked for, not copied), whether a bucket outgrew
+    // its table; waits for the stream.  *hand_back: a key with a zero word, which no number of buckets helps -- the one-table pass takes the input.
+    int read_totals(uint64_t *keys_total, uint64_t *kept_total, bool *overflowed, bool *hand_back) {
+        uint32_t ov = 0;
+        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(keys_total, key_pos.p + n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (kept_total) MDBG_HIP_CHECK(ctx, hipMemcpyAsync(kept_total, row_of.p + n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, overflow.p, 4, hipMemcpyDeviceToHost));
+        *hand_back = ov == PART_OVERFLOW_ZERO_KEY;
+        *overflowed = ov != 0;
+        if (*hand_back) MDBG_DBG(ctx, "partitioned first pass: a key with a zero word: the one-table pass takes the input");
         return MDBG_OK;
+    }
+    // the kept keys of the group just counted as rows [0, kept_total) of `ro` (the caller's interval)
+    void emit_rows(const RowOut &ro) {
+        hipLaunchKernelGGL(emit_bucket_rows_kernel, dim3((unsigned)n_buckets), dim3(256), 0, ctx->stream, keys(), kcnt.p, rec.pos, rec.stride, n_kept.p, row_of.p, reads->d_min.p,
+                           ro, (uint64_t)0, table_priority(ctx));
+    }
+    void record_info(uint32_t attempt, uint64_t total_inst) const {
+        ctx->part_info[0] = 2; ctx->part_info[1] = n_groups; ctx->part_info[2] = bp.bucket_bits; ctx->part_info[3] = bp.n_levels;
+        ctx->part_info[4] = attempt; ctx->part_info[5] = bp.lds_slots; ctx->part_info[6] = n_buckets; ctx->part_info[7] = total_inst;
+        ctx->part_fell_back = fell_back_host;
     }
 };
 
@@ -1005,11 +998,40 @@ static bool part_applicable(const mdbg_minimizers *reads, uint32_t k) {
     return k <= PART_MAX_K && reads->n_min >= k && reads->n_min < (1ull << 32);
 }
 
+// The rescue tail of a partitioned pass, on the instances' clipped counts (cnt8): what RescuePlan / plan_rescue / launch_emit_rescued
+// (kminmer_host.hpp) are to a pass that reads its counts from a table's slots.
+struct PartRescue {
+    DevBuf<uint32_t> cnt;
+    DevBuf<uint64_t> pos;
+    uint64_t total = 0;                                // on its way: valid after the caller's next wait for the stream
+};
+
+// decision per read, row positions, the total asked for
+static int plan_part_rescue(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, const uint8_t *cnt8, uint32_t m_star, PartRescue &r) {
+    const uint32_t n_reads = reads->n_reads;
+    MDBG_TRY(r.cnt.alloc(ctx, n_reads));
+    MDBG_TRY(r.pos.alloc(ctx, (size_t)n_reads + 1));
+    {
+        LaunchTimer timer(ctx, "kminmer_rescue");
+        hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8, m_star, r.cnt.p, table_priority(ctx));
+    }
+    MDBG_TRY(exclusive_scan_u32(ctx, r.cnt.p, r.pos.p, n_reads));
+    MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&r.total, r.pos.p + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return MDBG_OK;
+}
+
+// the rescued rows behind the table's own, from row_base (inside the caller's "kminmer_emit")
+static void launch_emit_part_rescued(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, const uint8_t *cnt8, const PartRescue &r, const RowOut &ro, uint64_t row_base) {
+    if (!r.total) return;
+    const unsigned blocks = grid_for((uint64_t)reads->n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
+    hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, reads->n_reads, k, cnt8, r.cnt.p, r.pos.p, ro, row_base,
+                       table_priority(ctx));
+}
+
 int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, uint32_t min_abundance, mdbg_table **out, bool *done) {
     *done = false;
     if (!part_applicable(reads, k)) return MDBG_OK;
     const uint64_t M = reads->n_min;
-    const uint32_t n_reads = reads->n_reads;
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t m_star = rescue_m_star();
     const uint32_t clip = 2u * m_star + 1u;
@@ -1021,15 +1043,14 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
     DevBuf<uint8_t> cnt8;
     if (do_rescue) MDBG_TRY(cnt8.alloc(ctx, M));
     uint32_t cnt8_default = 0;
-    DevBuf<uint32_t> resc_cnt;
-    DevBuf<uint64_t> resc_pos;
+    PartRescue resc;
     std::vector<GroupRows> group_rows;
     const uint64_t n_groups = run.n_groups;
 
     for (uint32_t attempt = 1;; attempt++) {
         MDBG_TRY(run.begin_attempt());
-        if (run.too_many_buckets() || attempt > 4) {
-            MDBG_DBG(ctx, "partitioned first pass gives up at %u bucket bits", run.bucket_bits);
+        if (run.bp.too_many_buckets() || attempt > 4) {
+            MDBG_DBG(ctx, "partitioned first pass gives up at %u bucket bits", run.bp.bucket_bits);
             return MDBG_OK;
         }
         bool cnt8_filled = false;
@@ -1049,12 +1070,11 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             }
             MDBG_TRY(run.count_group(min_abundance, clip, 0, do_rescue ? cnt8.p : nullptr, cnt8_default));
             if (n_groups == 1) break;                   // totals are read with the rescue count's, below
-            uint64_t nk = 0, ns = 0; uint32_t ov = 0;
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&nk, run.key_pos.p + run.n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&ns, run.row_of.p + run.n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, run.overflow.p, 4, hipMemcpyDeviceToHost));
-            if (ov == PART_OVERFLOW_ZERO_KEY) { MDBG_DBG(ctx, "partitioned first pass: a key with a zero word: the one-table pass takes the input"); return MDBG_OK; }
-            if (ov) { overflowed = true; break; }
+            uint64_t nk = 0, ns = 0;
+            bool hand_back = false;
+            MDBG_TRY(run.read_totals(&nk, &ns, &overflowed, &hand_back));
+            if (hand_back) return MDBG_OK;
+            if (overflowed) break;
             total_keys += nk; total_solid += ns;
             group_rows.emplace_back();
             GroupRows &gr = group_rows.back();
@@ -1062,35 +1082,23 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
             MDBG_TRY(gr.lo.alloc(ctx, ns)); MDBG_TRY(gr.hi.alloc(ctx, ns)); MDBG_TRY(gr.ab.alloc(ctx, ns)); MDBG_TRY(gr.vec.alloc(ctx, ns * k));
             RowOut ro{gr.lo.p, gr.hi.p, gr.ab.p, gr.vec.p, k};
             LaunchTimer timer(ctx, "kminmer_emit");
-            hipLaunchKernelGGL(emit_bucket_rows_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.pos, run.stride, run.n_kept.p,
-                               run.row_of.p, reads->d_min.p, ro, (uint64_t)0, table_priority(ctx));
+            run.emit_rows(ro);
         }
 
         // rescue decision per read, row positions
-        uint64_t n_resc = 0;
-        MDBG_TRY(run.read_fell_back());
-        if (!overflowed && do_rescue) {
-            MDBG_TRY(resc_cnt.alloc(ctx, n_reads));
-            MDBG_TRY(resc_pos.alloc(ctx, (size_t)n_reads + 1));
-            {
-                LaunchTimer timer(ctx, "kminmer_rescue");
-                hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p, table_priority(ctx));
-            }
-            MDBG_TRY(exclusive_scan_u32(ctx, resc_cnt.p, resc_pos.p, n_reads));
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&n_resc, resc_pos.p + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (!overflowed && n_groups == 1) {
-            uint32_t ov = 0;
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&total_keys, run.key_pos.p + run.n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&total_solid, run.row_of.p + run.n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
-            MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, run.overflow.p, 4, hipMemcpyDeviceToHost));
-            if (ov == PART_OVERFLOW_ZERO_KEY) { MDBG_DBG(ctx, "partitioned first pass: a key with a zero word: the one-table pass takes the input"); return MDBG_OK; }
-            overflowed = ov != 0;
+        resc.total = 0;
+        // (with the pass's other totals: the wait below comes before record_info reads fell_back_host)
+        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&run.fell_back_host, run.fell_back.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (!overflowed && do_rescue) MDBG_TRY(plan_part_rescue(ctx, reads, k, cnt8.p, m_star, resc));
+        if (!overflowed && n_groups == 1) {            // (one wait brings these totals, the rescue count's and fell_back)
+            bool hand_back = false;
+            MDBG_TRY(run.read_totals(&total_keys, &total_solid, &overflowed, &hand_back));
+            if (hand_back) return MDBG_OK;
         } else {
             MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         }
         if (overflowed) {
-            MDBG_DBG(ctx, "partitioned first pass: a bucket outgrew its %u LDS slots at %u bucket bits, again with more", run.lds_slots, run.bucket_bits);
+            MDBG_DBG(ctx, "partitioned first pass: a bucket outgrew its %u LDS slots at %u bucket bits, again with more", run.bp.lds_slots, run.bp.bucket_bits);
             run.extra_bits += 2;
             continue;
         }
@@ -1099,14 +1107,13 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
         std::unique_ptr<mdbg_table> t(new mdbg_table());
         t->k = k;
         t->n_solid = total_solid;
-        t->st_minimizers = M; t->st_instances = total_inst; t->st_keys = total_keys; t->st_slots = n_groups * run.n_buckets * run.lds_slots;
-        MDBG_TRY(alloc_rows(ctx, t.get(), total_solid + n_resc, true));
+        t->st_minimizers = M; t->st_instances = total_inst; t->st_keys = total_keys; t->st_slots = n_groups * run.n_buckets * run.bp.lds_slots;
+        MDBG_TRY(alloc_rows(ctx, t.get(), total_solid + resc.total, true));
         RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, t->d_vec.p, k};
         {
             LaunchTimer timer(ctx, "kminmer_emit");
             if (n_groups == 1) {
-                hipLaunchKernelGGL(emit_bucket_rows_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.pos, run.stride,
-                                   run.n_kept.p, run.row_of.p, reads->d_min.p, ro, (uint64_t)0, table_priority(ctx));
+                run.emit_rows(ro);
             } else {
                 uint64_t at = 0;
                 for (GroupRows &gr : group_rows) {
@@ -1119,11 +1126,7 @@ int count_first_partitioned(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_
                     at += gr.n;
                 }
             }
-            if (n_resc) {
-                const unsigned blocks = grid_for((uint64_t)n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
-                hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, n_reads, k, cnt8.p, resc_cnt.p,
-                                   resc_pos.p, ro, total_solid, table_priority(ctx));
-            }
+            launch_emit_part_rescued(ctx, reads, k, cnt8.p, resc, ro, total_solid);
         }
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "partitioned first pass failed: %s", hipGetErrorString(e));
@@ -1159,16 +1162,14 @@ int part_local_keys(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, Par
     if (run.n_groups != 1) return MDBG_OK;            // (a rank's share that needs key groups: the one-table pass takes it)
     for (uint32_t attempt = 1;; attempt++) {
         MDBG_TRY(run.begin_attempt());
-        if (run.too_many_buckets() || attempt > 4) return MDBG_OK;
-        bool give_up = false;
+        if (run.bp.too_many_buckets() || attempt > 4) return MDBG_OK;
+        bool give_up = false, overflowed = false, hand_back = false;
         MDBG_TRY(run.split_group(0, &give_up));
         if (give_up) return MDBG_OK;
         MDBG_TRY(run.count_group(0u, 0u, 1, nullptr, 0u));       // keep every key; the instances' counts wait for the global ones
-        uint32_t ov = 0;
-        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&pl->n_keys, run.key_pos.p + run.n_buckets, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, run.overflow.p, 4, hipMemcpyDeviceToHost));
-        if (ov == PART_OVERFLOW_ZERO_KEY) return MDBG_OK;         // (no number of buckets helps: the one-table path)
-        if (ov) { run.extra_bits += 2; continue; }
+        MDBG_TRY(run.read_totals(&pl->n_keys, nullptr, &overflowed, &hand_back));
+        if (hand_back) return MDBG_OK;
+        if (overflowed) { run.extra_bits += 2; continue; }
         pl->attempt = attempt;
         break;
     }
@@ -1177,76 +1178,60 @@ int part_local_keys(mdbg_ctx *ctx, const mdbg_minimizers *reads, uint32_t k, Par
     MDBG_TRY(pl->lo.alloc(ctx, D)); MDBG_TRY(pl->hi.alloc(ctx, D)); MDBG_TRY(pl->cnt.alloc(ctx, D)); MDBG_TRY(pl->rep.alloc(ctx, D));
     {
         LaunchTimer timer(ctx, "shard_rows");
-        hipLaunchKernelGGL(gather_bucket_keys_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.pos, run.stride, run.n_kept.p,
+        hipLaunchKernelGGL(gather_bucket_keys_kernel, dim3((unsigned)run.n_buckets), dim3(256), 0, ctx->stream, run.keys(), run.kcnt.p, run.rec.pos, run.rec.stride, run.n_kept.p,
                            run.row_of.p, pl->lo.p, pl->hi.p, pl->cnt.p, pl->rep.p);
     }
     MDBG_HIP_CHECK(ctx, hipGetLastError());
     run.record_info(pl->attempt, run.I);
     // the free record buffer and the per-instance count array are not needed any more; the records, their bucket offsets and row_of are
-    run.buf[run.cur ^ 1] = RecBufs();
+    run.rec.buf[run.rec.cur ^ 1] = RecBufs();
     run.kcnt.release();
     *out = pl.release();
     *done = true;
     return MDBG_OK;
 }
 
-template <uint32_t C>
-static void launch_bucket_apply(mdbg_ctx *ctx, PartLocal *pl, const uint32_t *gcount, uint32_t clip, uint8_t *cnt8) {
-    PartRun &run = pl->run;
-    hipLaunchKernelGGL(bucket_apply_kernel<C>, dim3((unsigned)run.n_buckets), dim3(BC_NT), 0, ctx->stream, run.records(), run.pos, run.stride, run.row_of.p, pl->lo.p, pl->hi.p,
-                       gcount, clip, cnt8);
-}
-
 // gcount[i]: the global count of local key i; listed[i]: this rank lists the key (and it is solid)
 int part_local_finish(mdbg_ctx *ctx, PartLocal *pl, const uint32_t *gcount, const uint32_t *listed, uint32_t min_abundance, mdbg_table **out) {
     PartRun &run = pl->run;
     const mdbg_minimizers *reads = run.reads;
-    const uint32_t k = run.k, n_reads = run.n_reads;
+    const uint32_t k = run.k;
     const uint64_t M = run.M, D = pl->n_keys;
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const uint32_t m_star = rescue_m_star();
     const uint32_t clip = 2u * m_star + 1u;
     const bool do_rescue = min_abundance <= 1 && clip <= 254u;
-    DevBuf<uint64_t> lpos, resc_pos;
+    DevBuf<uint64_t> lpos;
     DevBuf<uint8_t> cnt8;
-    DevBuf<uint32_t> resc_cnt;
+    PartRescue resc;
     MDBG_TRY(lpos.alloc(ctx, D + 1));
     MDBG_TRY(exclusive_scan_u32(ctx, listed, lpos.p, D));
-    uint64_t n_solid = 0, n_resc = 0;
+    uint64_t n_solid = 0;
     MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&n_solid, lpos.p + D, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (do_rescue) {
         MDBG_TRY(cnt8.alloc(ctx, M));
         MDBG_HIP_CHECK(ctx, hipMemsetAsync(cnt8.p, 0, M, ctx->stream));
         {
             LaunchTimer timer(ctx, "kminmer_insert");
-            if (run.lds_slots == 256) launch_bucket_apply<256>(ctx, pl, gcount, clip, cnt8.p);
-            else if (run.lds_slots == 1024) launch_bucket_apply<1024>(ctx, pl, gcount, clip, cnt8.p);
-            else launch_bucket_apply<2048>(ctx, pl, gcount, clip, cnt8.p);
+            with_lds_slots(run.bp.lds_slots, [&](auto slots) {
+                hipLaunchKernelGGL(bucket_apply_kernel<decltype(slots)::value>, dim3((unsigned)run.n_buckets), dim3(BC_NT), 0, ctx->stream, run.records(), run.rec.pos, run.rec.stride,
+                                   run.row_of.p, pl->lo.p, pl->hi.p, gcount, clip, cnt8.p);
+            });
         }
-        MDBG_TRY(resc_cnt.alloc(ctx, n_reads));
-        MDBG_TRY(resc_pos.alloc(ctx, (size_t)n_reads + 1));
-        {
-            LaunchTimer timer(ctx, "kminmer_rescue");
-            hipLaunchKernelGGL(rescue_count_p_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, ctx->stream, reads->d_off.p, n_reads, k, cnt8.p, m_star, resc_cnt.p, table_priority(ctx));
-        }
-        MDBG_TRY(exclusive_scan_u32(ctx, resc_cnt.p, resc_pos.p, n_reads));
-        MDBG_HIP_CHECK(ctx, hipMemcpyAsync(&n_resc, resc_pos.p + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MDBG_TRY(plan_part_rescue(ctx, reads, k, cnt8.p, m_star, resc));
     }
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::unique_ptr<mdbg_table> t(new mdbg_table());
     t->k = k;
     t->n_solid = n_solid;
-    t->st_minimizers = M; t->st_instances = pl->n_inst; t->st_keys = D; t->st_slots = run.n_buckets * run.lds_slots;
-    MDBG_TRY(alloc_rows(ctx, t.get(), n_solid + n_resc, true));
+    t->st_minimizers = M; t->st_instances = pl->n_inst; t->st_keys = D; t->st_slots = run.n_buckets * run.bp.lds_slots;
+    MDBG_TRY(alloc_rows(ctx, t.get(), n_solid + resc.total, true));
     RowOut ro{t->d_lo.p, t->d_hi.p, t->d_ab.p, t->d_vec.p, k};
     {
         LaunchTimer timer(ctx, "kminmer_emit");
         if (D) hipLaunchKernelGGL(emit_listed_rows_kernel, dim3(grid_for(D, 256)), dim3(256), 0, ctx->stream, pl->lo.p, pl->hi.p, gcount, pl->rep.p, listed, lpos.p, D,
                                   reads->d_min.p, ro);
-        if (n_resc) {
-            const unsigned blocks = grid_for((uint64_t)n_reads * 16, 256, (unsigned)ctx->n_cu * 16u);
-            hipLaunchKernelGGL(emit_rescued_p_kernel, dim3(blocks), dim3(256), 0, ctx->stream, reads->d_off.p, reads->d_min.p, n_reads, k, cnt8.p, resc_cnt.p, resc_pos.p, ro, n_solid, table_priority(ctx));
-        }
+        launch_emit_part_rescued(ctx, reads, k, cnt8.p, resc, ro, n_solid);
     }
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return set_error(ctx, MDBG_EHIP, "sharded first pass (partitioned) failed: %s", hipGetErrorString(e));
@@ -1255,55 +1240,31 @@ int part_local_finish(mdbg_ctx *ctx, PartLocal *pl, const uint32_t *gcount, cons
 }
 
 // ---- the owner's side: n_recv rows [lo, hi, count] -> one reply per row (global count | bit 63 = this row's sender lists the key) -------
-template <uint32_t C>
-static void launch_owner_buckets(mdbg_ctx *ctx, uint64_t n_buckets, RecView in, const uint64_t *pos, uint32_t stride, const uint64_t *rows, uint64_t *reply, uint32_t *overflow) {
-    hipLaunchKernelGGL(owner_bucket_kernel<C>, dim3((unsigned)n_buckets), dim3(BC_NT), 0, ctx->stream, in, pos, stride, rows, reply, overflow);
-}
-
 int part_owner_reduce(mdbg_ctx *ctx, const uint64_t *d_rows, uint64_t n_recv, uint64_t *d_reply, bool *done) {
     *done = false;
     if (n_recv < (1ull << 17) || n_recv >= (1ull << 32)) return MDBG_OK;
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const uint32_t lds_slots = ctx->part_lds_slots == 256 || ctx->part_lds_slots == 2048 ? ctx->part_lds_slots : 1024u;
     // every bucket must hold its rows' distinct keys: sized for the ROWS (a key arrives once from every rank that saw it, so this is generous)
-    uint32_t bits = 0;
-    while ((double)(1ull << bits) < (double)n_recv / (0.78 * lds_slots) && bits <= PART_MAX_BITS) bits++;
-    if (bits > PART_MAX_BITS) return MDBG_OK;
-    const uint32_t n_levels = bits <= 8 ? 1u : (bits + 7u) / 8u;
+    const BucketPlan bp = owner_plan(n_recv, ctx->part_lds_slots);
+    if (bp.too_many_buckets()) return MDBG_OK;
     const SplitForm form = split_form(ctx);
-    const uint32_t tile = form.tile;
     RecBufs buf[2];
     MDBG_TRY(buf[0].ensure(ctx, n_recv));
     MDBG_TRY(buf[1].ensure(ctx, n_recv));
     DevBuf<uint32_t> hist, overflow;
     DevBuf<uint64_t> place[3];
+    LevelBufs rec{buf, hist, place};
     MDBG_TRY(overflow.alloc(ctx, 1));
     MDBG_HIP_CHECK(ctx, hipMemsetAsync(overflow.p, 0, 4, ctx->stream));
     LaunchTimer timer(ctx, "shard_reduce");
-    hipLaunchKernelGGL(rows_to_records_kernel, dim3(grid_for(n_recv, 256)), dim3(256), 0, ctx->stream, d_rows, n_recv, buf[0].view());
-    uint32_t cur = 0, left = bits, used = 0, prev_bps = 1;
-    uint64_t n_seg = 1;
-    for (uint32_t l = 0; l < n_levels; l++) {
-        const uint32_t b = (left + (n_levels - l) - 1) / (n_levels - l);
-        SplitArgs d{};
-        d.in = buf[cur].view();
-        d.n_min = n_recv;                                          // level 1: one segment, the rows as they arrived
-        d.seg_pos = l ? place[l - 1].p : nullptr; d.seg_stride = prev_bps;
-        d.blocks_per_seg = deeper_blocks_per_seg(n_recv, n_seg, tile);
-        d.ways = 1u << b; d.shift = b ? 64u - used - b : 0u; d.tile = tile;
-        const uint64_t entries = n_seg * d.ways * d.blocks_per_seg;
-        MDBG_TRY(hist.alloc(ctx, entries));
-        MDBG_TRY(place[l].alloc(ctx, entries + 1));
-        const unsigned grid = level_grid(n_seg, d.blocks_per_seg);
-        launch_split_hist(ctx, false, form, grid, d, hist.p);
-        MDBG_TRY(exclusive_scan_u32(ctx, hist.p, place[l].p, entries));
-        launch_split_scatter(ctx, false, form, grid, d, place[l].p, buf[cur ^ 1].view());
-        cur ^= 1; used += b; left -= b; n_seg <<= b; prev_bps = d.blocks_per_seg;
-    }
-    const uint64_t n_buckets = 1ull << bits;
-    if (lds_slots == 256) launch_owner_buckets<256>(ctx, n_buckets, buf[cur].view(), place[n_levels - 1].p, prev_bps, d_rows, d_reply, overflow.p);
-    else if (lds_slots == 1024) launch_owner_buckets<1024>(ctx, n_buckets, buf[cur].view(), place[n_levels - 1].p, prev_bps, d_rows, d_reply, overflow.p);
-    else launch_owner_buckets<2048>(ctx, n_buckets, buf[cur].view(), place[n_levels - 1].p, prev_bps, d_rows, d_reply, overflow.p);
+    hipLaunchKernelGGL(rows_to_records_kernel, dim3(grid_for(n_recv, 256)), dim3(256), 0, ctx->stream, d_rows, n_recv, rec.buf[0].view());
+    // Priority 0, not table_priority(ctx): the owner's split launches have never been raised, and whether they should be is a measurement
+    // of its own.  No interval per launch: the one "shard_reduce" object covers every launch here, the scans included.
+    MDBG_TRY(run_record_levels<NoInterval>(ctx, form, rec, n_recv, bp, 0, 0u, nullptr));
+    with_lds_slots(bp.lds_slots, [&](auto slots) {
+        hipLaunchKernelGGL(owner_bucket_kernel<decltype(slots)::value>, dim3(1u << bp.bucket_bits), dim3(BC_NT), 0, ctx->stream, rec.buf[rec.cur].view(), rec.pos, rec.stride, d_rows,
+                           d_reply, overflow.p);
+    });
     MDBG_HIP_CHECK(ctx, hipGetLastError());
     uint32_t ov = 0;
     MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &ov, overflow.p, 4, hipMemcpyDeviceToHost));

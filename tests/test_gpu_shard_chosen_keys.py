@@ -9,8 +9,8 @@ Which form answered is read from the launch timers: every LaunchTimer object nam
 timed region; the one-table form one per table build plus the reply; a bucket attempt that handed over is the sum of both.  So
 "== 1" where the bucket form must answer, "> 1" where it must not, and nothing finer.
 
-The plan of the bucket form (part_owner_reduce): bits = the least b with 2^b >= n_recv / (0.78 * slots), one split level up to 8 bits, two
-up to 16.  For the sizes used here:
+The plan of the bucket form (owner_plan, csrc/partition_plan.hpp, whose host test pins the rows below): bits = the least b with
+2^b >= n_recv / (0.78 * slots), one split level up to 8 bits, two up to 16.  For the sizes used here:
     n_recv = 2^17      slots 1024: 131072 / 798.72 = 164.1 -> 8 bits, one level     slots 2048: 82.1 -> 7 bits, one level
                        slots  256: 131072 / 199.68 = 656.4 -> 10 bits, two levels (5 + 5)
     n_recv = 300 000   slots 1024: 375.6 -> 9 bits, two levels (5 + 4)   slots 2048: 187.8 -> 8 bits, one   slots 256: 1502.4 -> 11 bits, two
