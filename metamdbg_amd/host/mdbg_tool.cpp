@@ -46,6 +46,7 @@
 #include "../../include/mdbg_hip.h"
 #include "device_text_feed.hpp"
 #include "fastx.hpp"
+#include "graph_plan.hpp"
 #include "hostfeed.hpp"
 #include "ordered_place.hpp"
 #include "records.hpp"
@@ -1092,59 +1093,21 @@ int run_read_selection(int argc, char **argv, bool asmStep = false) {
 }
 
 // ---- graph ---------------------------------------------------------------------------------------------------------
-// a vector whose resize() leaves new elements uninitialised (they are overwritten at once: 0.8 GB of zero-filling is 0.1 s)
-template <typename T>
-struct DefaultInit : std::allocator<T> {
-    template <typename U> struct rebind { using other = DefaultInit<U>; };
-    using std::allocator<T>::allocator;
-    template <typename U> void construct(U *p) noexcept(std::is_nothrow_default_constructible<U>::value) { ::new ((void *)p) U; }
-    template <typename U, typename... A> void construct(U *p, A &&...args) { ::new ((void *)p) U(std::forward<A>(args)...); }
-};
-using U32Vec = std::vector<uint32_t, DefaultInit<uint32_t>>;
-
-// "u32 n; u8 circ; u32 m[n]" records (read_data_corrected.txt, unitig_data.txt) -> CSR.  One walk over the record headers for the
-// offsets, then the values are copied by a few threads (a 50 Gbp read set is 0.8 GB of these records: 0.45 s of a 0.75 s `graph` when
-// it was one loop over a zero-filled copy of the file).
-template <typename Vec>
-void parse_minimizer_reads(const uint8_t *raw, size_t size, Vec &mins, std::vector<uint64_t> &offs,
-                           std::vector<uint8_t> *circular = nullptr, int threads = 1) {
+// "u32 n; u8 circ; u32 m[n]" records (unitig_data.txt) -> CSR, in one walk.  (read_data_corrected.txt, a thousand times the size, is never
+// parsed here: host/records.hpp indexes it and its bytes travel as they are.)
+void parse_minimizer_reads(const std::vector<uint8_t> &raw, std::vector<uint32_t> &mins, std::vector<uint64_t> &offs, std::vector<uint8_t> &circular) {
     offs.assign(1, 0);
-    offs.reserve(size / 64 + 16);
-    std::vector<size_t> at;                       // byte position of every record's values
-    at.reserve(size / 64 + 16);
-    size_t o = 0;
-    uint64_t total = 0;
-    while (o + 5 <= size) {
+    for (size_t o = 0; o + 5 <= raw.size();) {
         uint32_t n;
-        memcpy(&n, raw + o, 4);
-        if (circular) circular->push_back(raw[o + 4]);
+        memcpy(&n, raw.data() + o, 4);
+        circular.push_back(raw[o + 4]);
         o += 5;
-        if (o + (size_t)n * 4 > size) die("truncated minimizer read file");
-        at.push_back(o);
+        if (o + (size_t)n * 4 > raw.size()) die("truncated minimizer read file");
+        mins.resize(offs.back() + n);
+        if (n) memcpy(mins.data() + offs.back(), raw.data() + o, (size_t)n * 4);
         o += (size_t)n * 4;
-        total += n;
-        offs.push_back(total);
+        offs.push_back(mins.size());
     }
-    const size_t base = mins.size();
-    mins.resize(base + total);
-    const size_t nRec = at.size();
-    const unsigned nThr = (unsigned)std::max(1, std::min(threads, 16));
-    auto copy = [&](unsigned t) {
-        for (size_t r = nRec * t / nThr, r1 = nRec * (t + 1) / nThr; r < r1; r++) {
-            const size_t k = (size_t)(offs[r + 1] - offs[r]);
-            if (k) memcpy(mins.data() + base + offs[r], raw + at[r], k * 4);
-        }
-    };
-    if (nThr == 1 || total < (1u << 20)) { for (unsigned t = 0; t < nThr; t++) copy(t); }
-    else {
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < nThr; t++) pool.emplace_back(copy, t);
-        for (auto &th : pool) th.join();
-    }
-}
-void parse_minimizer_reads(const std::vector<uint8_t> &raw, std::vector<uint32_t> &mins, std::vector<uint64_t> &offs,
-                           std::vector<uint8_t> *circular = nullptr) {
-    parse_minimizer_reads(raw.data(), raw.size(), mins, offs, circular, 1);
 }
 
 // a whole file mapped read-only (no copy, no zero-fill)
@@ -1259,17 +1222,35 @@ void load_prev_inputs(const std::string &dir, PrevInputs &in) {
     }
     std::ifstream probe(dir + "/unitig_data.txt", std::ios::binary);
     if (probe) {
-        parse_minimizer_reads(read_file(dir + "/unitig_data.txt", true), in.unitigMins, in.unitigOffs, &in.unitigCirc);
+        parse_minimizer_reads(read_file(dir + "/unitig_data.txt", true), in.unitigMins, in.unitigOffs, in.unitigCirc);
         in.hasUnitigs = true;
     }
 }
 
-struct RankTable {
-    std::vector<uint8_t> rec;
-    std::vector<uint32_t> vec;
+// What the job says about a table -- a whole one, a rank's or a piece's share of one, or the sum over the shares.
+struct TableTotals {
     uint64_t n = 0, nSolid = 0;
-    int hasVec = 0;
-    uint64_t sums[4] = {0, 0, 0, 0};  // mdbg_table_checksum of the share: [0] is the "Checksum kminmer abundance" the reference logs
+    int hasVec = 0;                   // summed: any share's view (a share without reads still reports the table's kind, but do not rely on it)
+    uint64_t sums[4] = {0, 0, 0, 0};  // mdbg_table_checksum: [0] is the "Checksum kminmer abundance" the reference logs
+    static TableTotals of(mdbg_ctx *ctx, mdbg_table *table) {
+        TableTotals t;
+        mdbg_table_info(table, nullptr, &t.n, &t.nSolid, &t.hasVec);
+        check_on(ctx, mdbg_table_checksum(ctx, table, t.sums), "mdbg_table_checksum");
+        return t;
+    }
+    void add(const TableTotals &o) {
+        n += o.n; nSolid += o.nSolid; hasVec |= o.hasVec;
+        for (int i = 0; i < 4; i++) sums[i] += o.sums[i];
+    }
+    // record count, solid count and the four order-independent sums: equal for the union of the shares and the table of the whole set
+    bool same_table(const TableTotals &o) const {
+        return n == o.n && nSolid == o.nSolid && sums[0] == o.sums[0] && sums[1] == o.sums[1] && sums[2] == o.sums[2] && sums[3] == o.sums[3];
+    }
+};
+
+struct RankTable {
+    TableTotals totals;
+    std::vector<uint8_t> rec, vec;   // the share's 20-byte records and its k-min-mer vectors (k u32 a row), as they go to the files
     std::string smallContigs;        // records for smallContigs_k<k>.bin (the rank that holds unitig_data.txt)
 };
 
@@ -1318,40 +1299,50 @@ struct PrevOnDevice {
 
 // Where the reads of read_data_corrected.txt are: the mapped file itself (the bytes path: any range of whole records is a file of its own --
 // record r of the range starts at byte 5 r + 4 off[r] of the range -- so every rank, piece or self-check takes its reads straight from the
-// file's bytes) or, with MDBG_TOOL_PARSE_ON_HOST, the array a host parse made.
+// file's bytes).  asmStep's second command, which finds the reads on the device, has no file: no read comes from here then.
 struct ReadSource {
-    const uint8_t *raw = nullptr;                 // the mapped file, or null
-    const U32Vec *mins = nullptr;                 // the parsed values (raw == null)
-    const std::vector<uint64_t> *offs = nullptr;  // minimizers before each read, n_reads + 1
+    std::unique_ptr<MappedFile> file;             // read_data_corrected.txt (null: the reads are resident)
+    std::vector<uint64_t> offs{0};                // minimizers before each read, n_reads + 1
     int threads = 4;
-    uint64_t n_minimizers() const { return offs->back(); }
+    size_t n_reads() const { return offs.size() - 1; }
+    uint64_t n_minimizers() const { return offs.back(); }
 };
 
 mdbg_minimizers *upload_read_range(mdbg_ctx *ctx, const ReadSource &src, size_t r0, size_t r1) {
-    const std::vector<uint64_t> &offs = *src.offs;
-    std::vector<uint64_t> rel(offs.begin() + (long)r0, offs.begin() + (long)r1 + 1);
-    mdbg_minimizers *reads = nullptr;
-    if (!src.raw) {
-        check_on(ctx, mdbg_minimizers_from_host(ctx, src.mins->data(), rel.data(), (uint32_t)(r1 - r0), &reads), "mdbg_minimizers_from_host");
-        return reads;
-    }
+    std::vector<uint64_t> rel(src.offs.begin() + (long)r0, src.offs.begin() + (long)r1 + 1);
     const uint64_t base = rel[0];
     for (uint64_t &o : rel) o -= base;
-    const size_t b0 = 5 * r0 + 4 * (size_t)offs[r0], b1 = 5 * r1 + 4 * (size_t)offs[r1];
-    mdbg_bytes *rb = upload_file_bytes(ctx, src.raw + b0, b1 - b0, src.threads);
+    const std::pair<size_t, size_t> b = graph_plan::byte_range(src.offs, r0, r1);
+    mdbg_bytes *rb = upload_file_bytes(ctx, src.file->p + b.first, b.second - b.first, src.threads);
+    mdbg_minimizers *reads = nullptr;
     check_on(ctx, mdbg_minimizers_from_record_bytes(ctx, rb, rel.data(), (uint32_t)(r1 - r0), nullptr, &reads), "mdbg_minimizers_from_record_bytes");
     mdbg_bytes_free(rb);
     return reads;
+}
+
+// Where the rows of a finished table go.  A sink gets the table and the number of rows already in the files in front of it.
+using TableSink = std::function<void(mdbg_ctx *, mdbg_table *, uint64_t rowBase)>;
+struct RowsTo {
+    enum Where { Files, Host, Nowhere } where;   // through `sink`; into the RankTable's vectors; dropped (the self-check wants the totals only)
+    TableSink sink;
+};
+
+// The pass above firstK of one read range (and, where given, the unitigs) against the previous table, on one context: the range's own table.
+mdbg_table *local_pass(mdbg_ctx *ctx, const Parameters &P, mdbg_minimizers *reads, mdbg_minimizers *unitigs, mdbg_table *prev) {
+    const uint32_t k = (uint32_t)P.kminmerSize;
+    mdbg_table *local = nullptr;
+    if (k == P.firstK + 1) check_on(ctx, mdbg_kminmer_count_refined(ctx, reads, unitigs, k, prev, &local), "mdbg_kminmer_count_refined");
+    else check_on(ctx, mdbg_kminmer_index(ctx, reads, unitigs, k, prev, &local), "mdbg_kminmer_index");
+    return local;
 }
 
 // One rank's part of `graph`: reads [r0, r1) of read_data_corrected.txt on `ctx`; with a communicator the table is built
 // across the ranks (include/mdbg_hip.h "the exchange inside the library") and `out` is this rank's share of it.
 // unitig_data.txt -- sequences, not reads -- goes to rank 0 only.
 void graph_rank(mdbg_ctx *ctx, mdbg_comm *comm, int rank, const Parameters &P, const Args &a, const ReadSource &src,
-                size_t r0, size_t r1, const PrevInputs &in, RankTable &out, bool rowsToHost = true,
-                const std::function<void(mdbg_ctx *, mdbg_table *)> &sink = nullptr, mdbg_minimizers *resident = nullptr) {
+                size_t r0, size_t r1, const PrevInputs &in, RankTable &out, const RowsTo &rows, mdbg_minimizers *resident = nullptr) {
     const uint32_t k = (uint32_t)P.kminmerSize;
-    mdbg_minimizers *reads = resident;          // asmStep: the reads are on the device already (freed here like an uploaded set)
+    mdbg_minimizers *reads = resident;          // the reads are on the device already (freed here like an uploaded set)
     if (!reads) reads = upload_read_range(ctx, src, r0, r1);
     mdbg_table *table = nullptr;
     if (a.firstPass) {
@@ -1361,11 +1352,7 @@ void graph_rank(mdbg_ctx *ctx, mdbg_comm *comm, int rank, const Parameters &P, c
         PrevOnDevice dev;
         dev.build(ctx, P, in, rank == 0, out.smallContigs, a.threads);
         if (rank == 0) g_trace.mark("graph: the previous table on the device");
-        mdbg_table *prev = dev.prev;
-        mdbg_minimizers *unitigs = dev.unitigs;
-        mdbg_table *local = nullptr;
-        if (k == P.firstK + 1) check_on(ctx, mdbg_kminmer_count_refined(ctx, reads, unitigs, k, prev, &local), "mdbg_kminmer_count_refined");
-        else check_on(ctx, mdbg_kminmer_index(ctx, reads, unitigs, k, prev, &local), "mdbg_kminmer_index");
+        mdbg_table *local = local_pass(ctx, P, reads, dev.unitigs, dev.prev);
         if (comm) {
             // the ranks agree on who lists a key several of them found (include/mdbg_hip.h, "Sharded k > firstK")
             mdbg_shard *sh = nullptr;
@@ -1379,14 +1366,14 @@ void graph_rank(mdbg_ctx *ctx, mdbg_comm *comm, int rank, const Parameters &P, c
         } else table = local;
         dev.free();
     }
-    mdbg_table_info(table, nullptr, &out.n, &out.nSolid, &out.hasVec);
-    check_on(ctx, mdbg_table_checksum(ctx, table, out.sums), "mdbg_table_checksum");
+    out.totals = TableTotals::of(ctx, table);
+    const TableTotals &t = out.totals;
     if (rank == 0) g_trace.mark("graph: the pass done, the table on the device");
-    if (sink) sink(ctx, table);            // the rows go straight to their files (one rank: run_graph)
-    else if (rowsToHost) {
-        out.rec.resize(out.n * 20);
-        out.vec.resize(out.hasVec ? out.n * k : 0);
-        check_on(ctx, mdbg_table_to_host(ctx, table, out.rec.data(), out.hasVec ? out.vec.data() : nullptr), "mdbg_table_to_host");
+    if (rows.where == RowsTo::Files) rows.sink(ctx, table, 0);
+    else if (rows.where == RowsTo::Host) {
+        out.rec.resize(t.n * 20);
+        out.vec.resize(t.hasVec ? t.n * k * 4 : 0);
+        check_on(ctx, mdbg_table_to_host(ctx, table, out.rec.data(), t.hasVec ? (uint32_t *)out.vec.data() : nullptr), "mdbg_table_to_host");
     }
     mdbg_table_free(table);
     mdbg_minimizers_free(reads);
@@ -1398,7 +1385,7 @@ void graph_rank(mdbg_ctx *ctx, mdbg_comm *comm, int rank, const Parameters &P, c
 // 20 Gbp: 2.7 GB of rows, 4.2 GB of files -- 1.2 s of a 1.65 s `graph` when they went through pageable vectors and one writing thread.
 // (rowBase > 0: the table is the next share of a pass made in pieces -- its rows follow the rowBase rows already in the files)
 void stream_table_to_files(mdbg_ctx *ctx, mdbg_table *table, uint32_t k, const std::vector<std::string> &recFiles, const std::string &vecFile,
-                           uint64_t rowBase = 0, bool firstShare = true) {
+                           uint64_t rowBase) {
     uint64_t n = 0;
     int hasVec = 0;
     mdbg_table_info(table, nullptr, &n, nullptr, &hasVec);
@@ -1407,16 +1394,13 @@ void stream_table_to_files(mdbg_ctx *ctx, mdbg_table *table, uint32_t k, const s
     // The files of the k before are overwritten IN PLACE and cut to their new length at the end (ftruncate below): truncating a 300 MB
     // file of the page cache first gives its pages back one by one only for the writes to ask for them again (0.03 - 0.05 s a file at
     // configs[2]'s size).  What the next stage finds is the same: these bytes, this length.
-    for (const std::string &f : recFiles) {
+    auto opened = [](const std::string &f) {
         const int fd = open(f.c_str(), O_CREAT | O_WRONLY, 0644);
         if (fd < 0) die("cannot write " + f);
-        recFd.push_back(fd);
-    }
-    if (vec) {
-        const int fd = open(vecFile.c_str(), O_CREAT | O_WRONLY, 0644);
-        if (fd < 0) die("cannot write " + vecFile);
-        vecFd.push_back(fd);
-    }
+        return fd;
+    };
+    for (const std::string &f : recFiles) recFd.push_back(opened(f));
+    if (vec) vecFd.push_back(opened(vecFile));
     const uint64_t piece = (uint64_t)1 << 21;
     struct Buf { uint8_t *rec = nullptr; uint32_t *vec = nullptr; };
     Buf buf[2];
@@ -1429,8 +1413,7 @@ void stream_table_to_files(mdbg_ctx *ctx, mdbg_table *table, uint32_t k, const s
     std::vector<std::thread> writers;           // of the piece before the one coming down
     for (uint64_t first = 0, i = 0; first < n; first += piece, i++) {
         const uint64_t cnt = std::min(piece, n - first);
-        Buf &b = buf[i & 1];
-        if (i >= 2) { /* buf[i & 1] was written out two pieces ago: its writers were joined below */ }
+        Buf &b = buf[i & 1];                     // written out two pieces ago: its writers were joined below
         check_on(ctx, mdbg_table_to_host_range(ctx, table, first, cnt, b.rec, vec ? b.vec : nullptr), "mdbg_table_to_host_range");
         for (auto &t : writers) t.join();        // the other buffer is free again, this one is full
         writers.clear();
@@ -1460,10 +1443,9 @@ void stream_table_to_files(mdbg_ctx *ctx, mdbg_table *table, uint32_t k, const s
 // graph/CreateMdbg.hpp:3714-3851).  The minimizers of all the pieces stay on the device until the last share is written (4 bytes each).
 // cuts: read indexes, cuts[p] .. cuts[p + 1] = piece p.
 void graph_pieces(mdbg_ctx *ctx, const Parameters &P, const Args &a, const ReadSource &src, const std::vector<size_t> &cuts,
-                  const PrevInputs &in, RankTable &out, const std::function<void(mdbg_ctx *, mdbg_table *, uint64_t, bool)> &sink) {
+                  const PrevInputs &in, RankTable &out, const TableSink &sink) {
     const uint32_t k = (uint32_t)P.kminmerSize;
     const uint32_t n = (uint32_t)(cuts.size() - 1);
-    if (n > 64) die("graph: more than 64 pieces (" + std::to_string(n) + "): raise MDBG_TOOL_MAX_MINIMIZERS");
     // What this way of running the pass keeps on the device AT ONCE (round-4 ADVICE): every piece's minimizers (4 bytes each) and, until the
     // last share is written, every piece's shard state -- the instance records of the partitioned local pass (20 bytes per k-min-mer instance)
     // or the local table and its instance slots (up to 36) -- so about 40 bytes per minimizer of the whole read set.  A read set that needs
@@ -1489,28 +1471,22 @@ void graph_pieces(mdbg_ctx *ctx, const Parameters &P, const Args &a, const ReadS
         std::vector<uint64_t> c(64, 0);
         if (a.firstPass) check_on(ctx, mdbg_shard_begin(ctx, reads[p], k, n, &shards[p], &dRows[p], c.data()), "mdbg_shard_begin");
         else {
-            mdbg_minimizers *unitigs = p == 0 ? dev.unitigs : nullptr;      // sequences, not reads: with the first piece
-            if (k == P.firstK + 1) check_on(ctx, mdbg_kminmer_count_refined(ctx, reads[p], unitigs, k, dev.prev, &local[p]), "mdbg_kminmer_count_refined");
-            else check_on(ctx, mdbg_kminmer_index(ctx, reads[p], unitigs, k, dev.prev, &local[p]), "mdbg_kminmer_index");
+            local[p] = local_pass(ctx, P, reads[p], p == 0 ? dev.unitigs : nullptr, dev.prev);      // (the unitigs -- sequences, not reads -- with the first piece)
             check_on(ctx, mdbg_shard_from_table(ctx, local[p], n, &shards[p], &dRows[p], c.data()), "mdbg_shard_from_table");
         }
         for (uint32_t d = 0; d < n; d++) counts[(size_t)p * n + d] = c[d];
     }
     dev.free();
     check_on(ctx, mdbg_shard_exchange_local(ctx, shards.data(), n, dRows.data(), counts.data(), dReplies.data()), "mdbg_shard_exchange_local");
-    uint64_t rowBase = 0;
+    // The shares go to the files one behind the other: a share's rowBase is the rows of the shares before it, so it only grows -- which is what
+    // lets the sink cut the files to (rowBase + rows) after every share and still leave them at the whole table's length.
     for (uint32_t p = 0; p < n; p++) {
         mdbg_table *share = nullptr;
         if (a.firstPass) check_on(ctx, mdbg_shard_finish(ctx, shards[p], dReplies[p], a.minAbundance, &share), "mdbg_shard_finish");
         else check_on(ctx, mdbg_shard_keep(ctx, shards[p], dReplies[p], &share), "mdbg_shard_keep");
-        uint64_t rows = 0, solid = 0, sums[4] = {0, 0, 0, 0};
-        int hasVec = 0;
-        mdbg_table_info(share, nullptr, &rows, &solid, &hasVec);
-        check_on(ctx, mdbg_table_checksum(ctx, share, sums), "mdbg_table_checksum");
-        out.n += rows; out.nSolid += solid; out.hasVec |= hasVec;
-        for (int i = 0; i < 4; i++) out.sums[i] += sums[i];
-        sink(ctx, share, rowBase, p == 0);
-        rowBase += rows;
+        const uint64_t rowBase = out.totals.n;
+        out.totals.add(TableTotals::of(ctx, share));
+        sink(ctx, share, rowBase);
         mdbg_table_free(share);
         mdbg_shard_free(shards[p]);
         if (local[p]) mdbg_table_free(local[p]);
@@ -1524,169 +1500,180 @@ int run_graph(int argc, char **argv) {
     graph_main(a, a.pos[0], nullptr);
 }
 
-// `resident`: the reads of read_data_corrected.txt as asmStep left them on the device of g_ctx (null: the file is read)
-[[noreturn]] void graph_main(Args a, const std::string &dir, mdbg_minimizers *resident) {
+// ---- the stages of graph_main (below them), in the order it goes through them ----------------------------------------
+struct GraphJob {
+    Args a;
+    std::string dir;
     Parameters P;
-    P.load(dir + "/parameters.gz");
+    uint32_t k = 0;
+    int G = 1;                           // ranks
+    bool sharded = false;                // one context and one host thread per rank, the exchange inside the library
+    uint64_t maxMins = 3500000000ull;    // more minimizers than one call of the library takes: the pass in pieces (MDBG_TOOL_MAX_MINIMIZERS: the most one piece may hold)
+    mdbg_minimizers *resident = nullptr; // the reads as asmStep left them on the device of g_ctx (null: the file is read)
+};
+
+// Owns the shape of the job: G, sharded or not, the piece limit, and whether asmStep's resident reads serve or are dropped.
+GraphJob settle_job(const Args &a, const std::string &dir, mdbg_minimizers *resident) {
+    GraphJob J{a, dir};
+    J.P.load(dir + "/parameters.gz");
     g_log.open(dir);
-    const uint32_t k = (uint32_t)P.kminmerSize;
-    g_log.line("mdbg_tool graph (MI355X) k = " + std::to_string(k) + (a.firstPass ? " --firstpass" : "") +
+    J.k = (uint32_t)J.P.kminmerSize;
+    g_log.line("mdbg_tool graph (MI355X) k = " + std::to_string(J.k) + (a.firstPass ? " --firstpass" : "") +
                (a.gpus > 1 ? " --gpus " + std::to_string(a.gpus) : ""));
     // --gpus G: contiguous read ranges, one context (device r, one host thread) per rank, the exchange inside the library over
     // RCCL.  MDBG_TOOL_SHARDED=1 takes the same path with one rank (a communicator of one: what a one-GPU box can exercise).
-    const int G = std::max(1, a.gpus);
-    const bool sharded = G > 1 || getenv("MDBG_TOOL_SHARDED") != nullptr;
-    uint64_t maxMins = 3500000000ull;    // more minimizers than one call of the library takes: the pass in pieces (MDBG_TOOL_MAX_MINIMIZERS: the most one piece may hold)
-    if (const char *e = getenv("MDBG_TOOL_MAX_MINIMIZERS")) maxMins = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    J.G = std::max(1, a.gpus);
+    J.sharded = J.G > 1 || getenv("MDBG_TOOL_SHARDED") != nullptr;
+    if (const char *e = getenv("MDBG_TOOL_MAX_MINIMIZERS")) J.maxMins = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
     if (resident) {                      // only the plain one-rank pass takes the reads where they are; anything else reads the file it has just written
         uint64_t total = 0;
         mdbg_minimizers_info(resident, nullptr, &total);
-        if (sharded || total > maxMins) { mdbg_minimizers_free(resident); resident = nullptr; }
+        if (J.sharded || total > J.maxMins) { mdbg_minimizers_free(resident); resident = nullptr; }
     }
+    J.resident = resident;
+    return J;
+}
+
+// Owns read_data_corrected.txt.  It is not parsed into an array: its record headers are walked by several threads (host/records.hpp: exact)
+// while the context comes up, its bytes then travel as they are and the records are taken apart on the device
+// (mdbg_minimizers_from_record_bytes) -- by the one rank, by every rank of a --gpus G job and by every piece of a pass in pieces, each for its
+// own range of records.  Resident reads: no file, no read.
+void open_read_source(const GraphJob &J, ReadSource &src) {
+    src.threads = std::max(1, J.a.threads);
+    if (J.resident) return;
+    src.file.reset(new MappedFile(J.dir + "/read_data_corrected.txt", false));
+    mdbgfeed::RecordIndex idx = mdbgfeed::index_records(src.file->p, src.file->n, std::max(1, std::min(J.a.threads, 16)));
+    if (idx.truncated) die("truncated minimizer read file");
+    src.offs = std::move(idx.offs);
+    g_trace.mark("graph: read_data_corrected.txt mapped, its records indexed");
+    if (src.n_reads() >= (1ull << 32)) die("graph: more than 2^32 records in read_data_corrected.txt");
+}
+
+// Owns the pass on one rank: the cuts, the upload, the pass whole or in pieces, the rows streamed to their files as they come down
+// (graph/CreateMdbg.cpp:451-464, :515-522 for the copies).
+void one_rank_pass(GraphJob &J, const ReadSource &src, const PrevInputs &in, RankTable &out) {
+    const std::vector<std::string> recFiles = graph_plan::record_files(J.dir, J.a.firstPass, J.k, J.P.firstK);
+    const TableSink toFiles = [&](mdbg_ctx *c, mdbg_table *t, uint64_t rowBase) { stream_table_to_files(c, t, J.k, recFiles, J.dir + "/kminmerData_min.txt", rowBase); };
+    std::vector<size_t> cuts;
+    const graph_plan::Refusal refused = graph_plan::piece_cuts(src.offs, J.maxMins, cuts);
+    if (refused == graph_plan::Refusal::read_above_limit) die("graph: one read has more minimizers than a piece may hold");
+    const size_t nPieces = cuts.size() - 1;
+    if (nPieces == 1) {
+        if (!J.resident) {
+            J.resident = upload_read_range(g_ctx, src, 0, src.n_reads());
+            g_trace.mark("graph: the records' bytes on the device, taken apart there");
+        }
+        graph_rank(g_ctx, nullptr, 0, J.P, J.a, src, 0, src.n_reads(), in, out, {RowsTo::Files, toFiles}, J.resident);
+    } else {
+        g_log.line("\tThe pass runs in " + std::to_string(nPieces) + " pieces of at most " + std::to_string(J.maxMins) + " minimizers");
+        if (refused == graph_plan::Refusal::too_many_pieces) die("graph: more than 64 pieces (" + std::to_string(nPieces) + "): raise MDBG_TOOL_MAX_MINIMIZERS");
+        graph_pieces(g_ctx, J.P, J.a, src, cuts, in, out, toFiles);
+    }
+    g_trace.mark("graph: table built and written");
+}
+
+// Owns the ranks of a sharded job: one thread and one context each, their shares left in `parts`; rank 0's context stays as g_ctx.
+void sharded_pass(const GraphJob &J, const ReadSource &src, const PrevInputs &in, std::vector<RankTable> &parts) {
+    const int G = J.G;
+    uint8_t id[MDBG_COMM_ID_BYTES];
+    check(mdbg_comm_unique_id(id), "mdbg_comm_unique_id");
+    std::vector<mdbg_ctx *> ctxs((size_t)G, nullptr);
+    std::vector<std::thread> th;
+    for (int r = 0; r < G; r++) {
+        th.emplace_back([&, r] {
+            mdbg_ctx *ctx = nullptr;
+            // (MDBG_TOOL_SHARE_GPU=1, tests: every rank on device 0 -- the G-rank job on a one-GPU box; the exchange then runs as peer
+            // copies between the ranks' staging buffers on that device, RCCL refuses two ranks per device)
+            const int dev = getenv("MDBG_TOOL_SHARE_GPU") ? 0 : r;
+            if (mdbg_create(dev, &ctx) != MDBG_OK) die(std::string("mdbg_create(device ") + std::to_string(dev) + "): " + mdbg_last_error(nullptr));
+            ctxs[(size_t)r] = ctx;
+            mdbg_comm *comm = nullptr;
+            // MDBG_COMM_MODE = peer | rccl | auto (default auto: peer copies between the devices of this process, RCCL if they fail their self-test)
+            check_on(ctx, mdbg_comm_create(ctx, id, r, G, &comm), "mdbg_comm_create");
+            if (r == 0 && getenv("MDBG_TRACE"))
+                fprintf(stderr, "[mdbg_tool] exchange among %d ranks: %s%s%s\n", G, mdbg_comm_mode(comm) == MDBG_COMM_PEER ? "peer copies" : "RCCL",
+                        *mdbg_comm_note(comm) ? " (no peer copies: " : "", *mdbg_comm_note(comm) ? (std::string(mdbg_comm_note(comm)) + ")").c_str() : "");
+            const std::pair<size_t, size_t> range = graph_plan::rank_range(src.n_reads(), r, G);
+            graph_rank(ctx, comm, r, J.P, J.a, src, range.first, range.second, in, parts[(size_t)r], {RowsTo::Host, nullptr});
+            mdbg_comm_destroy(comm);
+        });
+    }
+    for (auto &t : th) t.join();
+    g_ctx = ctxs[0];
+    for (int r = 1; r < G; r++) mdbg_destroy(ctxs[(size_t)r]);
+}
+
+// Owns the job's check of itself: rank 0 repeats the pass alone over all the reads, and record count, solid count and the four
+// order-independent sums of the table (mdbg_table_checksum) must equal the sums over the ranks' shares -- the union of the shares IS the
+// single-GPU table.  A wrong exchange (a lost row, a count summed twice, two listers for one key) fails here, in the run that produced it.
+void self_check(const GraphJob &J, const ReadSource &src, const PrevInputs &in, const TableTotals &total) {
+    RankTable whole;
+    graph_rank(g_ctx, nullptr, 0, J.P, J.a, src, 0, src.n_reads(), in, whole, {RowsTo::Nowhere, nullptr});
+    const TableTotals &w = whole.totals;
+    const bool same = w.same_table(total);
+    const std::string what = "records " + std::to_string(total.n) + " / " + std::to_string(w.n) + ", solid " + std::to_string(total.nSolid) + " / " +
+                             std::to_string(w.nSolid) + ", checksum " + std::to_string(total.sums[0]) + " / " + std::to_string(w.sums[0]);
+    g_log.line(std::string("\tSelf-check of the ") + std::to_string(J.G) + "-rank table against the single-GPU pass: " + (same ? "ok" : "FAILED") + " (" + what + ")");
+    if (getenv("MDBG_TRACE")) fprintf(stderr, "[mdbg_tool] self-check %s: %s\n", same ? "ok" : "FAILED", what.c_str());
+    if (!same) die("graph --gpus " + std::to_string(J.G) + ": the sharded table differs from the single-GPU pass (" + what + ")");
+}
+
+// Owns the count lines the reference logs after a pass (the first: graph/CreateMdbg.cpp:300-328).
+void log_counts(const GraphJob &J, const TableTotals &total) {
+    if (J.a.firstPass) {
+        g_log.line("\tNb solid kminmers: " + std::to_string(total.nSolid));
+        g_log.line("\tNb rescued kminmers: " + std::to_string(total.n - total.nSolid));
+    } else g_log.line("\tNb kminmers: " + std::to_string(total.n));
+}
+
+// Owns the table files of a sharded job, which no sink streamed: the ranks' shares one after the other (the record order of these files is
+// unspecified in the reference as well).
+void write_rank_files(const GraphJob &J, const std::vector<RankTable> &parts, bool hasVec) {
+    auto write = [&](const std::string &to, std::vector<uint8_t> RankTable::*bytes) {
+        std::ofstream f(to, std::ios::binary);
+        for (const RankTable &t : parts) f.write((const char *)(t.*bytes).data(), (std::streamsize)(t.*bytes).size());
+        f.close();
+        if (!f) die("writing " + to + " failed");
+    };
+    const std::vector<std::string> recFiles = graph_plan::record_files(J.dir, J.a.firstPass, J.k, J.P.firstK);
+    write(recFiles[0], &RankTable::rec);
+    if (hasVec) write(J.dir + "/kminmerData_min.txt", &RankTable::vec);
+    for (size_t i = 1; i < recFiles.size(); i++) write(recFiles[i], &RankTable::rec);
+}
+
+[[noreturn]] void graph_main(Args a, const std::string &dir, mdbg_minimizers *resident) {
+    GraphJob J = settle_job(a, dir, resident);
     // one rank: the library context (HIP start-up: 0.09 - 0.17 s, a third of this command on a 10 Gbp read set) is created on a thread of its
     // own while this one reads the input files
     int ctxRc = MDBG_OK;
     std::thread ctxThread;
-    if (!sharded && !g_ctx) ctxThread = std::thread([&] { ctxRc = mdbg_create(0, &g_ctx); });
-    U32Vec mins;
-    std::vector<uint64_t> offs{0};
-    // One rank (the reference's own call): read_data_corrected.txt is not parsed into an array here.  Its record headers are walked by
-    // several threads (host/records.hpp: exact) while the context comes up, its bytes then travel as they are and the records are taken
-    // apart on the device (mdbg_minimizers_from_record_bytes) -- by every rank of a --gpus G job and every piece of a pass in pieces for its own
-    // range of records.  MDBG_TOOL_PARSE_ON_HOST=1: the way of rounds 1 - 5 (one walk, a host copy of the values, one pageable upload).
-    const bool byBytes = !resident && !getenv("MDBG_TOOL_PARSE_ON_HOST");
-    std::unique_ptr<MappedFile> corrected;
-    if (!resident) {
-        offs.clear();
-        corrected.reset(new MappedFile(dir + "/read_data_corrected.txt", !byBytes));
-        if (byBytes) {
-            mdbgfeed::RecordIndex idx = mdbgfeed::index_records(corrected->p, corrected->n, std::max(1, std::min(a.threads, 16)));
-            if (idx.truncated) die("truncated minimizer read file");
-            offs = std::move(idx.offs);
-            g_trace.mark("graph: read_data_corrected.txt mapped, its records indexed");
-        } else {
-            parse_minimizer_reads(corrected->p, corrected->n, mins, offs, nullptr, std::max(1, a.threads));
-            corrected.reset();
-            g_trace.mark("graph: read_data_corrected.txt read and parsed");
-        }
-    }
-    const size_t nReads = offs.size() - 1;
-    if (nReads >= (1ull << 32)) die("graph: more than 2^32 records in read_data_corrected.txt");
+    if (!J.sharded && !g_ctx) ctxThread = std::thread([&] { ctxRc = mdbg_create(0, &g_ctx); });
     ReadSource src;
-    src.raw = byBytes ? corrected->p : nullptr; src.mins = &mins; src.offs = &offs; src.threads = std::max(1, a.threads);
+    open_read_source(J, src);
     PrevInputs in;
-    if (!a.firstPass) load_prev_inputs(dir, in);
+    if (!J.a.firstPass) load_prev_inputs(dir, in);
     // every `graph` run truncates smallContigs/smallContigs_k<k>.bin (graph/CreateMdbg.cpp:258-259)
-    std::ofstream small(dir + "/smallContigs/smallContigs_k" + std::to_string(k) + ".bin", std::ios::binary);
+    std::ofstream small(dir + "/smallContigs/smallContigs_k" + std::to_string(J.k) + ".bin", std::ios::binary);
 
-    bool streamed = false;               // the table files were written as the rows came down (one rank)
-    std::vector<RankTable> parts((size_t)G);
-    if (!sharded) {
+    std::vector<RankTable> parts((size_t)J.G);
+    if (!J.sharded) {
         if (ctxThread.joinable()) ctxThread.join();
         check(ctxRc, "mdbg_create");
         g_trace.mark("graph: context created");
-        // one rank: the rows are streamed to their files (graph/CreateMdbg.cpp:451-464, :515-522 for the copies)
-        std::vector<std::string> recFiles{dir + "/kminmerData_abundance.txt"};
-        if (a.firstPass) recFiles.push_back(dir + "/kminmerData_abundance_init.txt");
-        if (k == P.firstK + 1) recFiles.push_back(dir + "/kminmerData_abundance_init_k" + std::to_string(P.firstK + 1) + ".txt");
-        std::vector<size_t> cuts{0};
-        for (size_t r = 0, first = 0; r < nReads; r++) {
-            if (offs[r + 1] - offs[r] > maxMins) die("graph: one read has more minimizers than a piece may hold");
-            if (offs[r + 1] - offs[first] > maxMins) { cuts.push_back(r); first = r; }
-        }
-        cuts.push_back(nReads);
-        if (byBytes && cuts.size() <= 2) {
-            resident = upload_read_range(g_ctx, src, 0, nReads);
-            g_trace.mark("graph: the records' bytes on the device, taken apart there");
-        }
-        if (cuts.size() > 2) {
-            g_log.line("\tThe pass runs in " + std::to_string(cuts.size() - 1) + " pieces of at most " + std::to_string(maxMins) + " minimizers");
-            graph_pieces(g_ctx, P, a, src, cuts, in, parts[0], [&](mdbg_ctx *c, mdbg_table *t, uint64_t rowBase, bool firstShare) {
-                stream_table_to_files(c, t, k, recFiles, dir + "/kminmerData_min.txt", rowBase, firstShare);
-            });
-        } else
-            graph_rank(g_ctx, nullptr, 0, P, a, src, 0, nReads, in, parts[0], false,
-                       [&](mdbg_ctx *c, mdbg_table *t) { stream_table_to_files(c, t, k, recFiles, dir + "/kminmerData_min.txt"); }, resident);
-        streamed = true;
-        g_trace.mark("graph: table built and written");
-    } else {
-        uint8_t id[MDBG_COMM_ID_BYTES];
-        check(mdbg_comm_unique_id(id), "mdbg_comm_unique_id");
-        std::vector<mdbg_ctx *> ctxs((size_t)G, nullptr);
-        std::vector<std::thread> th;
-        for (int r = 0; r < G; r++) {
-            th.emplace_back([&, r] {
-                mdbg_ctx *ctx = nullptr;
-                // (MDBG_TOOL_SHARE_GPU=1, tests: every rank on device 0 -- the G-rank job on a one-GPU box; the exchange then runs as peer
-                // copies between the ranks' staging buffers on that device, RCCL refuses two ranks per device)
-                const int dev = getenv("MDBG_TOOL_SHARE_GPU") ? 0 : r;
-                if (mdbg_create(dev, &ctx) != MDBG_OK) die(std::string("mdbg_create(device ") + std::to_string(dev) + "): " + mdbg_last_error(nullptr));
-                ctxs[(size_t)r] = ctx;
-                mdbg_comm *comm = nullptr;
-                // MDBG_COMM_MODE = peer | rccl | auto (default auto: peer copies between the devices of this process, RCCL if they fail their self-test)
-                check_on(ctx, mdbg_comm_create(ctx, id, r, G, &comm), "mdbg_comm_create");
-                if (r == 0 && getenv("MDBG_TRACE"))
-                    fprintf(stderr, "[mdbg_tool] exchange among %d ranks: %s%s%s\n", G, mdbg_comm_mode(comm) == MDBG_COMM_PEER ? "peer copies" : "RCCL",
-                            *mdbg_comm_note(comm) ? " (no peer copies: " : "", *mdbg_comm_note(comm) ? (std::string(mdbg_comm_note(comm)) + ")").c_str() : "");
-                graph_rank(ctx, comm, r, P, a, src, nReads * (size_t)r / (size_t)G, nReads * (size_t)(r + 1) / (size_t)G, in, parts[(size_t)r]);
-                mdbg_comm_destroy(comm);
-            });
-        }
-        for (auto &t : th) t.join();
-        g_ctx = ctxs[0];
-        for (int r = 1; r < G; r++) mdbg_destroy(ctxs[(size_t)r]);
-    }
-    uint64_t n = 0, nSolid = 0, sums[4] = {0, 0, 0, 0};
-    int hasVec = 0;                  // any rank's view: a rank without reads (G > reads) still reports the table's kind, but do not rely on it
+        one_rank_pass(J, src, in, parts[0]);
+    } else sharded_pass(J, src, in, parts);
+    TableTotals total;
     for (const RankTable &t : parts) {
-        n += t.n; nSolid += t.nSolid; hasVec |= t.hasVec;
-        for (int i = 0; i < 4; i++) sums[i] += t.sums[i];
+        total.add(t.totals);
         small.write(t.smallContigs.data(), (std::streamsize)t.smallContigs.size());
     }
     // the line the reference itself logs when it loads this table again at the next k (graph/CreateMdbg.cpp:3321, :3397)
-    g_log.line("\tChecksum kminmer abundance: " + std::to_string(sums[0]));
-    if (sharded && a.verify) {
-        // The job checks itself: rank 0 repeats the pass alone over all the reads, and record count, solid count and the four
-        // order-independent sums of the table (mdbg_table_checksum) must equal the sums over the ranks' shares -- the union of the
-        // shares IS the single-GPU table.  A wrong exchange (a lost row, a count summed twice, two listers for one key) fails here,
-        // in the run that produced it.  --no-verify skips it.
-        RankTable whole;
-        graph_rank(g_ctx, nullptr, 0, P, a, src, 0, nReads, in, whole, false);
-        const bool same = whole.n == n && whole.nSolid == nSolid && whole.sums[0] == sums[0] && whole.sums[1] == sums[1] &&
-                          whole.sums[2] == sums[2] && whole.sums[3] == sums[3];
-        const std::string what = "records " + std::to_string(n) + " / " + std::to_string(whole.n) + ", solid " + std::to_string(nSolid) + " / " +
-                                 std::to_string(whole.nSolid) + ", checksum " + std::to_string(sums[0]) + " / " + std::to_string(whole.sums[0]);
-        g_log.line(std::string("\tSelf-check of the ") + std::to_string(G) + "-rank table against the single-GPU pass: " + (same ? "ok" : "FAILED") + " (" + what + ")");
-        if (getenv("MDBG_TRACE")) fprintf(stderr, "[mdbg_tool] self-check %s: %s\n", same ? "ok" : "FAILED", what.c_str());
-        if (!same) die("graph --gpus " + std::to_string(G) + ": the sharded table differs from the single-GPU pass (" + what + ")");
-    }
-    if (a.firstPass) {   // the two counts the reference logs after its first pass (graph/CreateMdbg.cpp:300-328)
-        g_log.line("\tNb solid kminmers: " + std::to_string(nSolid));
-        g_log.line("\tNb rescued kminmers: " + std::to_string(n - nSolid));
-    } else {
-        g_log.line("\tNb kminmers: " + std::to_string(n));
-    }
-    // the ranks' shares one after the other: the record order of these files is unspecified in the reference as well
-    auto write_records = [&](const std::string &to) {
-        std::ofstream f(dir + to, std::ios::binary);
-        for (const RankTable &t : parts) f.write((const char *)t.rec.data(), (std::streamsize)t.rec.size());
-        f.close();
-        if (!f) die("writing " + dir + to + " failed");
-    };
-    if (!streamed) {
-        write_records("/kminmerData_abundance.txt");
-        if (hasVec) {
-            std::ofstream f(dir + "/kminmerData_min.txt", std::ios::binary);
-            for (const RankTable &t : parts) f.write((const char *)t.vec.data(), (std::streamsize)(t.vec.size() * 4));
-            f.close();
-            if (!f) die("writing " + dir + "/kminmerData_min.txt failed");
-        }
-        // graph/CreateMdbg.cpp:515-522
-        if (a.firstPass) write_records("/kminmerData_abundance_init.txt");
-        if (k == P.firstK + 1) write_records("/kminmerData_abundance_init_k" + std::to_string(P.firstK + 1) + ".txt");
-    }
+    g_log.line("\tChecksum kminmer abundance: " + std::to_string(total.sums[0]));
+    if (J.sharded && J.a.verify) self_check(J, src, in, total);       // (--no-verify skips it)
+    log_counts(J, total);
+    if (J.sharded) write_rank_files(J, parts, total.hasVec);
     small.close();
-    if (!small) die("writing smallContigs_k" + std::to_string(k) + ".bin failed");
+    if (!small) die("writing smallContigs_k" + std::to_string(J.k) + ".bin failed");
     g_trace.mark("graph: tables written");
     write_perf(dir);
     g_trace.mark("graph: done");

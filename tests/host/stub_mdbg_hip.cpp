@@ -22,7 +22,7 @@ struct mdbg_table { uint32_t k = 0; std::vector<uint8_t> rec; std::vector<uint32
 struct mdbg_bytes { std::vector<uint8_t> d; std::atomic<uint64_t> tickets{0}; };
 struct mdbg_census {};
 struct mdbg_comm {};
-struct mdbg_shard {};
+struct mdbg_shard { mdbg_table *table = nullptr; ~mdbg_shard() { delete table; } };       // a piece of a first pass in pieces: its rows, until mdbg_shard_finish hands them out
 
 static void jitter() {           // a little work of varying length, like kernels of varying batches
     static std::atomic<uint32_t> x{12345};
@@ -153,7 +153,9 @@ int mdbg_census_top(mdbg_ctx *, const mdbg_census *, uint32_t *, uint32_t *n) { 
 void mdbg_census_free(mdbg_census *c) { delete c; }
 // ---- `graph --firstpass` through the stub: one fake row per read that has at least k minimizers (key and abundance a function of the read's
 // minimizers alone, the vector its first k), in the order the reads are given -- enough to check that `asmStep` hands the first pass the same
-// reads as `graph` finds in the file.  The passes above firstK are not exercised: their entry points exist so that the tool links.
+// reads as `graph` finds in the file.  The other two ways of running the first pass -- as ranks of a communicator, in pieces on one device -- make the
+// same rows for their range of reads and exchange nothing (a row belongs to the rank or piece that holds its read), so the three ways must
+// write the same bytes.  The passes above firstK are not exercised: their entry points exist so that the tool links.
 int mdbg_kminmer_count_first(mdbg_ctx *, const mdbg_minimizers *m, uint32_t k, uint32_t, mdbg_table **out) {
     jitter();
     mdbg_table *t = new mdbg_table();
@@ -171,7 +173,7 @@ int mdbg_kminmer_count_first(mdbg_ctx *, const mdbg_minimizers *m, uint32_t k, u
     *out = t;
     return MDBG_OK;
 }
-int mdbg_kminmer_count_first_sharded(mdbg_ctx *, mdbg_comm *, const mdbg_minimizers *, uint32_t, uint32_t, mdbg_table **) { return MDBG_ENODEV; }
+int mdbg_kminmer_count_first_sharded(mdbg_ctx *c, mdbg_comm *, const mdbg_minimizers *m, uint32_t k, uint32_t min_ab, mdbg_table **out) { return mdbg_kminmer_count_first(c, m, k, min_ab, out); }
 int mdbg_prev_from_records(mdbg_ctx *, const uint8_t *, uint64_t, mdbg_table **) { return MDBG_ENODEV; }
 int mdbg_prev_overlay_unitigs(mdbg_ctx *, mdbg_table *, const mdbg_minimizers *, const uint32_t *, uint32_t) { return MDBG_ENODEV; }
 int mdbg_kminmer_count_refined(mdbg_ctx *, const mdbg_minimizers *, const mdbg_minimizers *, uint32_t, const mdbg_table *, mdbg_table **) { return MDBG_ENODEV; }
@@ -201,13 +203,20 @@ int mdbg_unitig_edge_index(mdbg_ctx *, const mdbg_minimizers *, uint32_t, mdbg_t
 int mdbg_table_keys_to_host(mdbg_ctx *, const mdbg_table *, uint64_t *) { return MDBG_ENODEV; }
 int mdbg_shard_from_table(mdbg_ctx *, const mdbg_table *, uint32_t, mdbg_shard **, const uint64_t **, uint64_t *) { return MDBG_ENODEV; }
 int mdbg_shard_exchange(mdbg_ctx *, mdbg_comm *, mdbg_shard *, const uint64_t *, const uint64_t *, const uint64_t **) { return MDBG_ENODEV; }
-int mdbg_shard_begin(mdbg_ctx *, const mdbg_minimizers *, uint32_t, uint32_t, mdbg_shard **, const uint64_t **, uint64_t *) { return MDBG_ENODEV; }
-int mdbg_shard_finish(mdbg_ctx *, mdbg_shard *, const uint64_t *, uint32_t, mdbg_table **) { return MDBG_ENODEV; }
-int mdbg_shard_exchange_local(mdbg_ctx *, mdbg_shard *const *, uint32_t, const uint64_t *const *, const uint64_t *, const uint64_t **) { return MDBG_ENODEV; }
+int mdbg_shard_begin(mdbg_ctx *c, const mdbg_minimizers *m, uint32_t k, uint32_t n_ranks, mdbg_shard **out, const uint64_t **rows, uint64_t *counts) {
+    mdbg_shard *s = new mdbg_shard();
+    mdbg_kminmer_count_first(c, m, k, 0, &s->table);
+    *rows = nullptr;
+    for (uint32_t d = 0; d < n_ranks; d++) counts[d] = 0;      // nothing to send: every row stays with its piece
+    *out = s;
+    return MDBG_OK;
+}
+int mdbg_shard_finish(mdbg_ctx *, mdbg_shard *s, const uint64_t *, uint32_t, mdbg_table **out) { *out = s->table; s->table = nullptr; return MDBG_OK; }
+int mdbg_shard_exchange_local(mdbg_ctx *, mdbg_shard *const *, uint32_t, const uint64_t *const *, const uint64_t *, const uint64_t **) { return MDBG_OK; }
 int mdbg_shard_keep(mdbg_ctx *, mdbg_shard *, const uint64_t *, mdbg_table **) { return MDBG_ENODEV; }
 void mdbg_shard_free(mdbg_shard *s) { delete s; }
-int mdbg_comm_unique_id(uint8_t *) { return MDBG_ENODEV; }
-int mdbg_comm_create(mdbg_ctx *, const uint8_t *, int, int, mdbg_comm **) { return MDBG_ENODEV; }
+int mdbg_comm_unique_id(uint8_t *id) { memset(id, 0, MDBG_COMM_ID_BYTES); return MDBG_OK; }
+int mdbg_comm_create(mdbg_ctx *, const uint8_t *, int, int, mdbg_comm **out) { *out = new mdbg_comm(); return MDBG_OK; }
 int mdbg_comm_create_mode(mdbg_ctx *, const uint8_t *, int, int, int, mdbg_comm **) { return MDBG_ENODEV; }
 int mdbg_comm_mode(const mdbg_comm *) { return MDBG_COMM_RCCL; }
 const char *mdbg_comm_note(const mdbg_comm *) { return ""; }
