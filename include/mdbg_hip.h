@@ -713,7 +713,8 @@ int  mdbg_sequences_to_fasta_bytes(mdbg_ctx *ctx, const mdbg_sequences *seqs, co
  *
  * What stays with the caller: the compression of the match lists (TurboPFor, compressMatches :1315-1320) and the BGZF partition files --
  * the reference's way of carrying a chunk's result to its merge, which an mdbg_selection (or its arrays, stored and given back through
- * mdbg_selection_from_host) replaces -- and the base-level alignRead of ReadCorrection. */
+ * mdbg_selection_from_host) replaces -- and, behind mdbg_map_verify below, performPoaCorrection4 of ReadCorrection with its low-density
+ * re-chaining and the graph it builds. */
 typedef struct mdbg_map_index mdbg_map_index;
 typedef struct mdbg_anchors mdbg_anchors;
 typedef struct mdbg_chains mdbg_chains;
@@ -756,6 +757,90 @@ int  mdbg_selection_to_host(mdbg_ctx *ctx, const mdbg_selection *s, uint64_t *se
 int  mdbg_selection_device_ptrs(const mdbg_selection *s, const void *d_ptrs[4]);
 void mdbg_selection_free(mdbg_selection *s);
 uint32_t mdbg_select_lds_positions(void);
+
+/* ---- the selected pairs verified at correction density --------------------------------------------------------------------------------
+ * Replaces ReadCorrectionFunctor::filterAlignments (readSelection/ReadCorrection.hpp:5006-5117): for every read to be corrected and every
+ * neighbour the selection kept for it, the join of the two reads' minimizers at the full correction density, the chain of
+ * MinimizerChainer::computeChainingAlignment (readSelection/MinimizerChainer.hpp:114-705; chainAnchors / argmaxPosition :735-961), and the
+ * four tests of :5088-5094.  What survives is {neighbour, isQueryReversed}, the only input performPoaCorrection4 takes.
+ *
+ * Names.  The reference calls the read being corrected referenceRead and the other queryRead; the selection calls the read being corrected
+ * the query and mdbg_selected::ref_read the other -- the opposite way round.  Here the read being corrected is the TARGET (a query of the
+ * selection) and the other read the NEIGHBOUR (a ref_read of one of its rows); the fields reference_* belong to the target, query_* to the
+ * neighbour, as in AlignmentResult2.
+ *
+ * mdbg_minimizers_attach_strands  gives a set that has attached positions the direction bytes (one per minimizer, 0 or 1) and the raw read
+ *       lengths (one per read) a scan output has.  MDBG_EINVAL: a set without positions, a scan output, a direction byte other than 0 or 1
+ *       (the message names the first offending read).
+ *
+ * mdbg_map_verify  `reads` is the set at correction density and holds the global reads [reads_first_read, reads_first_read + n); it must
+ *       carry positions, directions and read lengths: a scan output, a concat of scan outputs, the density-thresholded form of either, or a
+ *       host set given mdbg_minimizers_attach_positions and mdbg_minimizers_attach_strands; anything else is MDBG_EINVAL.  A slice
+ *       (mdbg_minimizers_slice) carries offsets and values only and is refused like any other set without positions: to verify against a
+ *       range of a resident scan output, concat the scans of that range, or pass the whole set and let the rows outside be ABSENT.  Target t of `sel` is global read
+ *       target_first_read + t.  One mdbg_verified row per selected row, in the selection's order (row_offsets is the selection's
+ *       sel_offsets); a row whose target or neighbour lies outside `reads` gets MDBG_VERIFY_ABSENT and zero fields (the reference's
+ *       _mReads4.find miss, :5033).  ReadCorrectionFunctor::operator() does not correct targets below 10 minimizers at assembly density
+ *       (Utils::isReadTooShort); that stays the caller's business: every listed target is verified.
+ *       Anchors of a pair (:5051-5069): one for every (i, j) with target.m[i] == neighbour.m[j] -- ref_position = target.pos[i],
+ *       query_position = neighbour.pos[j], reversed = target.dir[i] != neighbour.dir[j] -- in (i, j) order, which is the order the
+ *       reference's sort by (ref_position, query_position) leaves (MinimizerChainer.hpp:154-159).  Fewer than 3: no chain (:146).
+ *       Chain: the predecessor test, score, band and both tie rules are those mdbg_map_chains documents (:862-961, :735-858); the best
+ *       anchor has the largest score, on a tie the smallest i (:810-815); its parents walked to the root are the chain, FIRST the root and
+ *       LAST the best anchor; a chain of 3 anchors or fewer is no chain (:268; the mapper's limit is below 3).  Scores are integers; a pair
+ *       of 209 715 anchors or more gets MDBG_VERIFY_TOO_LONG and zero fields, known after the count, before anything is allocated for it.
+ *       Summary (:274-307, :356-428, :547-569, :581-582, :614, :657-673), n_t, n_q the minimizer counts, L_t, L_q the raw lengths, f and l
+ *       the first and last anchor, ri / qi their indexes: query_reversed = f.qi > l.qi.  Forward: overhang_start = min(tpos[f.ri],
+ *       qpos[f.qi]), start_mis = min(f.ri, f.qi), overhang_end = min(L_t - tpos[l.ri - 1], L_q - qpos[l.qi - 1]), end_mis = min(n_t - l.ri
+ *       - 1, n_q - l.qi - 1).  Reversed: overhang_start = min(tpos[f.ri], L_q - qpos[f.qi - 1]), start_mis = min(f.ri, n_q - f.qi - 1),
+ *       overhang_end = min(L_t - tpos[l.ri - 1], qpos[l.qi]), end_mis = min(n_t - l.ri - 1, l.qi).  (The - 1 on the indexes is the
+ *       reference's own.)  Overhangs are int64 cut to 32 bits.  For consecutive chain anchors a, b: rg = b.ri - a.ri - 1, qg = b.qi - a.qi
+ *       - 1 (a.qi - b.qi - 1 when reversed); mismatches += min(rg, qg), the excess of rg is deletions, of qg insertions.  n_matches = the
+ *       chain's length, n_mismatches = start_mis + the sum + end_mis, n_seeds = min(matches + mismatches + deletions, matches + mismatches +
+ *       insertions), align_length = l.ref_position - f.ref_position, reference_start / _end = f's / l's ref_position, query_start / _end =
+ *       f's / l's query_position, swapped when reversed.
+ *       Kept (:5088-5094) iff overhang_start <= max_overhang and overhang_end <= max_overhang and align_length >= min_overlap_length and
+ *       identity >= min_identity, identity = 1.0 - (float)(1.0 - pow(n_matches / (long double)n_seeds, 1.0 / minimizer_size)), 1 when the
+ *       two are equal.  The reference compares _alignLength with a float; min_overlap_length is a uint32_t here.  The device compares
+ *       n_matches with a table the host makes with that very expression (mdbg_verify_min_matches) once a call.
+ *       The kept list: per target (kept_offsets[n_targets + 1]) the rows with MDBG_VERIFY_KEPT in the rows' order -- ascending neighbour,
+ *       as the reference walks alignedQueryReads -- as kept_neighbour (u32) and kept_reversed (u8).
+ *       MDBG_EINVAL: max_chaining_band 0, minimizer_size 0, a min_identity that is not a number, a set without positions, directions or
+ *       lengths.  MDBG_ERANGE: 2^32 anchors or
+ *       more in one call.  An empty selection gives an empty result.  Timer names: "verify_join", "verify_chains", "verify_rows",
+ *       "radix_sort".
+ * mdbg_verification_info  targets, rows, chains found, kept.  _to_host: any array may be NULL.  device_ptrs, in order: row_offsets (u64),
+ *       rows (mdbg_verified), kept_offsets (u64), kept_neighbour (u32), kept_reversed (u8).
+ * mdbg_verify_lds_anchors  anchors of a pair up to which its scores and parents live in LDS, and minimizers of a neighbour up to which the
+ *       join keeps its lookup in LDS; a longer one goes through global memory.
+ * mdbg_verify_min_matches  host only, no context: min_matches[s], s = 0 ... n_seeds_max (n_seeds_max + 1 values), the smallest n_matches
+ *       whose identity at n_seeds = s is not below min_identity, or s + 1 when none is.  MDBG_EINVAL: a null argument, minimizer_size 0,
+ *       n_seeds_max = 2^32 - 1 (the table would have 2^32 values), a min_identity that is not a number (mdbg_map_verify refuses that too). */
+typedef struct mdbg_verification mdbg_verification;
+typedef struct { uint32_t max_chaining_band;   /* ReadCorrection.hpp:1739: 62 at 0.025 */
+                 uint32_t max_overhang;        /* :5088-5089: 1000 */
+                 uint32_t min_overlap_length;  /* :1638: 1000 */
+                 float    min_identity;        /* :1639: 0.96f */
+                 uint32_t minimizer_size;      /* Parameters::_minimizerSize, the root in the identity */
+                 uint32_t reserved[3]; } mdbg_verify_params;
+#define MDBG_VERIFY_CHAIN     1u   /* a chain of 4 anchors or more was found; the fields are set */
+#define MDBG_VERIFY_KEPT      2u   /* ... and it passed the four tests */
+#define MDBG_VERIFY_ABSENT    4u   /* the target or the neighbour is not in `reads` (the reference's _mReads4.find miss, :5033) */
+#define MDBG_VERIFY_TOO_LONG  8u   /* 209 715 anchors or more: never an approximate chain (as MDBG_CHAIN_TOO_LONG) */
+typedef struct { uint32_t neighbour, flags, query_reversed, n_anchors;
+                 int32_t n_matches, n_mismatches, n_deletions, n_insertions;
+                 uint32_t overhang_start, overhang_end, align_length, n_seeds;
+                 uint32_t reference_start, reference_end, query_start, query_end; } mdbg_verified;   /* 64 bytes */
+int  mdbg_minimizers_attach_strands(mdbg_ctx *ctx, mdbg_minimizers *m, const uint8_t *directions, const uint32_t *read_lengths);
+int  mdbg_map_verify(mdbg_ctx *ctx, const mdbg_selection *sel, uint32_t target_first_read, const mdbg_minimizers *reads, uint32_t reads_first_read,
+                     const mdbg_verify_params *p, mdbg_verification **out);
+int  mdbg_verification_info(const mdbg_verification *v, uint64_t info[4]);
+int  mdbg_verification_to_host(mdbg_ctx *ctx, const mdbg_verification *v, uint64_t *row_offsets, mdbg_verified *rows, uint64_t *kept_offsets,
+                               uint32_t *kept_neighbour, uint8_t *kept_reversed);
+int  mdbg_verification_device_ptrs(const mdbg_verification *v, const void *d_ptrs[5]);
+void mdbg_verification_free(mdbg_verification *v);
+uint32_t mdbg_verify_lds_anchors(void);
+int  mdbg_verify_min_matches(const mdbg_verify_params *p, uint32_t n_seeds_max, uint32_t *min_matches);
 /* The library's stable radix sort (8-bit digits, least significant first; a digit in which all keys agree is skipped) on caller-chosen
    data: n uint64 keys from byte keys_at of `keys` and their n uint32 values from byte values_at of `values`, sorted by key in place, equal
    keys keeping their order.  Returns when done.  info (optional): digit passes run, digit passes skipped.  MDBG_EINVAL: a null argument,

@@ -27,6 +27,11 @@ CHAIN = np.dtype([("ref_read", "<u4"), ("flags", "<u4"), ("score", "<i4"), ("n_m
                   ("n_diff_query", "<i8"), ("n_diff_reference", "<i8"), ("query_start", "<i8"), ("query_end", "<i8"),
                   ("reference_start", "<i8"), ("reference_end", "<i8"), ("alignment_score", "<i8")])        # mdbg_chain
 SELECTED = np.dtype([("ref_read", "<u4"), ("score", "<i4"), ("n_matches", "<u4"), ("part", "<u4"), ("pair", "<u8")])   # mdbg_selected
+VERIFY_CHAIN, VERIFY_KEPT, VERIFY_ABSENT, VERIFY_TOO_LONG = 1, 2, 4, 8      # MDBG_VERIFY_*: the flags of a row of mdbg_map_verify
+VERIFIED = np.dtype([("neighbour", "<u4"), ("flags", "<u4"), ("query_reversed", "<u4"), ("n_anchors", "<u4"),
+                     ("n_matches", "<i4"), ("n_mismatches", "<i4"), ("n_deletions", "<i4"), ("n_insertions", "<i4"),
+                     ("overhang_start", "<u4"), ("overhang_end", "<u4"), ("align_length", "<u4"), ("n_seeds", "<u4"),
+                     ("reference_start", "<u4"), ("reference_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4")])     # mdbg_verified
 
 
 class MdbgError(RuntimeError):
@@ -45,6 +50,11 @@ class ScanParams(C.Structure):
 class MapParams(C.Structure):
     _fields_ = [("max_chaining_band", C.c_uint32), ("min_anchors", C.c_uint32), ("query_begin", C.c_uint32), ("query_end", C.c_uint32),
                 ("reserved", C.c_uint32 * 4)]
+
+
+class VerifyParams(C.Structure):
+    _fields_ = [("max_chaining_band", C.c_uint32), ("max_overhang", C.c_uint32), ("min_overlap_length", C.c_uint32), ("min_identity", C.c_float),
+                ("minimizer_size", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 # name -> (restype, argtypes); every symbol include/mdbg_hip.h declares
@@ -195,6 +205,14 @@ SIGNATURES = {
     "mdbg_selection_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
     "mdbg_selection_free": (None, [_P]),
     "mdbg_select_lds_positions": (C.c_uint32, []),
+    "mdbg_minimizers_attach_strands": (C.c_int, [_P, _P, _P, _P]),
+    "mdbg_map_verify": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(VerifyParams), C.POINTER(_P)]),
+    "mdbg_verification_info": (C.c_int, [_P, _u64p]),
+    "mdbg_verification_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "mdbg_verification_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_verification_free": (None, [_P]),
+    "mdbg_verify_lds_anchors": (C.c_uint32, []),
+    "mdbg_verify_min_matches": (C.c_int, [C.POINTER(VerifyParams), C.c_uint32, _u32p]),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
@@ -705,6 +723,41 @@ class Context:
         """Positions of a query up to which the selection counts in LDS (mdbg_select_lds_positions)."""
         return int(lib().mdbg_select_lds_positions())
 
+    # -- the selected pairs verified at correction density --------------------------------------------
+    def minimizers_with_strands(self, mins: np.ndarray, offsets: np.ndarray, positions: np.ndarray, directions: np.ndarray, read_lengths: np.ndarray) -> "Minimizers":
+        """A set from the host with what mdbg_map_verify reads of a scan output: positions, directions, raw read lengths."""
+        m = self.minimizers_with_positions(mins, offsets, positions)
+        m.attach_strands(directions, read_lengths)
+        return m
+
+    @staticmethod
+    def _verify_params(band: int, max_overhang: int, min_overlap_length: int, min_identity: float, minimizer_size: int) -> VerifyParams:
+        return VerifyParams(band, max_overhang, min_overlap_length, min_identity, minimizer_size, (C.c_uint32 * 3)())
+
+    def map_verify(self, sel: "Selection", reads: "Minimizers", target_first_read: int = 0, reads_first_read: int = 0, band: int = 62, max_overhang: int = 1000,
+                   min_overlap_length: int = 1000, min_identity: float = 0.96, minimizer_size: int = 15) -> "Verification":
+        """Every selected row's anchors at correction density, their chain, its summary and the verdict of filterAlignments (mdbg_map_verify)."""
+        h = C.c_void_p()
+        p = self._verify_params(band, max_overhang, min_overlap_length, min_identity, minimizer_size)
+        self.check(lib().mdbg_map_verify(self.h, sel.h if sel is not None else None, target_first_read, reads.h if reads is not None else None, reads_first_read,
+                                         C.byref(p), C.byref(h)))
+        return Verification(self, h)
+
+    @staticmethod
+    def verify_lds_anchors() -> int:
+        """Anchors of a pair (and minimizers of a neighbour) up to which mdbg_map_verify works in LDS (mdbg_verify_lds_anchors)."""
+        return int(lib().mdbg_verify_lds_anchors())
+
+    @staticmethod
+    def verify_min_matches(n_seeds_max: int, min_identity: float = 0.96, minimizer_size: int = 15) -> np.ndarray:
+        """min_matches[s], s = 0 ... n_seeds_max: the smallest n_matches whose identity passes (mdbg_verify_min_matches; host only)."""
+        out = np.zeros(n_seeds_max + 1, np.uint32)
+        p = Context._verify_params(1, 0, 0, min_identity, minimizer_size)
+        rc = lib().mdbg_verify_min_matches(C.byref(p), n_seeds_max, out.ctypes.data_as(_u32p))
+        if rc != 0:
+            raise MdbgError(rc, "mdbg_verify_min_matches: invalid argument")
+        return out
+
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
         cut, fmt = C.c_uint64(0), C.c_int(0)
@@ -1025,6 +1078,12 @@ class Minimizers:
         pos = np.ascontiguousarray(positions, dtype=np.uint32)
         self.ctx.check(lib().mdbg_minimizers_attach_positions(self.ctx.h, self.h, _ptr(pos) if len(pos) else None))
 
+    def attach_strands(self, directions: np.ndarray, read_lengths: np.ndarray) -> None:
+        """One direction byte (0 or 1) per minimizer and the raw length of every read (mdbg_minimizers_attach_strands)."""
+        d = np.ascontiguousarray(directions, dtype=np.uint8)
+        n = np.ascontiguousarray(read_lengths, dtype=np.uint32)
+        self.ctx.check(lib().mdbg_minimizers_attach_strands(self.ctx.h, self.h, _ptr(d) if len(d) else None, _ptr(n) if len(n) else None))
+
     def free(self) -> None:
         if self.h:
             lib().mdbg_minimizers_free(self.h)
@@ -1141,6 +1200,29 @@ class Selection(_MapHandle):
         p = (C.c_void_p * 4)()
         lib().mdbg_selection_device_ptrs(self.h, p)
         return dict(zip(("sel_offsets", "rows", "match_offsets", "matches"), [x or 0 for x in p]))
+
+
+class Verification(_MapHandle):
+    """One verified row per selected row and the kept neighbours of every target (mdbg_map_verify)."""
+    _free = "mdbg_verification_free"
+    _NAMES = ("row_offsets", "rows", "kept_offsets", "kept_neighbour", "kept_reversed")
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_verification_info(self.h, a)
+        return dict(zip(("n_targets", "n_rows", "n_chains", "n_kept"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        i = self.info()
+        out = dict(row_offsets=np.zeros(i["n_targets"] + 1, np.uint64), rows=np.zeros(i["n_rows"], VERIFIED), kept_offsets=np.zeros(i["n_targets"] + 1, np.uint64),
+                   kept_neighbour=np.zeros(i["n_kept"], np.uint32), kept_reversed=np.zeros(i["n_kept"], np.uint8))
+        self.ctx.check(lib().mdbg_verification_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = (C.c_void_p * 5)()
+        lib().mdbg_verification_device_ptrs(self.h, p)
+        return dict(zip(self._NAMES, [x or 0 for x in p]))
 
 
 class Spans:

@@ -135,6 +135,15 @@ struct mdbg_chains {
     mdbg::DevBuf<uint32_t> d_matches;         // n_matches
 };
 
+// The selected rows of every query and their match lists (select.hip); mdbg_map_verify (verify.hip) reads the rows.
+struct mdbg_selection {
+    uint64_t n_queries = 0, n_selected = 0, n_matches = 0, n_candidates = 0;
+    mdbg::DevBuf<uint64_t> d_sel_off;         // n_queries + 1
+    mdbg::DevBuf<mdbg_selected> d_rows;       // n_selected
+    mdbg::DevBuf<uint64_t> d_match_off;       // n_selected + 1
+    mdbg::DevBuf<uint32_t> d_matches;         // n_matches
+};
+
 // The k-min-mer spans of a batch (spans.hip); mdbg_spans_extract (extract.hip) reads the windows' fields.
 struct mdbg_spans {
     uint32_t n_reads = 0, k = 0;

@@ -21,14 +21,6 @@
 #include <algorithm>
 #include <memory>
 
-struct mdbg_selection {
-    uint64_t n_queries = 0, n_selected = 0, n_matches = 0, n_candidates = 0;
-    mdbg::DevBuf<uint64_t> d_sel_off;         // n_queries + 1
-    mdbg::DevBuf<mdbg_selected> d_rows;       // n_selected
-    mdbg::DevBuf<uint64_t> d_match_off;       // n_selected + 1
-    mdbg::DevBuf<uint32_t> d_matches;         // n_matches
-};
-
 namespace mdbg {
 
 static_assert(sizeof(mdbg_selected) == 24, "a selected row is 24 bytes");
