@@ -234,6 +234,7 @@ const StepKernel *extract_step_kernels(uint32_t *n);
 const StepKernel *stitch_step_kernels(uint32_t *n);
 const StepKernel *mapper_step_kernels(uint32_t *n);
 const StepKernel *select_step_kernels(uint32_t *n);
+const StepKernel *verify_step_kernels(uint32_t *n);
 
 int set_error(mdbg_ctx *ctx, int code, const char *fmt, ...);
 extern thread_local std::string g_last_error;  // for failures before a context exists (per calling thread)
@@ -263,6 +264,11 @@ inline hipError_t memcpy_sync(mdbg_ctx *ctx, void *dst, const void *src, size_t 
     hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(ctx->stream);
+}
+
+// An optional output of a *_to_host call: copied on the context stream when the caller gave a pointer (the caller waits once, behind the last).
+inline hipError_t download_async(mdbg_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
 }
 
 // RAII device allocation (synchronous hipMalloc; sizes here are tens of MB to GB, allocated
@@ -366,6 +372,36 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A value that is the same in every lane, said so to the compiler: lane 0's copy, in a scalar register.
+__device__ __forceinline__ uint32_t wave_uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// Maximum / sum across the 64 lanes, in every lane (butterfly, six steps).
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, 64));
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64); v = o > v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+    return v;
+}
+
+// One wave an item, items drawn in order from a device counter: lane 0 adds 1, the wave reads its lane (readfirstlane, as the scan draws its
+// reads).  The loop around the draw keeps two rules.  Every turn begins at a point all lanes pass together -- a wave_lds_sync in front of
+// the draw, which also lets the last item's lanes finish with the wave's LDS before it is overwritten -- and every item takes ONE path to
+// the end of the turn: no early `continue` behind an `if (lane == 0)`.  (The mapper's chain kernel first left the turn that way for a pair too
+// long to chain: to the compiler the other lanes then ran on alone into a turn in which lane 0 drew nothing -- item 0 again, for ever.)
+__device__ __forceinline__ uint64_t wave_draw(unsigned long long *counter) {
+    uint32_t lo = 0, hi = 0;
+    if (lane_id() == 0) { const unsigned long long drawn = atomicAdd(counter, 1ull); lo = (uint32_t)drawn; hi = (uint32_t)(drawn >> 32); }
+    return ((uint64_t)wave_uniform_u32(hi) << 32) | wave_uniform_u32(lo);
 }
 
 // Inclusive prefix sum across the 64 lanes (shuffle ladder).

@@ -240,10 +240,9 @@ extern "C" int mdbg_sequences_info(const mdbg_sequences *s, uint64_t *n, uint64_
 extern "C" int mdbg_sequences_to_host(mdbg_ctx *ctx, const mdbg_sequences *s, uint64_t *byte_offsets, uint32_t *lengths, uint8_t *bytes) try {
     if (!ctx || !s) return set_error(ctx, MDBG_EINVAL, "mdbg_sequences_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    auto dl = [&](void *dst, const void *src, size_t n_bytes) { return dst && n_bytes ? hipMemcpyAsync(dst, src, n_bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(byte_offsets, s->d_off.p, (s->n + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(lengths, s->d_len.p, s->n * 4));
-    MDBG_HIP_CHECK(ctx, dl(bytes, s->d_bytes.p, s->n_bytes));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, byte_offsets, s->d_off.p, (s->n + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, lengths, s->d_len.p, s->n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, bytes, s->d_bytes.p, s->n_bytes));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)

@@ -15,14 +15,12 @@
 //                spread over many waves.  Generation order is (query, query index); one sort_u64_pairs by (query << 32 | the reference
 //                window's number) gives (query, ref_read, ref_position, query_position): a read's windows are numbered in position order,
 //                and equal keys keep the generation order.  Group heads, sizes, the min_anchors filter and the final rows follow.
-//   the chains   one wave a pair, pairs drawn in order from a device counter.  For anchor i lane t evaluates predecessor i - 1 - t (64 a
-//                trip, ceil(band / 64) trips); a candidate is (score << 32 | j), so one 64-bit max over the wave is "best score, largest j".
-//                Scores and parents of the pair live in LDS up to MAP_LDS_ANCHORS anchors, above in a pooled global buffer.  Lane 0 walks
-//                the parents and writes the row and the pair's match list into a staging array (a list is no longer than its pair); the
-//                lists are compacted behind a scan, dealt by output element.
+//   the chains   one wave a pair, pairs drawn in order from a device counter (wave_draw); the dynamic programme is chain_wave
+//                (chain_wave.hpp), which the verifier runs too.  Lane 0 walks the parents and writes the row and the pair's match list
+//                into a staging array (a list is no longer than its pair); the lists are compacted behind a scan, dealt by output element.
 #include "common.hpp"
 #include "objects.hpp"
-#include "mapper_dev.hpp"
+#include "chain_wave.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -51,8 +49,6 @@ namespace mdbg {
 
 static_assert(sizeof(mdbg_chain) == 80, "a chain row is 80 bytes");
 static_assert(sizeof(mdbg_map_params) == 32, "mdbg_map_params is 32 bytes");
-
-constexpr uint32_t MAP_LDS_ANCHORS = 1024;    // anchors of a pair whose scores and parents fit a wave's share of LDS (8 KB a wave, 32 KB a block)
 
 // ---- the index ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void map_window_counts_kernel(const uint64_t *off, uint32_t n_reads, uint32_t *wcount) {
@@ -110,8 +106,7 @@ __global__ __launch_bounds__(256) void map_compact_heads_kernel(const uint64_t *
 __global__ __launch_bounds__(256) void map_longest_kernel(const uint32_t *start, uint64_t n, unsigned long long *longest) {
     uint32_t m = 0;
     for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256u) m = max(m, start[k + 1u] - start[k]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    m = wave_max_u32(m);
     if (lane_id() == 0 && m) atomicMax(longest, (unsigned long long)m);
 }
 
@@ -194,8 +189,7 @@ __global__ __launch_bounds__(256) void map_group_sizes_kernel(const uint32_t *gs
         kflag[g] = keep ? 1u : 0u;
         if (keep) m = max(m, size);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
+    m = wave_max_u32(m);
     if (lane_id() == 0 && m) atomicMax(longest, (unsigned long long)m);
 }
 
@@ -246,71 +240,39 @@ __global__ __launch_bounds__(256) void map_emit_kernel(const uint32_t *vals, con
 }
 
 // ---- the chains --------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// One wave a pair.  g_score / g_parent: n_anchors each, for the pairs above MAP_LDS_ANCHORS (null when there is none).  staged: n_anchors,
+// One wave a pair.  g_score / g_parent: n_anchors each, for the pairs above CHAIN_LDS_ANCHORS (null when there is none).  staged: n_anchors,
 // the pair's match list from its first anchor's place on.  counters: [0] the next pair, [1] chains found.
 __global__ __launch_bounds__(256) void map_chain_kernel(const uint64_t *anchor_off, const uint32_t *pair_ref, uint64_t n_pairs, const uint32_t *ref_pos,
                                                         const uint32_t *ref_idx, const uint32_t *q_pos, const uint32_t *q_idx, const uint8_t *rev, uint32_t band,
                                                         unsigned long long *counters, int32_t *g_score, uint32_t *g_parent, mdbg_chain *chains, uint32_t *n_matches,
                                                         uint32_t *staged) {
-    __shared__ int32_t s_score[4][MAP_LDS_ANCHORS];
-    __shared__ uint32_t s_parent[4][MAP_LDS_ANCHORS];
+    __shared__ int32_t s_score[4][CHAIN_LDS_ANCHORS];
+    __shared__ uint32_t s_parent[4][CHAIN_LDS_ANCHORS];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (;;) {
-        // Every turn begins at a point all lanes pass together (also: lane 0 has walked the last pair's parents before they are overwritten), and
-        // every pair takes ONE path to the end of the turn.  Lane 0 draws, the wave reads its lane: readfirstlane, as the scan draws its
-        // reads.  (A first form left the turn early, by `continue` behind an `if (lane == 0)`, for a pair too long to chain: to the compiler
-        // the other lanes then ran on alone into a next turn in which lane 0 drew nothing -- pair 0 again, for ever: a branch to itself.)
-        wave_lds_sync();
-        uint32_t lo = 0, hi = 0;
-        if (lane == 0) { const unsigned long long drawn = atomicAdd(counters, 1ull); lo = (uint32_t)drawn; hi = (uint32_t)(drawn >> 32); }
-        const uint64_t p = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+        wave_lds_sync();          // the turn's common start, one path to its end (wave_draw); lane 0 has walked the last pair's parents before they are overwritten
+        const uint64_t p = wave_draw(counters);
         if (p >= n_pairs) break;
         const uint64_t a0 = anchor_off[p];
         const uint32_t n = (uint32_t)(anchor_off[p + 1u] - a0);
         const bool chained = n != 0u && n < MAP_CHAIN_TOO_LONG_FROM;      // the same in every lane
-        const bool in_lds = n <= MAP_LDS_ANCHORS;
+        const bool in_lds = n <= CHAIN_LDS_ANCHORS;
         int32_t *score = in_lds ? s_score[wave] : g_score + a0;
         uint32_t *parent = in_lds ? s_parent[wave] : g_parent + a0;
-        const uint32_t *rp = ref_pos + a0, *qp = q_pos + a0;
-        const uint8_t *rv = rev + a0;
-        int32_t best_score = 0;
-        uint32_t best_i = 0;
-        for (uint32_t i = 0; chained && i < n; i++) {
-            const uint32_t ri = rp[i], qi = qp[i], rvi = rv[i];
-            const uint32_t cnt = map_band_count(i, band);
-            uint64_t best = 0;
-            for (uint32_t base = 0; base < cnt; base += 64u) {
-                const uint32_t t = base + lane;
-                if (t < cnt) {
-                    const uint32_t j = i - 1u - t;
-                    const uint64_t c = map_candidate(score[j], map_pred_gap(ri, qi, rvi, rp[j], qp[j], rv[j]), j);
-                    best = c > best ? c : best;
-                }
-            }
-            best = wave_max_u64(best);
-            const int32_t sc = map_candidate_score(best);
-            if (lane == 0) { score[i] = sc; parent[i] = map_candidate_parent(best); }
-            if (in_lds) wave_lds_sync(); else __threadfence_block();         // (the next anchor's lanes read what lane 0 wrote)
-            if (map_better_end(sc, best_score)) { best_score = sc; best_i = i; }
-        }
+        const uint32_t *rp = ref_pos + a0;
+        const ChainEnd end = chain_wave(chained ? n : 0u, rp, q_pos + a0, rev + a0, band, score, parent, in_lds);
         if (lane == 0) {
+            const uint32_t best_i = end.i;
             mdbg_chain row;
             row.ref_read = pair_ref[p]; row.flags = n && !chained ? MDBG_CHAIN_TOO_LONG : 0u; row.score = 0; row.n_matches = 0u; row.query_reversed = 0u; row.reserved = 0u;
             row.n_diff_query = row.n_diff_reference = row.query_start = row.query_end = row.reference_start = row.reference_end = row.alignment_score = 0;
+            // map_chain_walk, written out: through the helper this kernel's map_chains timer read 1.2 % above the parent's in every one of
+            // eleven alternating runs, written out it reads the parent's (profiles/chain_shared_bench_alternating.txt); the verifier calls it
             uint32_t len = 0, root = best_i;
             if (chained)
                 for (uint32_t at = best_i; at != MAP_NO_PARENT; at = parent[at]) { root = at; len++; }
             if (len >= MAP_MIN_CHAIN) {
-                const MapChain c = map_chain_fields(best_score, len, q_idx[a0 + best_i], q_idx[a0 + root], ref_idx[a0 + best_i], ref_idx[a0 + root], rp[best_i], rp[root]);
+                const MapChain c = map_chain_fields(end.score, len, q_idx[a0 + best_i], q_idx[a0 + root], ref_idx[a0 + best_i], ref_idx[a0 + root], rp[best_i], rp[root]);
                 row.flags = MDBG_CHAIN_FOUND; row.score = c.score; row.n_matches = c.n_matches; row.query_reversed = c.query_reversed;
                 row.n_diff_query = c.n_diff_query; row.n_diff_reference = c.n_diff_reference; row.query_start = c.query_start; row.query_end = c.query_end;
                 row.reference_start = c.reference_start; row.reference_end = c.reference_end; row.alignment_score = c.alignment_score;
@@ -458,12 +420,11 @@ extern "C" int mdbg_map_index_to_host(mdbg_ctx *ctx, const mdbg_map_index *ix, u
     if (!ctx || !ix) return set_error(ctx, MDBG_EINVAL, "mdbg_map_index_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t n = ix->n_entries;
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(pairs, ix->d_pair.p, n * 8));
-    MDBG_HIP_CHECK(ctx, dl(reads, ix->d_read.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(positions, ix->d_pos.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(indexes, ix->d_idx.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(reversed, ix->d_rev.p, n));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pairs, ix->d_pair.p, n * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, reads, ix->d_read.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, positions, ix->d_pos.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, indexes, ix->d_idx.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, reversed, ix->d_rev.p, n));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
@@ -596,16 +557,15 @@ extern "C" int mdbg_anchors_to_host(mdbg_ctx *ctx, const mdbg_anchors *a, uint64
     if (!ctx || !a) return set_error(ctx, MDBG_EINVAL, "mdbg_anchors_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t n = a->n_anchors;
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(pair_offsets, a->d_pair_off.p, ((size_t)a->n_queries + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(pair_ref_read, a->d_pair_ref.p, (size_t)a->n_pairs * 4));
-    MDBG_HIP_CHECK(ctx, dl(anchor_offsets, a->d_anchor_off.p, ((size_t)a->n_pairs + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(ref_read, a->d_ref_read.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(ref_position, a->d_ref_pos.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(ref_index, a->d_ref_idx.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(query_position, a->d_q_pos.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(query_index, a->d_q_idx.p, n * 4));
-    MDBG_HIP_CHECK(ctx, dl(reversed, a->d_rev.p, n));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pair_offsets, a->d_pair_off.p, ((size_t)a->n_queries + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pair_ref_read, a->d_pair_ref.p, (size_t)a->n_pairs * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, anchor_offsets, a->d_anchor_off.p, ((size_t)a->n_pairs + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, ref_read, a->d_ref_read.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, ref_position, a->d_ref_pos.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, ref_index, a->d_ref_idx.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, query_position, a->d_q_pos.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, query_index, a->d_q_idx.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, reversed, a->d_rev.p, n));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
@@ -635,7 +595,7 @@ extern "C" int mdbg_map_chains(mdbg_ctx *ctx, const mdbg_anchors *a, const mdbg_
     DevBuf<uint32_t> n_matches, staged, g_parent;
     DevBuf<int32_t> g_score;
     MDBG_TRY(counters.alloc(ctx, 2)); MDBG_TRY(n_matches.alloc(ctx, np)); MDBG_TRY(staged.alloc(ctx, na));
-    const bool spill = a->longest > MAP_LDS_ANCHORS;          // some pair's scores and parents do not fit LDS
+    const bool spill = a->longest > CHAIN_LDS_ANCHORS;          // some pair's scores and parents do not fit LDS
     if (spill) { MDBG_TRY(g_score.alloc(ctx, na)); MDBG_TRY(g_parent.alloc(ctx, na)); }
     MDBG_HIP_CHECK(ctx, hipMemsetAsync(counters.p, 0, 16, ctx->stream));
     {
@@ -672,11 +632,10 @@ extern "C" int mdbg_chains_info(const mdbg_chains *c, uint64_t info[4]) {
 extern "C" int mdbg_chains_to_host(mdbg_ctx *ctx, const mdbg_chains *c, uint64_t *pair_offsets, mdbg_chain *chains, uint64_t *match_offsets, uint32_t *matches) try {
     if (!ctx || !c) return set_error(ctx, MDBG_EINVAL, "mdbg_chains_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(pair_offsets, c->d_pair_off.p, ((size_t)c->n_queries + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(chains, c->d_chain.p, (size_t)c->n_pairs * sizeof(mdbg_chain)));
-    MDBG_HIP_CHECK(ctx, dl(match_offsets, c->d_match_off.p, ((size_t)c->n_pairs + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(matches, c->d_matches.p, (size_t)c->n_matches * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pair_offsets, c->d_pair_off.p, ((size_t)c->n_queries + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, chains, c->d_chain.p, (size_t)c->n_pairs * sizeof(mdbg_chain)));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, match_offsets, c->d_match_off.p, ((size_t)c->n_pairs + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, matches, c->d_matches.p, (size_t)c->n_matches * 4));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)

@@ -98,8 +98,33 @@ __host__ __device__ __forceinline__ uint32_t map_candidate_parent(uint64_t c) { 
 // predecessors of anchor i under the band: j = i - 1 down to i - band (:1147 breaks on i - j > band), not below 0
 __host__ __device__ __forceinline__ uint32_t map_band_count(uint32_t i, uint32_t band) { return i < band ? i : band; }
 
+// What ONE of 64 lanes sees for anchor i: lane t of a trip evaluates predecessor i - 1 - t, 64 a trip, ceil(count / 64) trips; the best
+// packed candidate over the lane's trips.  The maximum over the 64 lanes is the anchor's (score, parent).  score[j], j < i, are final.
+__host__ __device__ __forceinline__ uint64_t map_lane_best(const int32_t *score, const uint32_t *rp, const uint32_t *qp, const uint8_t *rv, uint32_t i, uint32_t band,
+                                                           uint32_t lane) {
+    const uint32_t ri = rp[i], qi = qp[i], rvi = rv[i];
+    const uint32_t cnt = map_band_count(i, band);
+    uint64_t best = 0;
+    for (uint32_t base = 0; base < cnt; base += 64u) {
+        const uint32_t t = base + lane;
+        if (t < cnt) {
+            const uint32_t j = i - 1u - t;
+            const uint64_t c = map_candidate(score[j], map_pred_gap(ri, qi, rvi, rp[j], qp[j], rv[j]), j);
+            best = c > best ? c : best;
+        }
+    }
+    return best;
+}
+
 // the best anchor of a pair: the largest score, on a tie the smallest i (:963-967 replaces on > only, i ascending)
 __host__ __device__ __forceinline__ bool map_better_end(int32_t score, int32_t best_so_far) { return score > best_so_far; }
+
+// the chain that ends at best_i, walked by its parents: its length, and its root (the anchor without a parent)
+__host__ __device__ __forceinline__ uint32_t map_chain_walk(const uint32_t *parent, uint32_t best_i, uint32_t *root) {
+    uint32_t len = 0;
+    for (uint32_t at = best_i; at != MAP_NO_PARENT; at = parent[at]) { *root = at; len++; }
+    return len;
+}
 
 // What chainAnchors leaves of a chain (:1017-1047).  `first` is the BEST anchor, `last` the root of its chain.  The index differences
 // are taken in 32 bits without sign and widened, as the reference's u_int32_t arithmetic does.

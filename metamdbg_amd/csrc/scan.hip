@@ -301,12 +301,6 @@ __device__ __forceinline__ uint32_t window_sq_sum(uint64_t x0, uint64_t x1, uint
     return sum;
 }
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // sum of a 32-bit value over the wave, as a scalar; the caller sees to it that the sum fits 32 bits.  The ladder of
 // wave_inclusive_sum_dpp and one v_readlane: 7 vector instructions and no LDS crossbar where six rounds of 64-bit
 // __shfl_xor took 12 ds_bpermute, their addresses and 12 adds with carry.

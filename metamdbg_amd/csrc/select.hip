@@ -128,14 +128,11 @@ __global__ __launch_bounds__(256) void select_kernel(SelectView v, uint64_t n_qu
     __shared__ uint32_t s_words[4][SELECT_LDS_POSITIONS / 4u];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (;;) {
-        // every turn begins at a point all lanes pass together, and every query takes ONE path to the end of the turn (mapper.hip, map_chain_kernel)
-        wave_lds_sync();
-        uint32_t lo = 0, hi = 0;
-        if (lane == 0) { const unsigned long long drawn = atomicAdd(counter, 1ull); lo = (uint32_t)drawn; hi = (uint32_t)(drawn >> 32); }
-        const uint64_t q = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+        wave_lds_sync();          // the turn's common start, one path to its end (wave_draw)
+        const uint64_t q = wave_draw(counter);
         if (q >= n_queries) break;
         const uint64_t c0 = v.cand_off[q];
-        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v.cand_off[q + 1u] - c0));
+        const uint32_t n = wave_uniform_u32((uint32_t)(v.cand_off[q + 1u] - c0));
         const uint64_t extent = v.extent[q];
         const bool in_lds = extent <= SELECT_LDS_POSITIONS;                    // the same in every lane
         uint8_t *count = in_lds ? reinterpret_cast<uint8_t *>(s_words[wave]) : g_count + v.spill_off[q];
@@ -144,8 +141,8 @@ __global__ __launch_bounds__(256) void select_kernel(SelectView v, uint64_t n_qu
             wave_lds_sync();
         }
         for (uint32_t k = 0; k < n; k++) {
-            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.order[c0 + k]);
-            const uint32_t len = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len[c]);
+            const uint32_t c = wave_uniform_u32(v.order[c0 + k]);
+            const uint32_t len = wave_uniform_u32(v.len[c]);
             const uint32_t *list = v.list[c];
             bool taken = false;
             for (uint32_t base = 0; base < len; base += 64u) {
@@ -494,11 +491,10 @@ extern "C" int mdbg_selection_info(const mdbg_selection *s, uint64_t info[4]) {
 extern "C" int mdbg_selection_to_host(mdbg_ctx *ctx, const mdbg_selection *s, uint64_t *sel_offsets, mdbg_selected *rows, uint64_t *match_offsets, uint32_t *matches) try {
     if (!ctx || !s) return set_error(ctx, MDBG_EINVAL, "mdbg_selection_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(sel_offsets, s->d_sel_off.p, ((size_t)s->n_queries + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(rows, s->d_rows.p, (size_t)s->n_selected * sizeof(mdbg_selected)));
-    MDBG_HIP_CHECK(ctx, dl(match_offsets, s->d_match_off.p, ((size_t)s->n_selected + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(matches, s->d_matches.p, (size_t)s->n_matches * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, sel_offsets, s->d_sel_off.p, ((size_t)s->n_queries + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, rows, s->d_rows.p, (size_t)s->n_selected * sizeof(mdbg_selected)));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, match_offsets, s->d_match_off.p, ((size_t)s->n_selected + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, matches, s->d_matches.p, (size_t)s->n_matches * 4));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)

@@ -276,17 +276,16 @@ extern "C" int mdbg_spans_to_host(mdbg_ctx *ctx, const mdbg_spans *s, uint64_t *
     if (!ctx || !s) return set_error(ctx, MDBG_EINVAL, "mdbg_spans_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t n = s->n_reads, m = s->n_min, w = s->n_windows;
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(window_offsets, s->d_woff.p, (n + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(min_start, s->d_s.p, m * 4));
-    MDBG_HIP_CHECK(ctx, dl(min_end, s->d_e.p, m * 4));
-    MDBG_HIP_CHECK(ctx, dl(hash_lo, s->d_lo.p, w * 8));
-    MDBG_HIP_CHECK(ctx, dl(hash_hi, s->d_hi.p, w * 8));
-    MDBG_HIP_CHECK(ctx, dl(reversed, s->d_rev.p, w));
-    MDBG_HIP_CHECK(ctx, dl(pos_start, s->d_ps.p, w * 4));
-    MDBG_HIP_CHECK(ctx, dl(pos_end, s->d_pe.p, w * 4));
-    MDBG_HIP_CHECK(ctx, dl(seq_length_start, s->d_ls.p, w * 4));
-    MDBG_HIP_CHECK(ctx, dl(seq_length_end, s->d_le.p, w * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, window_offsets, s->d_woff.p, (n + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, min_start, s->d_s.p, m * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, min_end, s->d_e.p, m * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, hash_lo, s->d_lo.p, w * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, hash_hi, s->d_hi.p, w * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, reversed, s->d_rev.p, w));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pos_start, s->d_ps.p, w * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, pos_end, s->d_pe.p, w * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, seq_length_start, s->d_ls.p, w * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, seq_length_end, s->d_le.p, w * 4));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)

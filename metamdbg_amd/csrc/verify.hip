@@ -7,17 +7,18 @@
 //   the lookup   every read of `reads` may be a neighbour of many targets, so the lookup of a read is made ONCE a call, not once a row: one
 //                sort_u64_pairs over the set's minimizers, key = read << 32 | minimizer, value = the index in the read.  Stable, so a read's
 //                piece [off[r], off[r + 1]) holds its minimizers ascending and equal ones in ascending index.
-//   the join     one wave a row.  The neighbour's piece of the lookup is staged in LDS up to VERIFY_LDS_ANCHORS minimizers; a longer
+//   the join     one wave a row.  The neighbour's piece of the lookup is staged in LDS up to CHAIN_LDS_ANCHORS minimizers; a longer
 //                neighbour is read where it lies -- the same code over another pointer.  The target's indexes are walked 64 a trip, a lane
 //                binary-searches its minimizer's run.  count: the runs' lengths summed over the wave; an exclusive scan places the rows'
 //                anchors.  fill: the same walk, a prefix sum over the trip's lanes gives every lane its place: anchors leave in (ri, qi)
 //                order, which is the reference's sorted order.  No sort of anchors, no atomic.
-//   the chains   as map_chain_kernel: one wave a row, rows drawn from a device counter, lane t evaluates predecessor i - 1 - t, one 64-bit
-//                max of (score << 32 | j).  Scores and parents in LDS up to VERIFY_LDS_ANCHORS anchors, above in a pooled global buffer.
-//                Lane 0 walks the parents twice -- length and root, then the gaps -- and writes the row: no match list leaves the kernel.
+//   the chains   one wave a row, rows drawn from a device counter (wave_draw); the dynamic programme is the mapper's, chain_wave
+//                (chain_wave.hpp).  Lane 0 walks the parents twice -- length and root, then the gaps -- and writes the row: no match list
+//                leaves the kernel.
 //   the rows     one lane a row: the four tests, the identity by table; the kept rows are compacted behind a scan.
 #include "common.hpp"
 #include "objects.hpp"
+#include "chain_wave.hpp"
 #include "verify_dev.hpp"
 
 #include <algorithm>
@@ -38,13 +39,8 @@ namespace mdbg {
 static_assert(sizeof(mdbg_verified) == 64, "a verified row is 64 bytes");
 static_assert(sizeof(mdbg_verify_params) == 32, "mdbg_verify_params is 32 bytes");
 
-constexpr uint32_t VERIFY_LDS_ANCHORS = 1024;     // anchors of a row whose scores and parents fit a wave's share of LDS (8 KB a wave, 32 KB a block);
-                                                  // also the minimizers of a neighbour whose lookup the join stages in LDS (the same 8 KB)
-
 struct VerifyReads { const uint64_t *off; const uint32_t *mins, *pos; const uint8_t *dir; const uint32_t *len; uint32_t n_reads, first_read; };
 struct VerifyAnchors { uint32_t *ri, *qi, *rpos, *qpos; uint8_t *rev; };
-
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // ---- the lookup ---------------------------------------------------------------------------------------------------------------------------
 // one lane a minimizer of the set: the sort's key and value
@@ -67,8 +63,7 @@ __global__ __launch_bounds__(256) void verify_sorted_kernel(const uint64_t *keys
 __global__ __launch_bounds__(256) void verify_longest_read_kernel(const uint64_t *off, uint32_t n_reads, unsigned long long *longest) {
     unsigned long long m = 0;
     for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * 256u) m = max(m, (unsigned long long)(off[r + 1u] - off[r]));
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_xor(m, d, 64); m = o > m ? o : m; }
+    m = wave_max_u64(m);
     if (lane_id() == 0 && m) atomicMax(longest, m);
 }
 
@@ -87,12 +82,6 @@ __global__ __launch_bounds__(256) void verify_row_reads_kernel(const uint64_t *s
 }
 
 // ---- the join -----------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-    return v;
-}
-
 // One wave a row.  sorted / sorted_idx: the lookup.  FILL false: n_anchors[row] = the row's anchors (cut to 32 bits), placed[row] = those that
 // are chained at all (verify_placed_anchors), *longest = the largest placed.  FILL true: the anchors of the rows with a_off[row + 1] >
 // a_off[row], from a_off[row] on, in (ri, qi) order.
@@ -100,15 +89,15 @@ template <bool FILL>
 __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const uint32_t *sorted, const uint32_t *sorted_idx, const uint32_t *row_t, const uint32_t *row_q,
                                                           uint64_t n_rows, uint32_t *n_anchors, uint32_t *placed, unsigned long long *longest, const uint64_t *a_off,
                                                           VerifyAnchors out) {
-    __shared__ uint32_t s_key[4][VERIFY_LDS_ANCHORS];
-    __shared__ uint32_t s_idx[4][VERIFY_LDS_ANCHORS];
+    __shared__ uint32_t s_key[4][CHAIN_LDS_ANCHORS];
+    __shared__ uint32_t s_idx[4][CHAIN_LDS_ANCHORS];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * 256u) >> 6;
     for (uint64_t row = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6; row < n_rows; row += n_waves) {
         // every turn begins at a point all lanes pass together (the last row's lanes have read the staged lookup before it is overwritten),
-        // and what decides a row's path is the same in every lane (mapper.hip, map_chain_kernel)
+        // and what decides a row's path is the same in every lane (common.hpp, wave_draw)
         wave_lds_sync();
-        const uint32_t tl = uniform_u32(row_t[row]), ql = uniform_u32(row_q[row]);
+        const uint32_t tl = wave_uniform_u32(row_t[row]), ql = wave_uniform_u32(row_q[row]);
         const bool present = tl != VERIFY_NO_READ && ql != VERIFY_NO_READ;
         uint64_t base = 0, end = 0;
         if (FILL) { base = a_off[row]; end = a_off[row + 1u]; }
@@ -116,8 +105,8 @@ __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const 
         uint64_t acc = 0;
         if (work) {
             const uint64_t t0 = rd.off[tl], q0 = rd.off[ql];
-            const uint32_t n_t = uniform_u32((uint32_t)(rd.off[tl + 1u] - t0)), n_q = uniform_u32((uint32_t)(rd.off[ql + 1u] - q0));
-            const bool in_lds = n_q <= VERIFY_LDS_ANCHORS;
+            const uint32_t n_t = wave_uniform_u32((uint32_t)(rd.off[tl + 1u] - t0)), n_q = wave_uniform_u32((uint32_t)(rd.off[ql + 1u] - q0));
+            const bool in_lds = n_q <= CHAIN_LDS_ANCHORS;
             if (in_lds) {
                 for (uint32_t k = lane; k < n_q; k += 64u) { s_key[wave][k] = sorted[q0 + k]; s_idx[wave][k] = sorted_idx[q0 + k]; }
                 wave_lds_sync();
@@ -154,60 +143,28 @@ __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const 
 }
 
 // ---- the chains ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t verify_wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// One wave a row.  g_score / g_parent: as many as there are anchors, for the rows above VERIFY_LDS_ANCHORS (null when there is none).
+// One wave a row.  g_score / g_parent: as many as there are anchors, for the rows above CHAIN_LDS_ANCHORS (null when there is none).
 // counters: [0] the next row, [1] chains found.  Every row is written, by lane 0: flags MDBG_VERIFY_CHAIN and the summary, or
 // MDBG_VERIFY_ABSENT / MDBG_VERIFY_TOO_LONG / 0 and zero fields (n_anchors stays for a row without a chain).
 __global__ __launch_bounds__(256) void verify_chain_kernel(VerifyReads rd, const mdbg_selected *sel, const uint32_t *row_t, const uint32_t *row_q, const uint32_t *n_anchors,
                                                            const uint64_t *a_off, uint64_t n_rows, const uint32_t *a_ri, const uint32_t *a_qi, const uint32_t *a_rpos,
                                                            const uint32_t *a_qpos, const uint8_t *a_rev, uint32_t band, unsigned long long *counters, int32_t *g_score,
                                                            uint32_t *g_parent, mdbg_verified *rows) {
-    __shared__ int32_t s_score[4][VERIFY_LDS_ANCHORS];
-    __shared__ uint32_t s_parent[4][VERIFY_LDS_ANCHORS];
+    __shared__ int32_t s_score[4][CHAIN_LDS_ANCHORS];
+    __shared__ uint32_t s_parent[4][CHAIN_LDS_ANCHORS];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
     for (;;) {
-        // every turn begins at a point all lanes pass together, and every row takes ONE path to the end of the turn (mapper.hip, map_chain_kernel)
-        wave_lds_sync();
-        uint32_t lo = 0, hi = 0;
-        if (lane == 0) { const unsigned long long drawn = atomicAdd(counters, 1ull); lo = (uint32_t)drawn; hi = (uint32_t)(drawn >> 32); }
-        const uint64_t p = ((uint64_t)uniform_u32(hi) << 32) | uniform_u32(lo);
+        wave_lds_sync();          // the turn's common start, one path to its end (wave_draw); lane 0 has walked the last row's parents before they are overwritten
+        const uint64_t p = wave_draw(counters);
         if (p >= n_rows) break;
         const uint64_t a0 = a_off[p];
-        const uint32_t n = uniform_u32((uint32_t)(a_off[p + 1u] - a0));     // 0: absent, fewer than 3 anchors, or too long
-        const bool in_lds = n <= VERIFY_LDS_ANCHORS;
+        const uint32_t n = wave_uniform_u32((uint32_t)(a_off[p + 1u] - a0));     // 0: absent, fewer than 3 anchors, or too long -- not chained
+        const bool in_lds = n <= CHAIN_LDS_ANCHORS;
         int32_t *score = in_lds ? s_score[wave] : g_score + a0;
         uint32_t *parent = in_lds ? s_parent[wave] : g_parent + a0;
-        const uint32_t *rp = a_rpos + a0, *qp = a_qpos + a0;
-        const uint8_t *rv = a_rev + a0;
-        int32_t best_score = 0;
-        uint32_t best_i = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t ri = rp[i], qi = qp[i], rvi = rv[i];
-            const uint32_t cnt = map_band_count(i, band);
-            uint64_t best = 0;
-            for (uint32_t b0 = 0; b0 < cnt; b0 += 64u) {
-                const uint32_t t = b0 + lane;
-                if (t < cnt) {
-                    const uint32_t j = i - 1u - t;
-                    const uint64_t c = map_candidate(score[j], map_pred_gap(ri, qi, rvi, rp[j], qp[j], rv[j]), j);
-                    best = c > best ? c : best;
-                }
-            }
-            best = verify_wave_max_u64(best);
-            const int32_t sc = map_candidate_score(best);
-            if (lane == 0) { score[i] = sc; parent[i] = map_candidate_parent(best); }
-            if (in_lds) wave_lds_sync(); else __threadfence_block();         // (the next anchor's lanes read what lane 0 wrote)
-            if (map_better_end(sc, best_score)) { best_score = sc; best_i = i; }
-        }
+        const ChainEnd end = chain_wave(n, a_rpos + a0, a_qpos + a0, a_rev + a0, band, score, parent, in_lds);
         if (lane == 0) {
+            const uint32_t best_i = end.i;
             const uint32_t tl = row_t[p], ql = row_q[p], na = n_anchors[p];
             mdbg_verified row;
             row.neighbour = sel[p].ref_read;
@@ -215,9 +172,8 @@ __global__ __launch_bounds__(256) void verify_chain_kernel(VerifyReads rd, const
             row.n_anchors = row.flags ? 0u : na;
             row.query_reversed = 0u; row.n_matches = row.n_mismatches = row.n_deletions = row.n_insertions = 0;
             row.overhang_start = row.overhang_end = row.align_length = row.n_seeds = row.reference_start = row.reference_end = row.query_start = row.query_end = 0u;
-            uint32_t len = 0, root = best_i;
-            if (n)
-                for (uint32_t at = best_i; at != MAP_NO_PARENT; at = parent[at]) { root = at; len++; }
+            uint32_t root = best_i;
+            const uint32_t len = n ? map_chain_walk(parent, best_i, &root) : 0u;
             if (len >= VERIFY_MIN_CHAIN) {
                 const uint32_t *ri = a_ri + a0, *qi = a_qi + a0;
                 const uint32_t reversed = verify_query_reversed(qi[root], qi[best_i]);
@@ -260,6 +216,22 @@ __global__ __launch_bounds__(256) void verify_kept_kernel(const mdbg_verified *r
     for (uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x; t <= n_targets; t += (uint64_t)gridDim.x * 256u) kept_off[t] = kpos[row_off[t]];
 }
 
+const StepKernel *verify_step_kernels(uint32_t *n) {
+    static const StepKernel k[] = {
+        {"verify_keys", reinterpret_cast<const void *>(verify_keys_kernel), 256, 2},
+        {"verify_sorted", reinterpret_cast<const void *>(verify_sorted_kernel), 256, 2},
+        {"verify_longest_read", reinterpret_cast<const void *>(verify_longest_read_kernel), 256, 2},
+        {"verify_row_reads", reinterpret_cast<const void *>(verify_row_reads_kernel), 256, 2},
+        {"verify_join_count", reinterpret_cast<const void *>(verify_join_kernel<false>), 256, 2},
+        {"verify_join_fill", reinterpret_cast<const void *>(verify_join_kernel<true>), 256, 2},
+        {"verify_chain", reinterpret_cast<const void *>(verify_chain_kernel), 256, 2},
+        {"verify_rows", reinterpret_cast<const void *>(verify_rows_kernel), 256, 2},
+        {"verify_kept", reinterpret_cast<const void *>(verify_kept_kernel), 256, 2},
+    };
+    *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
+    return k;
+}
+
 // a set mdbg_map_verify can read: positions, directions and read lengths present, CSR order
 static int verify_set_ready(mdbg_ctx *ctx, const mdbg_minimizers *m) {
     if (!m->d_pos.p || !m->d_dir.p || !m->d_len.p)
@@ -279,7 +251,7 @@ static int verify_params_ok(mdbg_ctx *ctx, const char *who, const mdbg_verify_pa
 
 using namespace mdbg;
 
-extern "C" uint32_t mdbg_verify_lds_anchors(void) { return VERIFY_LDS_ANCHORS; }
+extern "C" uint32_t mdbg_verify_lds_anchors(void) { return CHAIN_LDS_ANCHORS; }
 
 extern "C" int mdbg_verify_min_matches(const mdbg_verify_params *p, uint32_t n_seeds_max, uint32_t *min_matches) {
     if (!p || !min_matches || p->minimizer_size == 0 || p->min_identity != p->min_identity || n_seeds_max == 0xFFFFFFFFu) return MDBG_EINVAL;      // (2^32 - 1: s <= n_seeds_max would never end)
@@ -379,7 +351,7 @@ extern "C" int mdbg_map_verify(mdbg_ctx *ctx, const mdbg_selection *sel, uint32_
     DevBuf<unsigned long long> counters;
     DevBuf<uint64_t> kpos;
     MDBG_TRY(a_ri.alloc(ctx, total)); MDBG_TRY(a_qi.alloc(ctx, total)); MDBG_TRY(a_rpos.alloc(ctx, total)); MDBG_TRY(a_qpos.alloc(ctx, total)); MDBG_TRY(a_rev.alloc(ctx, total));
-    const bool spill = h_longest[0] > VERIFY_LDS_ANCHORS;      // some row's scores and parents do not fit LDS
+    const bool spill = h_longest[0] > CHAIN_LDS_ANCHORS;      // some row's scores and parents do not fit LDS
     if (spill) { MDBG_TRY(g_score.alloc(ctx, total)); MDBG_TRY(g_parent.alloc(ctx, total)); }
     MDBG_TRY(counters.alloc(ctx, 2)); MDBG_TRY(keep.alloc(ctx, nr)); MDBG_TRY(kpos.alloc(ctx, (size_t)nr + 1));
     MDBG_HIP_CHECK(ctx, hipMemsetAsync(counters.p, 0, 16, ctx->stream));
@@ -433,12 +405,11 @@ extern "C" int mdbg_verification_to_host(mdbg_ctx *ctx, const mdbg_verification 
                                          uint8_t *kept_reversed) try {
     if (!ctx || !v) return set_error(ctx, MDBG_EINVAL, "mdbg_verification_to_host: null argument");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    auto dl = [&](void *dst, const void *src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    MDBG_HIP_CHECK(ctx, dl(row_offsets, v->d_row_off.p, ((size_t)v->n_targets + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(rows, v->d_rows.p, (size_t)v->n_rows * sizeof(mdbg_verified)));
-    MDBG_HIP_CHECK(ctx, dl(kept_offsets, v->d_kept_off.p, ((size_t)v->n_targets + 1) * 8));
-    MDBG_HIP_CHECK(ctx, dl(kept_neighbour, v->d_kept_neighbour.p, (size_t)v->n_kept * 4));
-    MDBG_HIP_CHECK(ctx, dl(kept_reversed, v->d_kept_reversed.p, (size_t)v->n_kept));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, row_offsets, v->d_row_off.p, ((size_t)v->n_targets + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, rows, v->d_rows.p, (size_t)v->n_rows * sizeof(mdbg_verified)));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, kept_offsets, v->d_kept_off.p, ((size_t)v->n_targets + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, kept_neighbour, v->d_kept_neighbour.p, (size_t)v->n_kept * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, kept_reversed, v->d_kept_reversed.p, (size_t)v->n_kept));
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)

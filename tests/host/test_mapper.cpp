@@ -1,5 +1,5 @@
-// test_mapper.cpp -- metamdbg_amd/csrc/mapper_dev.hpp on the host, behind serial copies of the lane loops of mapper.hip's count, fill and
-// chain kernels, against a brute-force transcription of ReadMapper.hpp (the join of AlignReadsLowDensityFunctor::operator(), :726-742;
+// test_mapper.cpp -- metamdbg_amd/csrc/mapper_dev.hpp on the host, behind serial copies of the lane loops of mapper.hip's count and fill
+// kernels and the chain's own lane routine (map_lane_best, map_chain_walk) run lane by lane, against a brute-force transcription of ReadMapper.hpp (the join of AlignReadsLowDensityFunctor::operator(), :726-742;
 // argmaxPosition and chainAnchors, :887-1230, with the reference's own types: float scores, int64 positions, int32 differences).
 // Built with -fsanitize=address,undefined by tests/test_mapper_host.py; prints its counts, which that test holds above zero.
 #define __host__
@@ -62,27 +62,20 @@ static void check_runs(std::mt19937_64 &rng) {
 // ---- chains -------------------------------------------------------------------------------------------------------------------------------
 struct Result { std::vector<int32_t> score; std::vector<uint32_t> parent; uint32_t best = 0; bool found = false; MapChain c{}; std::vector<uint32_t> matches; };
 
-// serial copy of map_chain_kernel: 64 lanes a trip, one max over the candidates
+// chain_wave (chain_wave.hpp) with its 64 lanes in turn: the kernels' own map_lane_best per lane, one max, lane 0's store; then lane 0's walk
 static Result chain_lanes(const std::vector<Anchor> &a, uint32_t band) {
     Result r;
     const uint32_t n = (uint32_t)a.size();
     r.score.assign(n, 0); r.parent.assign(n, 0);
+    std::vector<uint32_t> rp(n), qp(n);
+    std::vector<uint8_t> rv(n);
+    for (uint32_t i = 0; i < n; i++) { rp[i] = a[i].rpos; qp[i] = a[i].qpos; rv[i] = (uint8_t)a[i].rev; }
     int32_t best_score = 0;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t cnt = map_band_count(i, band);
-        uint64_t lane_best[64] = {0};
-        for (uint32_t base = 0; base < cnt; base += 64u) {
-            if (base) g.trips_above_one++;
-            for (uint32_t lane = 0; lane < 64u; lane++) {
-                const uint32_t t = base + lane;
-                if (t >= cnt) continue;
-                const uint32_t j = i - 1u - t;
-                const uint64_t c = map_candidate(r.score[j], map_pred_gap(a[i].rpos, a[i].qpos, a[i].rev, a[j].rpos, a[j].qpos, a[j].rev), j);
-                lane_best[lane] = std::max(lane_best[lane], c);
-            }
-        }
+        g.trips_above_one += cnt ? (cnt - 1u) / 64u : 0u;
         uint64_t best = 0;
-        for (uint64_t c : lane_best) best = std::max(best, c);
+        for (uint32_t lane = 0; lane < 64u; lane++) best = std::max(best, map_lane_best(r.score.data(), rp.data(), qp.data(), rv.data(), i, band, lane));
         uint32_t at_best = 0;
         for (uint32_t t = 0; t < cnt && best; t++) {       // (counted, not used: how many predecessors reach the winning score)
             const uint32_t j = i - 1u - t;
@@ -95,8 +88,8 @@ static Result chain_lanes(const std::vector<Anchor> &a, uint32_t band) {
         if (map_better_end(r.score[i], best_score)) { best_score = r.score[i]; r.best = i; }
     }
     if (!n) return r;
-    uint32_t len = 0, root = r.best;
-    for (uint32_t at = r.best; at != MAP_NO_PARENT; at = r.parent[at]) { root = at; len++; }
+    uint32_t root = r.best;
+    const uint32_t len = map_chain_walk(r.parent.data(), r.best, &root);
     if (len < MAP_MIN_CHAIN) return r;
     r.found = true;
     r.c = map_chain_fields(best_score, len, a[r.best].qidx, a[root].qidx, a[r.best].ridx, a[root].ridx, a[r.best].rpos, a[root].rpos);

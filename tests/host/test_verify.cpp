@@ -1,5 +1,5 @@
 // test_verify.cpp -- metamdbg_amd/csrc/verify_dev.hpp (and the chain rules of mapper_dev.hpp it reuses) on the host, behind serial copies of
-// the lane loops of verify.hip's count, fill and chain kernels and of lane 0's walk, against a brute-force transcription of
+// the lane loops of verify.hip's count and fill kernels and of lane 0's second walk, and the chain's own map_lane_best lane by lane, against a brute-force transcription of
 // filterAlignments' join (ReadCorrection.hpp:5051-5069) and MinimizerChainer.hpp (the sort :154-159, chainAnchors / argmaxPosition :735-961
 // with float scores, the summary :274-673 with the reference's own loops).  Built with -fsanitize=address,undefined by
 // tests/test_verify_host.py; prints its counts, which that test holds above zero.
@@ -77,36 +77,30 @@ static std::vector<Anchor> fill_anchors(const Read &t, const Read &q, const std:
     return out;
 }
 
-// verify_chain_kernel: lane t evaluates predecessor i - 1 - t, one max of the packed candidates; then lane 0's first walk.  Root first.
+// chain_wave (chain_wave.hpp), its 64 lanes in turn: the kernels' own map_lane_best, one max, lane 0's store; then map_chain_walk.  Root first.
 static std::vector<uint32_t> chain_lanes(const std::vector<Anchor> &a, uint32_t band) {
     const uint32_t n = (uint32_t)a.size();
     std::vector<int32_t> score(n);
-    std::vector<uint32_t> parent(n);
+    std::vector<uint32_t> parent(n), rp(n), qp(n);
+    std::vector<uint8_t> rv(n);
+    for (uint32_t i = 0; i < n; i++) { rp[i] = a[i].rpos; qp[i] = a[i].qpos; rv[i] = (uint8_t)a[i].rev; }
     int32_t best_score = 0;
     uint32_t best_i = 0;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t cnt = map_band_count(i, band);
-        uint64_t lanes[64] = {0};
-        for (uint32_t b0 = 0; b0 < cnt; b0 += 64u) {
-            if (b0) g.trips_above_one++;
-            for (uint32_t lane = 0; lane < 64u; lane++) {
-                const uint32_t t = b0 + lane;
-                if (t >= cnt) continue;
-                const uint32_t j = i - 1u - t;
-                const uint64_t c = map_candidate(score[j], map_pred_gap(a[i].rpos, a[i].qpos, a[i].rev, a[j].rpos, a[j].qpos, a[j].rev), j);
-                lanes[lane] = c > lanes[lane] ? c : lanes[lane];
-            }
-        }
+        g.trips_above_one += cnt ? (cnt - 1u) / 64u : 0u;
         uint64_t best = 0;
-        for (uint64_t c : lanes) best = c > best ? c : best;
+        for (uint32_t lane = 0; lane < 64u; lane++) best = std::max(best, map_lane_best(score.data(), rp.data(), qp.data(), rv.data(), i, band, lane));
         score[i] = map_candidate_score(best);
         parent[i] = map_candidate_parent(best);
         if (map_better_end(score[i], best_score)) { best_score = score[i]; best_i = i; }
     }
     std::vector<uint32_t> walk;
-    if (n)
-        for (uint32_t at = best_i; at != MAP_NO_PARENT; at = parent[at]) walk.push_back(at);
-    std::reverse(walk.begin(), walk.end());
+    if (!n) return walk;
+    uint32_t root = best_i;
+    walk.resize(map_chain_walk(parent.data(), best_i, &root));
+    for (uint32_t k = (uint32_t)walk.size(), at = best_i; k > 0; at = parent[at]) walk[--k] = at;
+    CHECK(walk.front() == root && parent[root] == MAP_NO_PARENT);
     return walk;
 }
 

@@ -285,6 +285,35 @@ def test_empty_selection_and_targets_outside_the_reads(ctx):
     assert np.array_equal(got["kept_offsets"], [0, 0, 0]) and len(got["kept_neighbour"]) == 0
 
 
+def test_timers_and_kernel_attributes(ctx):
+    cfg = next(c for c in CONFIGS if c["name"] == "band5")
+    d = vm.load_fixture("band5")
+    m, sel = upload(ctx, vm.fixture_reads(d)), selection(ctx, d["sel_offsets"], d["sel_neighbour"])
+    ctx.timing(True)
+    ctx.timing_reset()
+    try:
+        v = ctx.map_verify(sel, m, **vm.fixture_params(cfg))
+        ctx.synchronize()
+        counts = {name: ctx.timing_get(name)[1] for name in ("verify_join", "verify_chains", "verify_rows", "radix_sort")}
+    finally:
+        ctx.timing(False)
+    # join: the keys in front of the sort; sorted + longest read + the rows' reads + count + its scan; fill.  rows: the tests + scan; the kept rows.
+    assert counts == dict(verify_join=3, verify_chains=1, verify_rows=2, radix_sort=1), counts
+    assert v.info()["n_chains"] == cfg["chains"]
+    for h in (v, sel, m):
+        h.free()
+    names = [n for n in ctx.step_kernel_names() if n.startswith("verify")]
+    assert sorted(names) == sorted(["verify_keys", "verify_sorted", "verify_longest_read", "verify_row_reads", "verify_join_count", "verify_join_fill", "verify_chain",
+                                    "verify_rows", "verify_kept"])
+    # four waves a block, each with two arrays of 32-bit words, verify_lds_anchors long: scores and parents (chain), keys and indexes (join)
+    wave_arrays = 4 * 2 * 4 * ctx.verify_lds_anchors()
+    assert wave_arrays == 32768
+    for name in names:
+        a = ctx.kernel_attributes(name)
+        lds = wave_arrays if name in ("verify_chain", "verify_join_count", "verify_join_fill") else 0
+        assert a["scratch"] == 0 and a["role"] == 2 and a["threads"] == 256 and a["static_lds"] == lds, (name, a)
+
+
 def test_two_contexts_on_two_threads(ctx):
     from metamdbg_amd import capi
     cfg = CONFIGS[0]

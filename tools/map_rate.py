@@ -60,7 +60,7 @@ def main():
     mins, off, pos = synthetic_reads(a.genome, a.read_len, a.coverage, 42)
     m = ctx.minimizers_with_positions(mins, off, pos)
     print(f"genome {a.genome} minimizers, {len(off) - 1} reads x {a.read_len} minimizers ({a.coverage:.0f}-fold), band {a.band}; {a.runs} timed runs a step")
-    for name in [n for n in ctx.step_kernel_names() if n.startswith(("map_", "sort_", "select"))]:
+    for name in [n for n in ctx.step_kernel_names() if n.startswith(("map_", "sort_", "select", "verify"))]:
         at = ctx.kernel_attributes(name)
         print(f"kernel {name:18s} registers {at['registers']:3d}  scratch {at['scratch']}  static LDS {at['static_lds']:6d}  threads {at['threads']}")
 
@@ -128,7 +128,7 @@ def main():
     ci = ch.info()
     chain_ms = [x + y for x, y in zip(t["map_chains"], t["map_matches"])]
     total += report("chains + match lists", chain_ms, 13 * n_a + 80 * ci["n_pairs"] + 4 * ci["n_matches"], ci["n_pairs"], "pairs")
-    print(f"chains: {ci['n_chains']} of {ci['n_pairs']} pairs, {ci['n_matches']} matches")
+    print(f"chains: {ci['n_chains']} of {ci['n_pairs']} pairs, {ci['n_matches']} matches; the timer map_chains alone " + " ".join(f"{x:.3f}" for x in t["map_chains"]) + " ms")
     print(f"all steps {total:.3f} ms: {n_a / total / 1e3:.1f} M anchors/s, {ci['n_pairs'] / total / 1e3:.2f} M pairs/s; the anchors' sort is {100 * sort_ms / total:.0f} % of it")
 
     sel, t = timed(lambda: ctx.map_select(ch, a.select_coverage), ("map_select", "radix_sort"))
@@ -140,7 +140,7 @@ def main():
                   n_c, "candidates")
     mean_list = ci["n_matches"] / max(n_c, 1)
     trips = max(1, -(-int(round(mean_list)) // 64))
-    print(f"select: its sort " + " ".join(f"{x:.3f}" for x in t["radix_sort"]) + f" ms; against the chains step of this run: {best / min(chain_ms):.2f}; "
+    print(f"select: the timer map_select alone " + " ".join(f"{x:.3f}" for x in t["map_select"]) + " ms, its sort " + " ".join(f"{x:.3f}" for x in t["radix_sort"]) + f" ms; against the chains step of this run: {best / min(chain_ms):.2f}; "
           f"mean list {mean_list:.1f} matches = {100 * mean_list / (64 * trips):.0f} % of the lanes of its {trips} trip(s)")
     by = ctx.selection_to_alignment_bytes(sel)
     chain_bytes = 8 * (n_q + 1) + 80 * ci["n_pairs"] + 8 * (ci["n_pairs"] + 1) + 4 * ci["n_matches"]
