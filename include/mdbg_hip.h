@@ -214,6 +214,14 @@ int  mdbg_reads_synthetic(mdbg_ctx *ctx, uint64_t seed, uint32_t n_reads, uint32
 int  mdbg_reads_info(const mdbg_reads *r, uint32_t *n_reads, uint64_t *n_bases, uint64_t *n_words);
 /* Copy read `index` back as ASCII (buffer of at least its length; quals may be NULL). */
 int  mdbg_reads_get(mdbg_ctx *ctx, const mdbg_reads *r, uint32_t index, char *bases, char *quals, uint32_t *length);
+/* A batch as the device holds it, read only (what the tests compare bit for bit; copies, no kernel): word_offsets n_reads + 1,
+ * lengths n_reads, words n_words, the invalid and the break mask n_words each (bit i of word w is base 32 w + i of the read
+ * that owns the word), the per-read masked flag n_reads, and the ascending list of masked reads, info[2] of them (size it by a
+ * first call, or give it n_reads).  info = {has_invalid, has_break, n_masked, n_words}.  Any pointer may be NULL.  An array the
+ * batch does not hold -- a mask released because no bit of it was set, a packed batch never marked -- is filled with zeros.
+ * Waits for an upload still in flight, as mdbg_reads_get does. */
+int  mdbg_reads_packed_to_host(mdbg_ctx *ctx, const mdbg_reads *r, uint64_t *word_offsets, uint32_t *lengths, uint64_t *words,
+                               uint32_t *invalid, uint32_t *breaks, uint8_t *masked, uint32_t *masked_list, uint64_t info[4]);
 /* Bulk export of reads [first, first+count) as concatenated ASCII: offsets gets count+1 entries
  * (relative to bases[0]); bases must hold the sum of their lengths (use mdbg_reads_info / a first
  * call with bases == NULL to size it: *n_bytes is always set). */

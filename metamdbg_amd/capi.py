@@ -83,6 +83,7 @@ SIGNATURES = {
                                        C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(_P)]),
     "mdbg_reads_info": (C.c_int, [_P, _u32p, _u64p, _u64p]),
     "mdbg_reads_get": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _u32p]),
+    "mdbg_reads_packed_to_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _u64p]),
     "mdbg_reads_export_ascii": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _u64p]),
     "mdbg_reads_export_qualities": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _u64p]),
     "mdbg_memcpy_device": (C.c_int, [_P, _P, _P, C.c_uint64]),
@@ -967,6 +968,18 @@ class Reads:
         q = C.create_string_buffer(L.value + 1) if with_quality else None
         self.ctx.check(lib().mdbg_reads_get(self.ctx.h, self.h, index, b, q, C.byref(L)))
         return (b.raw[: L.value], q.raw[: L.value]) if with_quality else b.raw[: L.value]
+
+    def packed_to_host(self) -> dict:
+        """The batch as the device holds it (mdbg_reads_packed_to_host): word_offsets, lengths, words, the invalid and break masks, the
+        per-read masked flag, the masked list, and has_invalid / has_break / n_masked / n_words."""
+        info = (C.c_uint64 * 4)()
+        self.ctx.check(lib().mdbg_reads_packed_to_host(self.ctx.h, self.h, None, None, None, None, None, None, None, info))
+        n, n_masked, nw = self.info()["n_reads"], int(info[2]), int(info[3])
+        d = dict(word_offsets=np.zeros(n + 1, np.uint64), lengths=np.zeros(n, np.uint32), words=np.zeros(nw, np.uint64),
+                 invalid=np.zeros(nw, np.uint32), breaks=np.zeros(nw, np.uint32), masked=np.zeros(n, np.uint8), masked_list=np.zeros(n_masked, np.uint32))
+        self.ctx.check(lib().mdbg_reads_packed_to_host(self.ctx.h, self.h, *(_ptr(a) for a in d.values()), info))
+        d.update(has_invalid=bool(info[0]), has_break=bool(info[1]), n_masked=int(info[2]), n_words=int(info[3]))
+        return d
 
     def export_ascii(self, first: int, count: int) -> tuple[np.ndarray, np.ndarray]:
         """(bases u8[], offsets u64[count+1]) of reads [first, first+count)."""

@@ -12,9 +12,9 @@ namespace mdbg {
 #define MDBG_C1 0x87c37b91114253d5ull
 #define MDBG_C2 0x4cf5ad432745937full
 
-__host__ __device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+__host__ __device__ __forceinline__ constexpr uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 
-__host__ __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
+__host__ __device__ __forceinline__ constexpr uint64_t fmix64(uint64_t k) {
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdull;
     k ^= k >> 33;
@@ -56,6 +56,17 @@ __host__ __device__ __forceinline__ uint64_t kmer_hash32(uint32_t v) {
     fmix64_halves(bl, bh);
     return (((uint64_t)ah << 32) | al) + (((uint64_t)bh << 32) | bl);
 }
+
+// The same hash of any 64-bit key, for the host: a k-mer that touches an invalid character has the value -1 in the reference
+// (utils/kmer/Kmer.hpp:567, :580) and is hashed and compared like every other (:1434) -- "skipped as minimizers" only because that
+// one hash, 0.7135 of 2^64, lies above the bound of every usual density.  mdbg_scan compares it with the threshold once (scan.hip).
+constexpr uint64_t kmer_hash64(uint64_t key) {
+    const uint64_t k1 = rotl64(key * MDBG_C1, 31) * MDBG_C2;
+    const uint64_t h1 = (k1 ^ 34ull) + 34ull, h2 = h1 + 34ull;
+    return fmix64(h1) + fmix64(h2);
+}
+constexpr uint64_t INVALID_KMER = ~0ull;
+static_assert(kmer_hash64(INVALID_KMER) == 0xb6a86ca16a85a979ull, "MurmurHash3_x64_128(&-1, 8, 42).h1 (the CPU oracle's orc_kmer_hash gives this value)");
 
 // The upper 32 bits of kmer_hash32(v) without the carry out of the lower halves: the final k ^= k >> 33 of either finaliser
 // touches only the lower half, so hi(h1) = hi(mix(a)) + hi(mix(b)) + carry, carry in {0, 1}.  Four operations per hash less

@@ -630,6 +630,28 @@ extern "C" int mdbg_reads_get(mdbg_ctx *ctx, const mdbg_reads *r, uint32_t index
     return MDBG_OK;
 } MDBG_API_CATCH(ctx)
 
+extern "C" int mdbg_reads_packed_to_host(mdbg_ctx *ctx, const mdbg_reads *r, uint64_t *word_offsets, uint32_t *lengths, uint64_t *words, uint32_t *invalid,
+                                         uint32_t *breaks, uint8_t *masked, uint32_t *masked_list, uint64_t info[4]) try {
+    if (!ctx || !r) return set_error(ctx, MDBG_EINVAL, "mdbg_reads_packed_to_host: null argument");
+    MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    MDBG_HIP_CHECK(ctx, reads_ready_host(r));
+    const size_t n = r->n_reads, nw = r->n_words;
+    if (info) { info[0] = r->has_invalid; info[1] = r->has_break; info[2] = r->n_masked; info[3] = r->n_words; }
+    MDBG_HIP_CHECK(ctx, download_async(ctx, word_offsets, r->d_word_off.p, (n + 1) * 8));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, lengths, r->d_len.p, n * 4));
+    MDBG_HIP_CHECK(ctx, download_async(ctx, words, r->d_words.p, nw * 8));
+    // a mask the batch has released reads as zeros
+    if (invalid && !r->d_invalid.p) memset(invalid, 0, nw * 4);
+    if (breaks && !r->d_break.p) memset(breaks, 0, nw * 4);
+    if (masked && !r->d_masked.p) memset(masked, 0, n);
+    if (r->d_invalid.p) MDBG_HIP_CHECK(ctx, download_async(ctx, invalid, r->d_invalid.p, nw * 4));
+    if (r->d_break.p) MDBG_HIP_CHECK(ctx, download_async(ctx, breaks, r->d_break.p, nw * 4));
+    if (r->d_masked.p) MDBG_HIP_CHECK(ctx, download_async(ctx, masked, r->d_masked.p, n));
+    if (r->d_masked_list.p) MDBG_HIP_CHECK(ctx, download_async(ctx, masked_list, r->d_masked_list.p, (size_t)r->n_masked * 4));
+    MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return MDBG_OK;
+} MDBG_API_CATCH(ctx)
+
 extern "C" int mdbg_reads_export_ascii(mdbg_ctx *ctx, const mdbg_reads *r, uint32_t first, uint32_t count,
                                        char *bases, uint64_t *offsets, uint64_t *n_bytes) try {
     if (!ctx || !r || (uint64_t)first + count > r->n_reads) return set_error(ctx, MDBG_EINVAL, "mdbg_reads_export_ascii: bad range");

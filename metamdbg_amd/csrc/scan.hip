@@ -21,7 +21,7 @@
 // 2-mer upper bound per 64-position window and confirmed by an exact 3-mer pass only when needed.
 //
 // Template variants: HAS_N adds a 1-bit "invalid" stream (characters with bit 3 set, Kmer.hpp:462;
-// k-mers touching one are never selected, :574-580); HAS_QUAL records, for every selected minimizer,
+// k-mers touching one have the value -1, :567 and :574-580, whose hash no density up to 0.71 selects); HAS_QUAL records, for every selected minimizer,
 // the ORIGINAL coordinates [rle[pos], rle[pos+K]) its per-minimizer minimum quality spans
 // (ReadSelection.hpp:1047-1142) -- the quality bytes themselves are read by the gather kernel.
 #include "common.hpp"
@@ -68,6 +68,8 @@ struct ScanArgs {
     uint32_t n_reads;
     uint32_t K;
     uint64_t threshold;           // hash < threshold  <=>  (double)hash < density * 2^64
+    uint32_t select_invalid;      // HAS_N: the hash of the value -1, which a k-mer touching an invalid character has, is below the threshold
+                                  // (densities above 0.7135): such k-mers are then selected, as 0xFFFFFFFF (Kmer.hpp:567, :580, :1434)
     uint32_t trim;                // MinimizerParser::_trimBps: 1 (default) skips the first and last l-mer, 0 keeps them
     uint32_t q_last;              // 1: quality span ends ON the last base of the l-mer (correction scan), 0: at the next run
     const uint32_t *rep;          // sorted repetitive minimizers
@@ -399,6 +401,7 @@ struct KmerTrip {
         } else { a0 = 0; a1 = 0; }   // lanes far beyond nk in a short last trip
         bool sel[PP];
         uint32_t val[PP];
+        bool touches_invalid[PP];
         uint32_t fwd = 0;
 #pragma unroll
         for (int u = 0; u < PP; u++) {
@@ -409,13 +412,17 @@ struct KmerTrip {
             fwd = u == 0 ? digit_reverse(e, K) : (((fwd << 2) | (e >> (2u * K - 2u))) & kmask);
             val[u] = fwd < rev ? fwd : rev;             // canonical; the direction is worked out for the selected few
 #if defined(SCAN_ABLATE) && SCAN_ABLATE == 1
-            sel[u] = (val[u] == 0x12345u) && (j < nk);                                  // ablation: no hash
+            sel[u] = val[u] == 0x12345u;                                                // ablation: no hash
 #else
-            // first k-mer of the read skipped (Kmer.hpp:1395)
             sel[u] = kmer_hash32(val[u]) < a.threshold;
-            if (!INTERIOR) sel[u] = sel[u] && (hp_base + j >= a.trim) && (j < nk);
 #endif
-            if (HAS_N) sel[u] = sel[u] && (istream_extract(SI, j < nk ? j : nk - 1u, kbits) == 0u);   // Kmer.hpp:574-580
+            // a k-mer that touches an invalid character counts with the value -1 (Kmer.hpp:567, :574-580): it is selected when THAT
+            // value's hash is below the threshold (ScanArgs::select_invalid), and then written as 0xFFFFFFFF with its own direction
+            touches_invalid[u] = HAS_N && istream_extract(SI, j < nk ? j : nk - 1u, kbits) != 0u;
+            if (HAS_N && touches_invalid[u]) sel[u] = a.select_invalid != 0u;
+            // first k-mer of the read skipped (Kmer.hpp:1395); the range test comes last, so it holds for both branches above and for
+            // the invalid k-mers alike
+            if (!INTERIOR) sel[u] = sel[u] && (hp_base + j >= a.trim) && (j < nk);
         }
         unsigned long long bal[PP];
         unsigned long long any = 0;
@@ -425,7 +432,7 @@ struct KmerTrip {
             if (a.n_rep) {   // Kmer.hpp:1437
 #pragma unroll
                 for (int u = 0; u < PP; u++) {
-                    if (sel[u]) sel[u] = !rep_contains(a.rep, a.n_rep, val[u]);
+                    if (sel[u]) sel[u] = !rep_contains(a.rep, a.n_rep, touches_invalid[u] ? 0xFFFFFFFFu : val[u]);
                     bal[u] = __ballot(sel[u]);
                 }
             }
@@ -442,7 +449,7 @@ struct KmerTrip {
                     if (idx < cap) {
                         // direction 1 iff the reverse complement is the canonical form, ties included (Kmer.hpp:427)
                         const uint32_t e = (u == 0 ? a0 : __builtin_amdgcn_alignbit(a1, a0, 2 * u)) & kmask;
-                        a.out_min[cap0 + idx] = val[u];
+                        a.out_min[cap0 + idx] = touches_invalid[u] ? 0xFFFFFFFFu : val[u];
                         a.out_pos[cap0 + idx] = p;
                         a.out_dir[cap0 + idx] = (uint8_t)(val[u] == (e ^ comp_mask) ? 1u : 0u);
                         if (HAS_QUAL) {
@@ -698,9 +705,10 @@ __global__ __launch_bounds__(SCAN_BLOCK, (HAS_QUAL || HAS_N) ? 1 : SCAN_MIN_WAVE
             if (HAS_QUAL && HPC) wave_lds_sync();   // carry_orig of the last tile
             const uint32_t e = carry & kmask;
             const uint32_t rev = e ^ comp_mask, fwd = digit_reverse(e, K);
-            const uint32_t d = fwd < rev ? 0u : 1u, v = d ? rev : fwd;
+            const uint32_t d = fwd < rev ? 0u : 1u;
+            uint32_t v = d ? rev : fwd;
             bool s1 = kmer_hash32(v) < a.threshold;
-            if (HAS_N) s1 = s1 && icarry == 0u;
+            if (HAS_N && icarry != 0u) { s1 = a.select_invalid != 0u; v = 0xFFFFFFFFu; }      // (as in KmerTrip::run)
             if (s1 && a.n_rep) s1 = !rep_contains(a.rep, a.n_rep, v);
             if (s1) {
                 if (lane == 0 && nout < cap) {
@@ -2466,6 +2474,7 @@ struct ScanJob {
         a.words = reads->d_words.p; a.word_off = reads->d_word_off.p; a.len = reads->d_len.p;
         a.qual = has_q ? reads->d_qual.p : nullptr; a.qual_off = has_q ? reads->d_qual_off.p : nullptr;
         a.K = p->minimizer_size; a.threshold = density_threshold(p->density);
+        a.select_invalid = kmer_hash64(INVALID_KMER) < a.threshold ? 1u : 0u;
         a.trim = p->no_end_trim ? 0u : 1u; a.q_last = p->quality_window == 1 ? 1u : 0u;
         a.rep = d_rep.p; a.n_rep = p->n_repetitive; a.apply_filters = p->apply_read_filters;
         a.out_flags = m->d_flags.p;
