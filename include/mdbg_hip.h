@@ -849,6 +849,85 @@ int  mdbg_verification_device_ptrs(const mdbg_verification *v, const void *d_ptr
 void mdbg_verification_free(mdbg_verification *v);
 uint32_t mdbg_verify_lds_anchors(void);
 int  mdbg_verify_min_matches(const mdbg_verify_params *p, uint32_t n_seeds_max, uint32_t *min_matches);
+
+/* ---- the kept pairs realigned at assembly density ------------------------------------------------------------------------------------------
+ * The first half of ReadCorrectionFunctor::performPoaCorrection4 (readSelection/ReadCorrection.hpp:5217-5285): everything in front of the
+ * POA graph.  Per target T (the read being corrected) and per kept neighbour N with its flag `reversed` (mdbg_map_verify's kept_neighbour /
+ * kept_reversed), in the kept order:
+ *   1. T' = Utils::getLowDensityMinimizerRead(T, assembly_density), N' likewise (Commons.hpp:2507-2574): a minimizer stays iff
+ *      Murmur3_x64_128 of its value as 8 bytes, seed 42, is below density * 2^64 -- the rule and the code of mdbg_apply_density_threshold.
+ *      Positions, directions and qualities go with the kept minimizers; length and read number stay.
+ *   2. Utils::isReadTooShort(N') (Commons.hpp:2190): fewer than min_minimizers -- the pair is skipped (:5253), MDBG_REALIGN_SHORT.
+ *   3. reversed: N' = N'.toReverseComplement() (Commons.hpp:1042-1079): the order of minimizers, positions, directions and qualities is
+ *      turned round, then dir = !dir and pos = read length - pos.
+ *   4. Anchors (:5263-5279): one for every (i, j) with T'.m[i] == N'.m[j]: ref_position = T'.pos[i], query_position = N'.pos[j],
+ *      reversed = T'.dir[i] != N'.dir[j], indexes i, j into the thinned, oriented reads.
+ *   5. MinimizerChainer::computeChainingAlignment(anchors, T', N', max_chaining_band) (MinimizerChainer.hpp:114-705) exactly as
+ *      mdbg_map_verify documents it: sorted by (ref_position, query_position), fewer than 3 anchors no result, the chain, 3 anchors or
+ *      fewer in it no result.  chain_reversed = f.qi > l.qi of the chain's first and last anchor.
+ *   6. The list _alignments (:330-569) of pairs (ref_index, query_index), "none" for the reference's -1: start_mis pairs (r, q) counting up
+ *      from (f.ri - start_mis, f.qi -+ start_mis); per chain link a -> b the pair of a, then mis + del pairs (r, none), then mis + ins
+ *      pairs (none, q), mis = min(rg, qg) and the excesses deletions and insertions as in mdbg_map_verify; then the pair of l and
+ *      end_mis pairs (r, q).  The query index runs downwards when chain_reversed.  start_mis / end_mis are mdbg_map_verify's, over the
+ *      THINNED counts.
+ *   7. normalizeAlignment (:1015-1111), one forward pass with in-place edits: an entry without a ref_index takes that of the first entry
+ *      at or behind it that has one if the two minimizers are equal, and that entry loses it; an entry without a query_index likewise
+ *      with the roles exchanged; an entry that has lost both is erased.  A robbed entry is visited later in the same pass: moves cascade.
+ *   8. Graph::addAlignment2 (:1179-1271) reads per entry its kind -- insertion (no ref_index), deletion (no query_index), match
+ *      (T'.m[ref_index] == N'.m[query_index]) or mismatch --, ref_index, N'.m[query_index] and N'.quality[query_index]: the entry arrays.
+ * What stays with the caller is the graph: Graph(T'.minimizers, T'.qualities) -- the backbone arrays below --, addAlignment2, computePath2,
+ * trimCorrectedPath.
+ *
+ * mdbg_map_realign  `reads` is the set mdbg_map_verify took (correction density, with positions, directions and lengths; the same refusals);
+ *       the call thins it itself, once.  Qualities are the set's per-minimizer qualities where it has them (a scan output, a concat, a host
+ *       set given mdbg_minimizers_attach_qualities), else 0.  The kept lists are read where they lie, on the device.
+ *       mdbg_map_realign_pairs takes them as host arrays (kept_offsets[n_targets + 1] rising from 0, kept_neighbour, kept_reversed 0 or 1) and
+ *       runs the same routine.  Target t is global read target_first_read + t; every listed target is processed, whatever its thinned
+ *       length (ReadCorrection.hpp:4935-4938 stays the caller's business: target_offsets tells).
+ *       Rows: one mdbg_realigned per kept pair in the kept order (row_offsets = kept_offsets).  A row outside `reads`: MDBG_REALIGN_ABSENT;
+ *       a thinned neighbour below min_minimizers: MDBG_REALIGN_SHORT; 209 715 anchors or more: MDBG_REALIGN_TOO_LONG -- zero fields and no
+ *       entries each.  No chain: flags 0, n_anchors kept.  A chain: MDBG_REALIGN_CHAIN, the counts as AlignmentResult2 holds them (taken
+ *       BEFORE normalisation, as the reference leaves them), _referenceStartIndex / _referenceEndIndex, and n_entries, the length of the
+ *       final list.
+ *       Entries (entry_offsets[rows + 1], after normalisation): ref_index (u32, 0xFFFFFFFF none), query_index (u32, into the thinned,
+ *       oriented neighbour, 0xFFFFFFFF none), query_minimizer (u32), query_quality (u8) -- both 0 for a deletion --, kind (u8: 0 match,
+ *       1 mismatch, 2 insertion, 3 deletion).  The backbone: target_offsets[targets + 1], target_minimizer (u32), target_quality (u8): T' of
+ *       every listed target, with or without a kept row; empty for a target outside `reads`.
+ *       MDBG_EINVAL: max_chaining_band 0, a density that is not > 0, min_minimizers 0, a null argument, a set without positions,
+ *       directions or lengths, kept offsets that do not rise from 0, a kept_reversed other than 0 or 1.  MDBG_ERANGE: 2^32 anchors or
+ *       entries or more in one call.  Empty input gives an empty result.  Timer names: "realign_thin", "realign_join", "realign_chains",
+ *       "realign_lists", "radix_sort".
+ * mdbg_realignment_info  targets, rows, chains, entries.  _to_host: any array may be NULL (target_offsets first tells the backbone's size).
+ *       device_ptrs, in order: row_offsets (u64), rows (mdbg_realigned), entry_offsets (u64), ref_index (u32), query_index (u32),
+ *       query_minimizer (u32), query_quality (u8), kind (u8), target_offsets (u64), target_minimizer (u32), target_quality (u8).
+ * mdbg_realign_lds_entries  raw entries of a row up to which its list is normalised in LDS; a longer list goes through global memory.
+ * mdbg_minimizers_attach_qualities  gives a set that has attached positions one quality byte per minimizer (what a scan output carries).
+ *       MDBG_EINVAL: a set without positions, a scan output. */
+typedef struct mdbg_realignment mdbg_realignment;
+typedef struct { uint32_t max_chaining_band;   /* ReadCorrection.hpp:1739, used at :5281: 62 at 0.025 */
+                 float    assembly_density;    /* Parameters::_minimizerDensity_assembly, 0.005f */
+                 uint32_t min_minimizers;      /* Utils::isReadTooShort: 10 */
+                 uint32_t reserved[5]; } mdbg_realign_params;                       /* 32 bytes */
+#define MDBG_REALIGN_CHAIN     1u   /* a chain of 4 anchors or more; the row's entries are present */
+#define MDBG_REALIGN_ABSENT    4u   /* target or neighbour not in `reads` */
+#define MDBG_REALIGN_TOO_LONG  8u   /* 209 715 anchors or more (as MDBG_VERIFY_TOO_LONG) */
+#define MDBG_REALIGN_SHORT    16u   /* the thinned neighbour has fewer than min_minimizers (:5253) */
+typedef struct { uint32_t neighbour, flags, oriented_reversed /* the flag given */, chain_reversed /* f.qi > l.qi */;
+                 uint32_t n_anchors, n_entries;
+                 int32_t  n_matches, n_mismatches, n_deletions, n_insertions;      /* AlignmentResult2's counts, before normalisation */
+                 uint32_t reference_start_index, reference_end_index; } mdbg_realigned;   /* 48 bytes */
+int  mdbg_map_realign(mdbg_ctx *ctx, const mdbg_verification *v, uint32_t target_first_read, const mdbg_minimizers *reads, uint32_t reads_first_read,
+                      const mdbg_realign_params *p, mdbg_realignment **out);
+int  mdbg_map_realign_pairs(mdbg_ctx *ctx, uint64_t n_targets, const uint64_t *kept_offsets, const uint32_t *kept_neighbour, const uint8_t *kept_reversed,
+                            uint32_t target_first_read, const mdbg_minimizers *reads, uint32_t reads_first_read, const mdbg_realign_params *p, mdbg_realignment **out);
+int  mdbg_realignment_info(const mdbg_realignment *r, uint64_t info[4]);
+int  mdbg_realignment_to_host(mdbg_ctx *ctx, const mdbg_realignment *r, uint64_t *row_offsets, mdbg_realigned *rows, uint64_t *entry_offsets, uint32_t *ref_index,
+                              uint32_t *query_index, uint32_t *query_minimizer, uint8_t *query_quality, uint8_t *kind, uint64_t *target_offsets,
+                              uint32_t *target_minimizer, uint8_t *target_quality);
+int  mdbg_realignment_device_ptrs(const mdbg_realignment *r, const void *d_ptrs[11]);
+void mdbg_realignment_free(mdbg_realignment *r);
+uint32_t mdbg_realign_lds_entries(void);
+int  mdbg_minimizers_attach_qualities(mdbg_ctx *ctx, mdbg_minimizers *m, const uint8_t *qualities);
 /* The library's stable radix sort (8-bit digits, least significant first; a digit in which all keys agree is skipped) on caller-chosen
    data: n uint64 keys from byte keys_at of `keys` and their n uint32 values from byte values_at of `values`, sorted by key in place, equal
    keys keeping their order.  Returns when done.  info (optional): digit passes run, digit passes skipped.  MDBG_EINVAL: a null argument,

@@ -9,8 +9,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmdbg_hip.so")
-SOURCES = ["context", "prims", "reads", "fastx", "inflate", "gzip", "scan", "minimizers", "kminmer", "tables", "shard", "spans", "extract", "stitch", "mapper", "select", "verify", "partition", "multigpu", "step_kernels"]
-HEADERS = ["common.hpp", "complexity_dev.hpp", "murmur.hpp", "prefilter.hpp", "scan_plan.hpp", "partition_plan.hpp", "segments_dev.hpp", "records_dev.hpp", "spans_dev.hpp", "extract_dev.hpp", "extract_plan.hpp", "stitch_dev.hpp", "mapper_dev.hpp", "chain_wave.hpp", "select_dev.hpp", "verify_dev.hpp", "objects.hpp", "table.hpp", "kminmer_dev.hpp", "kminmer_host.hpp", "peerlink.hpp", "deflate_core.hpp", os.path.join("..", "..", "include", "mdbg_hip.h")]
+SOURCES = ["context", "prims", "reads", "fastx", "inflate", "gzip", "scan", "minimizers", "kminmer", "tables", "shard", "spans", "extract", "stitch", "mapper", "select", "verify", "realign", "partition", "multigpu", "step_kernels"]
+HEADERS = ["common.hpp", "complexity_dev.hpp", "murmur.hpp", "prefilter.hpp", "scan_plan.hpp", "partition_plan.hpp", "segments_dev.hpp", "records_dev.hpp", "spans_dev.hpp", "extract_dev.hpp", "extract_plan.hpp", "stitch_dev.hpp", "mapper_dev.hpp", "chain_wave.hpp", "select_dev.hpp", "verify_dev.hpp", "verify_join.hpp", "realign_dev.hpp", "objects.hpp", "table.hpp", "kminmer_dev.hpp", "kminmer_host.hpp", "peerlink.hpp", "deflate_core.hpp", os.path.join("..", "..", "include", "mdbg_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

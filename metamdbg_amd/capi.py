@@ -32,6 +32,12 @@ VERIFIED = np.dtype([("neighbour", "<u4"), ("flags", "<u4"), ("query_reversed", 
                      ("n_matches", "<i4"), ("n_mismatches", "<i4"), ("n_deletions", "<i4"), ("n_insertions", "<i4"),
                      ("overhang_start", "<u4"), ("overhang_end", "<u4"), ("align_length", "<u4"), ("n_seeds", "<u4"),
                      ("reference_start", "<u4"), ("reference_end", "<u4"), ("query_start", "<u4"), ("query_end", "<u4")])     # mdbg_verified
+REALIGN_CHAIN, REALIGN_ABSENT, REALIGN_TOO_LONG, REALIGN_SHORT = 1, 4, 8, 16      # MDBG_REALIGN_*: the flags of a row of mdbg_map_realign
+REALIGN_MATCH, REALIGN_MISMATCH, REALIGN_INSERTION, REALIGN_DELETION = 0, 1, 2, 3   # the kind of an entry
+REALIGN_NONE = 0xFFFFFFFF                                                           # an entry's missing index
+REALIGNED = np.dtype([("neighbour", "<u4"), ("flags", "<u4"), ("oriented_reversed", "<u4"), ("chain_reversed", "<u4"), ("n_anchors", "<u4"), ("n_entries", "<u4"),
+                      ("n_matches", "<i4"), ("n_mismatches", "<i4"), ("n_deletions", "<i4"), ("n_insertions", "<i4"),
+                      ("reference_start_index", "<u4"), ("reference_end_index", "<u4")])     # mdbg_realigned
 
 
 class MdbgError(RuntimeError):
@@ -55,6 +61,10 @@ class MapParams(C.Structure):
 class VerifyParams(C.Structure):
     _fields_ = [("max_chaining_band", C.c_uint32), ("max_overhang", C.c_uint32), ("min_overlap_length", C.c_uint32), ("min_identity", C.c_float),
                 ("minimizer_size", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class RealignParams(C.Structure):
+    _fields_ = [("max_chaining_band", C.c_uint32), ("assembly_density", C.c_float), ("min_minimizers", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
 # name -> (restype, argtypes); every symbol include/mdbg_hip.h declares
@@ -214,6 +224,14 @@ SIGNATURES = {
     "mdbg_verification_free": (None, [_P]),
     "mdbg_verify_lds_anchors": (C.c_uint32, []),
     "mdbg_verify_min_matches": (C.c_int, [C.POINTER(VerifyParams), C.c_uint32, _u32p]),
+    "mdbg_map_realign": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(RealignParams), C.POINTER(_P)]),
+    "mdbg_map_realign_pairs": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(RealignParams), C.POINTER(_P)]),
+    "mdbg_realignment_info": (C.c_int, [_P, _u64p]),
+    "mdbg_realignment_to_host": (C.c_int, [_P, _P] + [_P] * 11),
+    "mdbg_realignment_device_ptrs": (C.c_int, [_P, C.POINTER(_P)]),
+    "mdbg_realignment_free": (None, [_P]),
+    "mdbg_realign_lds_entries": (C.c_uint32, []),
+    "mdbg_minimizers_attach_qualities": (C.c_int, [_P, _P, _P]),
 }
 
 # mdbg_bgzf_block: src u64, then csize, isize, crc, reserved u32
@@ -759,6 +777,33 @@ class Context:
             raise MdbgError(rc, "mdbg_verify_min_matches: invalid argument")
         return out
 
+    # -- the kept pairs realigned at assembly density --------------------------------------------------
+    def map_realign(self, v: "Verification", reads: "Minimizers", target_first_read: int = 0, reads_first_read: int = 0, band: int = 62, assembly_density: float = 0.005,
+                    min_minimizers: int = 10) -> "Realignment":
+        """Every kept pair thinned, oriented, joined, chained, listed and normalised, read from the verification on the device (mdbg_map_realign)."""
+        h = C.c_void_p()
+        p = RealignParams(band, assembly_density, min_minimizers, (C.c_uint32 * 5)())
+        self.check(lib().mdbg_map_realign(self.h, v.h if v is not None else None, target_first_read, reads.h if reads is not None else None, reads_first_read, C.byref(p),
+                                          C.byref(h)))
+        return Realignment(self, h)
+
+    def map_realign_pairs(self, kept_offsets: np.ndarray, kept_neighbour: np.ndarray, kept_reversed: np.ndarray, reads: "Minimizers", target_first_read: int = 0,
+                          reads_first_read: int = 0, band: int = 62, assembly_density: float = 0.005, min_minimizers: int = 10) -> "Realignment":
+        """The same for kept lists held on the host (mdbg_map_realign_pairs)."""
+        off = np.ascontiguousarray(kept_offsets, dtype=np.uint64)
+        nb = np.ascontiguousarray(kept_neighbour, dtype=np.uint32)
+        rv = np.ascontiguousarray(kept_reversed, dtype=np.uint8)
+        h = C.c_void_p()
+        p = RealignParams(band, assembly_density, min_minimizers, (C.c_uint32 * 5)())
+        self.check(lib().mdbg_map_realign_pairs(self.h, len(off) - 1, _ptr(off), _ptr(nb) if len(nb) else None, _ptr(rv) if len(rv) else None, target_first_read,
+                                                reads.h if reads is not None else None, reads_first_read, C.byref(p), C.byref(h)))
+        return Realignment(self, h)
+
+    @staticmethod
+    def realign_lds_entries() -> int:
+        """Raw entries of a row up to which mdbg_map_realign normalises its list in LDS (mdbg_realign_lds_entries)."""
+        return int(lib().mdbg_realign_lds_entries())
+
     def fastx_whole_records(self, text: "DeviceBytes", begin: int, end: int) -> tuple:
         """(cut, format): [begin, cut) of the text holds whole records when more may follow ``end`` (mdbg_fastx_whole_records)."""
         cut, fmt = C.c_uint64(0), C.c_int(0)
@@ -1097,6 +1142,11 @@ class Minimizers:
         n = np.ascontiguousarray(read_lengths, dtype=np.uint32)
         self.ctx.check(lib().mdbg_minimizers_attach_strands(self.ctx.h, self.h, _ptr(d) if len(d) else None, _ptr(n) if len(n) else None))
 
+    def attach_qualities(self, qualities: np.ndarray) -> None:
+        """One quality byte per minimizer, what a scan output carries (mdbg_minimizers_attach_qualities)."""
+        q = np.ascontiguousarray(qualities, dtype=np.uint8)
+        self.ctx.check(lib().mdbg_minimizers_attach_qualities(self.ctx.h, self.h, _ptr(q) if len(q) else None))
+
     def free(self) -> None:
         if self.h:
             lib().mdbg_minimizers_free(self.h)
@@ -1235,6 +1285,35 @@ class Verification(_MapHandle):
     def device_ptrs(self) -> dict:
         p = (C.c_void_p * 5)()
         lib().mdbg_verification_device_ptrs(self.h, p)
+        return dict(zip(self._NAMES, [x or 0 for x in p]))
+
+
+class Realignment(_MapHandle):
+    """One realigned row per kept pair, the normalised alignment lists and the thinned targets (mdbg_map_realign)."""
+    _free = "mdbg_realignment_free"
+    _NAMES = ("row_offsets", "rows", "entry_offsets", "ref_index", "query_index", "query_minimizer", "query_quality", "kind", "target_offsets", "target_minimizer",
+              "target_quality")
+
+    def info(self) -> dict:
+        a = (C.c_uint64 * 4)()
+        lib().mdbg_realignment_info(self.h, a)
+        return dict(zip(("n_targets", "n_rows", "n_chains", "n_entries"), [int(v) for v in a]))
+
+    def to_host(self) -> dict:
+        i = self.info()
+        t, r, e = i["n_targets"], i["n_rows"], i["n_entries"]
+        target_offsets = np.zeros(t + 1, np.uint64)
+        self.ctx.check(lib().mdbg_realignment_to_host(self.ctx.h, self.h, *([None] * 8 + [_ptr(target_offsets), None, None])))      # the backbone's size first
+        b = int(target_offsets[-1])
+        out = dict(row_offsets=np.zeros(t + 1, np.uint64), rows=np.zeros(r, REALIGNED), entry_offsets=np.zeros(r + 1, np.uint64), ref_index=np.zeros(e, np.uint32),
+                   query_index=np.zeros(e, np.uint32), query_minimizer=np.zeros(e, np.uint32), query_quality=np.zeros(e, np.uint8), kind=np.zeros(e, np.uint8),
+                   target_offsets=target_offsets, target_minimizer=np.zeros(b, np.uint32), target_quality=np.zeros(b, np.uint8))
+        self.ctx.check(lib().mdbg_realignment_to_host(self.ctx.h, self.h, *[_ptr(a) for a in out.values()]))
+        return out
+
+    def device_ptrs(self) -> dict:
+        p = (C.c_void_p * 11)()
+        lib().mdbg_realignment_device_ptrs(self.h, p)
         return dict(zip(self._NAMES, [x or 0 for x in p]))
 
 

@@ -235,6 +235,7 @@ const StepKernel *stitch_step_kernels(uint32_t *n);
 const StepKernel *mapper_step_kernels(uint32_t *n);
 const StepKernel *select_step_kernels(uint32_t *n);
 const StepKernel *verify_step_kernels(uint32_t *n);
+const StepKernel *realign_step_kernels(uint32_t *n);
 
 int set_error(mdbg_ctx *ctx, int code, const char *fmt, ...);
 extern thread_local std::string g_last_error;  // for failures before a context exists (per calling thread)

@@ -661,9 +661,18 @@ extern "C" int mdbg_apply_density_threshold(mdbg_ctx *ctx, const mdbg_minimizers
     MDBG_TRY(ensure_canonical(ctx, in));
     if (!(density > 0.0f)) return set_error(ctx, MDBG_EINVAL, "mdbg_apply_density_threshold: density must be > 0");
     MDBG_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<mdbg_minimizers> m(new mdbg_minimizers());
+    const bool side = in->from_scan && in->d_pos.p;
+    MDBG_TRY(density_thin(ctx, in, density, side ? in->d_pos.p : nullptr, in->d_dir.p, in->d_mqual.p, "density_threshold", m.get()));
+    *out = m.release();
+    return MDBG_OK;
+} MDBG_API_CATCH(ctx)
+
+// The thinned form of a canonical set into the empty object m: flag, scan, compaction (Utils::applyDensityThreshold, Commons.hpp:2507-2550).
+// pos non-null: positions, directions and per-minimizer qualities go with the kept minimizers (dir and qual then non-null too).
+int mdbg::density_thin(mdbg_ctx *ctx, const mdbg_minimizers *in, float density, const uint32_t *side_pos, const uint8_t *side_dir, const uint8_t *side_qual, const char *timer_name, mdbg_minimizers *m) {
     const uint32_t n = in->n_reads;
     const uint64_t total = in->n_min;
-    std::unique_ptr<mdbg_minimizers> m(new mdbg_minimizers());
     m->n_reads = n;
     m->from_scan = in->from_scan;
     m->h_mean_quality = in->h_mean_quality;
@@ -674,14 +683,14 @@ extern "C" int mdbg_apply_density_threshold(mdbg_ctx *ctx, const mdbg_minimizers
     MDBG_TRY(pos.alloc(ctx, total + 1));
     MDBG_TRY(m->d_off.alloc(ctx, (size_t)n + 1));
     if (total) {
-        LaunchTimer timer(ctx, "density_threshold");
+        LaunchTimer timer(ctx, timer_name);
         hipLaunchKernelGGL(density_flag_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ctx->stream, in->d_min.p, total,
                            density_threshold(density), flag.p);
     }
     MDBG_TRY(exclusive_scan_u32(ctx, flag.p, pos.p, total));
     MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, &m->n_min, pos.p + total, 8, hipMemcpyDeviceToHost));
     MDBG_TRY(m->d_min.alloc(ctx, m->n_min));
-    const bool side = in->from_scan && in->d_pos.p;
+    const bool side = side_pos != nullptr;
     if (side) {
         MDBG_TRY(m->d_pos.alloc(ctx, m->n_min));
         MDBG_TRY(m->d_dir.alloc(ctx, m->n_min));
@@ -696,16 +705,15 @@ extern "C" int mdbg_apply_density_threshold(mdbg_ctx *ctx, const mdbg_minimizers
         MDBG_HIP_CHECK(ctx, hipMemcpyAsync(m->d_flags.p, in->d_flags.p, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     }
     {
-        LaunchTimer timer(ctx, "density_threshold");
+        LaunchTimer timer(ctx, timer_name);
         hipLaunchKernelGGL(density_offsets_kernel, dim3(grid_for((uint64_t)n + 1, 256)), dim3(256), 0, ctx->stream, in->d_off.p, n, pos.p, m->d_off.p);
         if (total)
             hipLaunchKernelGGL(density_compact_kernel, dim3(grid_for(total, 256)), dim3(256), 0, ctx->stream, total, flag.p, pos.p, in->d_min.p,
-                               side ? in->d_pos.p : nullptr, in->d_dir.p, in->d_mqual.p, m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
+                               side_pos, side_dir, side_qual, m->d_min.p, m->d_pos.p, m->d_dir.p, m->d_mqual.p);
     }
     MDBG_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    *out = m.release();
     return MDBG_OK;
-} MDBG_API_CATCH(ctx)
+}
 
 extern "C" int mdbg_purge_palindromes(mdbg_ctx *ctx, const mdbg_minimizers *in, uint32_t first_k, uint32_t last_k,
                                       mdbg_minimizers **out) try {

@@ -105,6 +105,10 @@ struct mdbg_minimizers {
 namespace mdbg {
 // brings a scattered scan output into CSR order in place (no-op otherwise); the object is logically unchanged
 int ensure_canonical(mdbg_ctx *ctx, const mdbg_minimizers *m);
+// the density-thresholded form of a canonical set into the empty object m (minimizers.hip; mdbg_apply_density_threshold and, with the side
+// arrays of a host set, mdbg_map_realign).  side_pos null: values only.  Waits for the stream (the kept count sizes the arrays).
+int density_thin(mdbg_ctx *ctx, const mdbg_minimizers *in, float density, const uint32_t *side_pos, const uint8_t *side_dir, const uint8_t *side_qual, const char *timer_name,
+                 mdbg_minimizers *m);
 }
 
 // k-min-mer table: output rows (file order) + an open-addressing lookup over the same keys.
@@ -142,6 +146,16 @@ struct mdbg_selection {
     mdbg::DevBuf<mdbg_selected> d_rows;       // n_selected
     mdbg::DevBuf<uint64_t> d_match_off;       // n_selected + 1
     mdbg::DevBuf<uint32_t> d_matches;         // n_matches
+};
+
+// One verified row per selected row and the kept neighbours of every target (verify.hip); mdbg_map_realign (realign.hip) reads the kept lists.
+struct mdbg_verification {
+    uint64_t n_targets = 0, n_rows = 0, n_chains = 0, n_kept = 0;
+    mdbg::DevBuf<uint64_t> d_row_off;         // n_targets + 1
+    mdbg::DevBuf<mdbg_verified> d_rows;       // n_rows
+    mdbg::DevBuf<uint64_t> d_kept_off;        // n_targets + 1
+    mdbg::DevBuf<uint32_t> d_kept_neighbour;  // n_kept
+    mdbg::DevBuf<uint8_t> d_kept_reversed;    // n_kept
 };
 
 // The k-min-mer spans of a batch (spans.hip); mdbg_spans_extract (extract.hip) reads the windows' fields.

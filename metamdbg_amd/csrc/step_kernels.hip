@@ -5,7 +5,7 @@
 using namespace mdbg;
 
 static const StepKernel *step_kernel_at(uint32_t i) {
-    const StepKernel *(*const tables[])(uint32_t *) = {scan_step_kernels, minimizers_step_kernels, prims_step_kernels, partition_step_kernels, extract_step_kernels, stitch_step_kernels, mapper_step_kernels, select_step_kernels, verify_step_kernels};
+    const StepKernel *(*const tables[])(uint32_t *) = {scan_step_kernels, minimizers_step_kernels, prims_step_kernels, partition_step_kernels, extract_step_kernels, stitch_step_kernels, mapper_step_kernels, select_step_kernels, verify_step_kernels, realign_step_kernels};
     for (auto table : tables) {
         uint32_t n = 0;
         const StepKernel *k = table(&n);

@@ -20,27 +20,17 @@
 #include "objects.hpp"
 #include "chain_wave.hpp"
 #include "verify_dev.hpp"
+#include "verify_join.hpp"
+#include "realign_dev.hpp"
 
 #include <algorithm>
 #include <memory>
 #include <vector>
 
-struct mdbg_verification {
-    uint64_t n_targets = 0, n_rows = 0, n_chains = 0, n_kept = 0;
-    mdbg::DevBuf<uint64_t> d_row_off;         // n_targets + 1
-    mdbg::DevBuf<mdbg_verified> d_rows;       // n_rows
-    mdbg::DevBuf<uint64_t> d_kept_off;        // n_targets + 1
-    mdbg::DevBuf<uint32_t> d_kept_neighbour;  // n_kept
-    mdbg::DevBuf<uint8_t> d_kept_reversed;    // n_kept
-};
-
 namespace mdbg {
 
 static_assert(sizeof(mdbg_verified) == 64, "a verified row is 64 bytes");
 static_assert(sizeof(mdbg_verify_params) == 32, "mdbg_verify_params is 32 bytes");
-
-struct VerifyReads { const uint64_t *off; const uint32_t *mins, *pos; const uint8_t *dir; const uint32_t *len; uint32_t n_reads, first_read; };
-struct VerifyAnchors { uint32_t *ri, *qi, *rpos, *qpos; uint8_t *rev; };
 
 // ---- the lookup ---------------------------------------------------------------------------------------------------------------------------
 // one lane a minimizer of the set: the sort's key and value
@@ -84,11 +74,13 @@ __global__ __launch_bounds__(256) void verify_row_reads_kernel(const uint64_t *s
 // ---- the join -----------------------------------------------------------------------------------------------------------------------------
 // One wave a row.  sorted / sorted_idx: the lookup.  FILL false: n_anchors[row] = the row's anchors (cut to 32 bits), placed[row] = those that
 // are chained at all (verify_placed_anchors), *longest = the largest placed.  FILL true: the anchors of the rows with a_off[row + 1] >
-// a_off[row], from a_off[row] on, in (ri, qi) order.
-template <bool FILL>
+// a_off[row], from a_off[row] on, in (ri, qi) order.  ORIENTED (mdbg_map_realign; the verifier's own form is compiled without it): the
+// neighbour of a row with row_rev[row] set is seen reverse-complemented -- its run walked backwards, index, position and direction by
+// realign_dev.hpp's oriented view -- so the anchors still leave in (ri, qi) order of the ORIENTED read.
+template <bool FILL, bool ORIENTED>
 __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const uint32_t *sorted, const uint32_t *sorted_idx, const uint32_t *row_t, const uint32_t *row_q,
                                                           uint64_t n_rows, uint32_t *n_anchors, uint32_t *placed, unsigned long long *longest, const uint64_t *a_off,
-                                                          VerifyAnchors out) {
+                                                          VerifyAnchors out, const uint8_t *row_rev) {
     __shared__ uint32_t s_key[4][CHAIN_LDS_ANCHORS];
     __shared__ uint32_t s_idx[4][CHAIN_LDS_ANCHORS];
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
@@ -107,6 +99,7 @@ __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const 
             const uint64_t t0 = rd.off[tl], q0 = rd.off[ql];
             const uint32_t n_t = wave_uniform_u32((uint32_t)(rd.off[tl + 1u] - t0)), n_q = wave_uniform_u32((uint32_t)(rd.off[ql + 1u] - q0));
             const bool in_lds = n_q <= CHAIN_LDS_ANCHORS;
+            const uint32_t turned = ORIENTED ? wave_uniform_u32(row_rev[row]) : 0u, len_q = ORIENTED ? wave_uniform_u32(rd.len[ql]) : 0u;
             if (in_lds) {
                 for (uint32_t k = lane; k < n_q; k += 64u) { s_key[wave][k] = sorted[q0 + k]; s_idx[wave][k] = sorted_idx[q0 + k]; }
                 wave_lds_sync();
@@ -123,6 +116,13 @@ __global__ __launch_bounds__(256) void verify_join_kernel(VerifyReads rd, const 
                 uint64_t at = base + (incl - run.count);
                 for (uint32_t k = 0; k < run.count; k++, at++) {
                     if (at >= end) break;                                        // (never, for counts this walk produced: nothing outside the row's room)
+                    if (ORIENTED) {
+                        const uint32_t j = idx[realign_run_entry(run.begin, run.count, k, turned)];
+                        out.ri[at] = i; out.qi[at] = realign_oriented_index(j, n_q, turned); out.rpos[at] = rd.pos[t0 + i];
+                        out.qpos[at] = realign_oriented_position(rd.pos[q0 + j], len_q, turned);
+                        out.rev[at] = (uint8_t)map_anchor_reversed(rd.dir[t0 + i], realign_oriented_direction(rd.dir[q0 + j], turned));
+                        continue;
+                    }
                     const uint32_t j = idx[run.begin + k];
                     out.ri[at] = i; out.qi[at] = j; out.rpos[at] = rd.pos[t0 + i]; out.qpos[at] = rd.pos[q0 + j];
                     out.rev[at] = (uint8_t)map_anchor_reversed(rd.dir[t0 + i], rd.dir[q0 + j]);
@@ -222,14 +222,41 @@ const StepKernel *verify_step_kernels(uint32_t *n) {
         {"verify_sorted", reinterpret_cast<const void *>(verify_sorted_kernel), 256, 2},
         {"verify_longest_read", reinterpret_cast<const void *>(verify_longest_read_kernel), 256, 2},
         {"verify_row_reads", reinterpret_cast<const void *>(verify_row_reads_kernel), 256, 2},
-        {"verify_join_count", reinterpret_cast<const void *>(verify_join_kernel<false>), 256, 2},
-        {"verify_join_fill", reinterpret_cast<const void *>(verify_join_kernel<true>), 256, 2},
+        {"verify_join_count", reinterpret_cast<const void *>(verify_join_kernel<false, false>), 256, 2},
+        {"verify_join_fill", reinterpret_cast<const void *>(verify_join_kernel<true, false>), 256, 2},
         {"verify_chain", reinterpret_cast<const void *>(verify_chain_kernel), 256, 2},
         {"verify_rows", reinterpret_cast<const void *>(verify_rows_kernel), 256, 2},
         {"verify_kept", reinterpret_cast<const void *>(verify_kept_kernel), 256, 2},
     };
     *n = (uint32_t)(sizeof(k) / sizeof(k[0]));
     return k;
+}
+
+int verify_lookup(mdbg_ctx *ctx, const char *timer, const VerifyReads &rd, uint64_t n_min, uint64_t *keys, uint32_t *sorted, uint32_t *sorted_idx) {
+    if (!n_min) return MDBG_OK;
+    const unsigned cap = (unsigned)ctx->n_cu * 32u;
+    {
+        LaunchTimer t(ctx, timer);
+        hipLaunchKernelGGL(verify_keys_kernel, dim3(grid_for(n_min, 256, cap)), dim3(256), 0, ctx->stream, rd.off, rd.mins, rd.n_reads, n_min, keys, sorted_idx);
+    }
+    MDBG_TRY(sort_u64_pairs(ctx, keys, sorted_idx, n_min, nullptr));
+    LaunchTimer t(ctx, timer);
+    hipLaunchKernelGGL(verify_sorted_kernel, dim3(grid_for(n_min, 256, cap)), dim3(256), 0, ctx->stream, keys, n_min, sorted);
+    return MDBG_OK;
+}
+
+void verify_join_count(mdbg_ctx *ctx, const VerifyReads &rd, const uint32_t *sorted, const uint32_t *sorted_idx, const uint32_t *row_t, const uint32_t *row_q, uint64_t n_rows,
+                       uint32_t *n_anchors, uint32_t *placed, unsigned long long *longest) {
+    hipLaunchKernelGGL((verify_join_kernel<false, false>), dim3(grid_for(n_rows, 4, (unsigned)ctx->n_cu * 4u)), dim3(256), 0, ctx->stream, rd, sorted, sorted_idx, row_t, row_q, n_rows,
+                       n_anchors, placed, longest, nullptr, VerifyAnchors{nullptr, nullptr, nullptr, nullptr, nullptr}, nullptr);
+}
+
+const void *verify_join_fill_oriented_kernel() { return reinterpret_cast<const void *>(verify_join_kernel<true, true>); }
+
+void verify_join_fill_oriented(mdbg_ctx *ctx, const VerifyReads &rd, const uint32_t *sorted, const uint32_t *sorted_idx, const uint32_t *row_t, const uint32_t *row_q,
+                               const uint8_t *row_reversed, uint64_t n_rows, const uint64_t *a_off, const VerifyAnchors &out) {
+    hipLaunchKernelGGL((verify_join_kernel<true, true>), dim3(grid_for(n_rows, 4, (unsigned)ctx->n_cu * 4u)), dim3(256), 0, ctx->stream, rd, sorted, sorted_idx, row_t, row_q, n_rows,
+                       nullptr, nullptr, nullptr, a_off, out, row_reversed);
 }
 
 // a set mdbg_map_verify can read: positions, directions and read lengths present, CSR order
@@ -332,8 +359,8 @@ extern "C" int mdbg_map_verify(mdbg_ctx *ctx, const mdbg_selection *sel, uint32_
         if (n_reads) hipLaunchKernelGGL(verify_longest_read_kernel, dim3(grid_for(n_reads, 256, cap)), dim3(256), 0, ctx->stream, rd.off, n_reads, longest.p + 1);
         hipLaunchKernelGGL(verify_row_reads_kernel, dim3(grid_for(nr, 256, cap)), dim3(256), 0, ctx->stream, sel->d_sel_off.p, (uint32_t)nt, sel->d_rows.p, nr, target_first_read,
                            reads_first_read, n_reads, row_t.p, row_q.p);
-        hipLaunchKernelGGL(verify_join_kernel<false>, dim3(grid_for(nr, 4, wave_cap)), dim3(256), 0, ctx->stream, rd, sorted.p, sorted_idx.p, row_t.p, row_q.p, nr, n_anchors.p,
-                           placed.p, longest.p, nullptr, none);
+        hipLaunchKernelGGL((verify_join_kernel<false, false>), dim3(grid_for(nr, 4, wave_cap)), dim3(256), 0, ctx->stream, rd, sorted.p, sorted_idx.p, row_t.p, row_q.p, nr,
+                           n_anchors.p, placed.p, longest.p, nullptr, none, nullptr);
         MDBG_TRY(exclusive_scan_u32(ctx, placed.p, a_off.p, nr));
     }
     uint64_t total = 0;
@@ -363,8 +390,8 @@ extern "C" int mdbg_map_verify(mdbg_ctx *ctx, const mdbg_selection *sel, uint32_
     MDBG_HIP_CHECK(ctx, memcpy_sync(ctx, min_matches.p, h_table.data(), (size_t)table_n * 4, hipMemcpyHostToDevice));      // (the host table may go when this returns)
     if (total) {
         LaunchTimer timer(ctx, "verify_join");
-        hipLaunchKernelGGL(verify_join_kernel<true>, dim3(grid_for(nr, 4, wave_cap)), dim3(256), 0, ctx->stream, rd, sorted.p, sorted_idx.p, row_t.p, row_q.p, nr, nullptr, nullptr,
-                           nullptr, a_off.p, VerifyAnchors{a_ri.p, a_qi.p, a_rpos.p, a_qpos.p, a_rev.p});
+        hipLaunchKernelGGL((verify_join_kernel<true, false>), dim3(grid_for(nr, 4, wave_cap)), dim3(256), 0, ctx->stream, rd, sorted.p, sorted_idx.p, row_t.p, row_q.p, nr, nullptr,
+                           nullptr, nullptr, a_off.p, VerifyAnchors{a_ri.p, a_qi.p, a_rpos.p, a_qpos.p, a_rev.p}, nullptr);
     }
     // ---- chains, rows: the kept rows' count is the second host wait -----------------------------------------------------------------------
     {

@@ -75,23 +75,36 @@ struct VerifySummary {
     uint32_t overhang_start, overhang_end, align_length, n_seeds, reference_start, reference_end, query_start, query_end;
 };
 __host__ __device__ __forceinline__ int64_t verify_min64(int64_t a, int64_t b) { return a < b ? a : b; }
+// the runs of index-aligned pairs in front of the first and behind the last anchor (nbStartingMissmatches / nbEndingMissmatches, :291-306);
+// mdbg_map_realign (realign_dev.hpp) emits them as entries
+struct VerifyEdges { int64_t start_mis, end_mis; };
+__host__ __device__ __forceinline__ VerifyEdges verify_edge_mismatches(uint32_t reversed, uint32_t first_ri, uint32_t first_qi, uint32_t last_ri, uint32_t last_qi, uint32_t n_t,
+                                                                       uint32_t n_q) {
+    VerifyEdges e;
+    if (reversed) {
+        e.start_mis = verify_min64((int64_t)first_ri, (int64_t)n_q - (int64_t)first_qi - 1);
+        e.end_mis = verify_min64((int64_t)n_t - (int64_t)last_ri - 1, (int64_t)last_qi);
+    } else {
+        e.start_mis = verify_min64((int64_t)first_ri, (int64_t)first_qi);
+        e.end_mis = verify_min64((int64_t)n_t - (int64_t)last_ri - 1, (int64_t)n_q - (int64_t)last_qi - 1);
+    }
+    return e;
+}
 __host__ __device__ __forceinline__ VerifySummary verify_summary(uint32_t n_matches, const VerifyGaps &gaps, uint32_t first_ri, uint32_t first_qi, uint32_t last_ri,
                                                                  uint32_t last_qi, const uint32_t *tpos, const uint32_t *qpos, uint32_t n_t, uint32_t n_q, uint32_t len_t,
                                                                  uint32_t len_q) {
     VerifySummary s;
     s.query_reversed = verify_query_reversed(first_qi, last_qi);
-    int64_t over_start, over_end, start_mis, end_mis;
+    int64_t over_start, over_end;
     if (s.query_reversed) {
         over_start = verify_min64((int64_t)tpos[first_ri], (int64_t)len_q - (int64_t)qpos[first_qi - 1u]);
-        start_mis = verify_min64((int64_t)first_ri, (int64_t)n_q - (int64_t)first_qi - 1);
         over_end = verify_min64((int64_t)len_t - (int64_t)tpos[last_ri - 1u], (int64_t)qpos[last_qi]);
-        end_mis = verify_min64((int64_t)n_t - (int64_t)last_ri - 1, (int64_t)last_qi);
     } else {
         over_start = verify_min64((int64_t)tpos[first_ri], (int64_t)qpos[first_qi]);
-        start_mis = verify_min64((int64_t)first_ri, (int64_t)first_qi);
         over_end = verify_min64((int64_t)len_t - (int64_t)tpos[last_ri - 1u], (int64_t)len_q - (int64_t)qpos[last_qi - 1u]);
-        end_mis = verify_min64((int64_t)n_t - (int64_t)last_ri - 1, (int64_t)n_q - (int64_t)last_qi - 1);
     }
+    const VerifyEdges edge = verify_edge_mismatches(s.query_reversed, first_ri, first_qi, last_ri, last_qi, n_t, n_q);
+    const int64_t start_mis = edge.start_mis, end_mis = edge.end_mis;
     s.n_matches = (int32_t)n_matches;
     s.n_mismatches = (int32_t)start_mis + gaps.mismatches + (int32_t)end_mis;
     s.n_deletions = gaps.deletions;
